@@ -2,6 +2,14 @@
 """LMI search hot path on MI355X: queries/s on a 10k-query batch (BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W] [--scale 10M|300K|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+workload and the index, warms up, times the K steps, writes the last timed
+step's answer with --dump-outputs, and prints one JSON line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the configuration, and the scan
+durations the timed launches record themselves).  --full adds every other
+measurement and check listed below to the line.
 
 One step = one search of the whole 10k-query batch exactly as the reference
 times it (search.py:116-141): H2D of the query batch from pinned host memory
@@ -13,7 +21,13 @@ started by torchrun or, without one, by this script itself (launch_ranks);
 the corpus striped over the ranks; all ranks search the same batch (strong
 scaling: value = nq / max-over-ranks step time, the RCCL all-gather inside).
 
-Besides the JSON fields of the driver contract the line carries:
+--dump-outputs DIR: DIR/dists.npy and DIR/anns.npy, the (distances, ids) the
+last timed step returned to its caller, both float64 [nq, k] (ids are exact
+in float64); a seeded sample of the rows, with DIR/rows.npy naming them, where
+the two would exceed 64 MB.  The workload and the batches are seeded, so two
+runs with the same arguments answer the same batch in their last step.
+
+With --full the line carries besides the JSON fields of the driver contract:
   roofline      K2 scan kernel: algorithmic bytes per launch / its average
                 duration (HIP events on the launch stream, every timed step)
   cpu_baseline  the oracle restatement (oracle/lmi_oracle.py, "port") timed on
@@ -311,6 +325,26 @@ def h2d_ms(src, dst, reps=10):
     return ms, src.numel() * src.element_size() / (ms * 1e-3) / 1e9
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, dists, anns, seed=0):
+    """--dump-outputs: the last timed step's answer as path/dists.npy and
+    path/anns.npy, float64 [rows, k]; above DUMP_BYTES in all, a seeded sample
+    of the rows (sorted; path/rows.npy holds their indices)."""
+    arrs = {"dists": np.ascontiguousarray(dists, dtype=np.float64),
+            "anns": np.ascontiguousarray(anns, dtype=np.float64)}
+    nq = arrs["dists"].shape[0]
+    per_row = sum(a[0].nbytes for a in arrs.values()) + 8 if nq else 0
+    os.makedirs(path, exist_ok=True)
+    if nq * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(nq, DUMP_BYTES // per_row, replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 STEP_TEXT = {
     "stream": lambda a: ("batch stream (StreamedSearch): per launch, a new host batch staged into "
                          "pinned memory, then on five streams -- the H2D of that batch (copy engine) "
@@ -414,6 +448,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the checks of the timed answers against "
+                         "Searcher.search, the other arithmetic, the one-batch-at-a-time step, the "
+                         "per-stage breakdown, the roofline, recall, list parity, the H2D alone and "
+                         "the CPU baseline (a plain run measures the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's answer as DIR/dists.npy and DIR/anns.npy "
+                         "(float64; a seeded row sample above 64 MB)")
     ap.add_argument("--scale", default="10M", choices=list(SCALES))
     ap.add_argument("--nq", type=int, default=10_000)
     ap.add_argument("--R", type=int, default=4)
@@ -457,6 +499,8 @@ def main():
                          "values); f64 = its arithmetic on float16 data (sklearn promotes). The "
                          "other one is timed too and reported under 'other_dist'")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank, world, local = init_from_env()
     if args.chunk_rows is None:
@@ -569,9 +613,10 @@ def main():
         """The step captured once as a HIP graph (Searcher.graph) and replayed,
         a new host batch staged before every step (GraphedSearch.run(q_nav,
         q_search)): W untimed steps, then K steps bracketed by barrier +
-        synchronize.  Before timing, the first replay's answer must equal an
-        eager step's bit for bit on every rank, else the eager step is timed
-        instead; after timing every answer is checked against its batch."""
+        synchronize.  With --full: before timing, the first replay's answer
+        must equal an eager step's bit for bit on every rank, else the eager
+        step is timed instead; after timing every answer is checked against
+        its batch."""
         pipeline = (not args.no_pipeline) if pipeline is None else pipeline
         try:
             gs = searcher.graph(*hb(0, dist), args.R, k=args.k, dist=dist, pipeline=pipeline)
@@ -588,17 +633,20 @@ def main():
             del gs
             return None if single else timed_eager(dist)
         g_d, g_a = (a.copy() for a in gs.run())
-        e_d, e_a = eager_of(0, dist)
-        same = agree(np.array_equal(g_d, e_d) and np.array_equal(g_a, e_a))
-        checks[f"{'single_' if single else ''}graph_vs_eager_{dist}"] = \
-            "bitwise equal" if same else "DIFFER"
+        same = True
+        if args.full:
+            e_d, e_a = eager_of(0, dist)
+            same = agree(np.array_equal(g_d, e_d) and np.array_equal(g_a, e_a))
+            checks[f"{'single_' if single else ''}graph_vs_eager_{dist}"] = \
+                "bitwise equal" if same else "DIFFER"
         if not same:
             log(f"[bench] graph replay differs from the eager step ({dist}); timing eager launches")
             graph_failed.append("first replay differs from the eager step")
             gs.close()
             del gs
             return None if single else timed_eager(dist)
-        h2d = h2d_ms(gs.h_blk[gs.rank_in_group], gs.d_blk) + (gs.upload_bytes(),)
+        h2d = h2d_ms(gs.h_blk[gs.rank_in_group], gs.d_blk) + (gs.upload_bytes(),) \
+            if args.full else None
         answers = []
 
         def steps(i0, n, keep):
@@ -632,11 +680,13 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device=device)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             el = float(t.item())
-        check_answers(f"{'single_' if single else ''}graph_answers_{dist}", answers, dist)
+        if args.full:
+            check_answers(f"{'single_' if single else ''}graph_answers_{dist}", answers, dist)
         if single:
             return el
         step_mode[dist] = "graph"
-        return el, kernel_ms(dist), answer_of_batch0(answers, dist), h2d
+        # (the scan's own time takes K eager steps of its own: --full)
+        return el, kernel_ms(dist) if args.full else None, answers, h2d
 
     def answer_of_batch0(answers, dist):
         for i, o in answers:
@@ -649,10 +699,11 @@ def main():
         launch t stages batch t mod B (host arrays -> this rank's pinned block)
         and runs one launch -- the H2D, router and plan of that batch, the scan
         of the batch of launch t-2, the merge / replay / D2H of the batch of
-        launch t-3 -- and the host copies the answer out.  Before timing, the
-        first launch's answer must equal an eager step's bit for bit on every
-        rank, else the per-batch step graph is timed instead; after timing every
-        timed answer is checked against Searcher.search of its batch."""
+        launch t-3 -- and the host copies the answer out.  With --full: before
+        timing, the first launch's answer must equal an eager step's bit for
+        bit on every rank, else the per-batch step graph is timed instead; after
+        timing every timed answer is checked against Searcher.search of its
+        batch."""
         try:
             ss = searcher.streamed(*hb(0, dist), args.R, k=args.k, dist=dist, capture=capture)
             ok = 1
@@ -677,9 +728,11 @@ def main():
             return (staged[t - 3] if t >= 3 else 0), o
 
         i0, (s_d, s_a) = launch(0)
-        e_d, e_a = eager_of(i0, dist)
-        same = agree(np.array_equal(s_d, e_d) and np.array_equal(s_a, e_a))
-        checks[f"stream_vs_eager_{dist}"] = "bitwise equal" if same else "DIFFER"
+        same = True
+        if args.full:
+            e_d, e_a = eager_of(i0, dist)
+            same = agree(np.array_equal(s_d, e_d) and np.array_equal(s_a, e_a))
+            checks[f"stream_vs_eager_{dist}"] = "bitwise equal" if same else "DIFFER"
         if not same:
             log(f"[bench] batch stream differs from the eager step ({dist}); timing the step graph")
             stream_failed.append("stream answer differs from the eager step")
@@ -687,7 +740,7 @@ def main():
             del ss
             return timed_graph(dist) if use_graph else timed_eager(dist)
         h2d = h2d_ms(ss.h_stage[0][:ss.staged_words], ss.d_blk[0][:ss.staged_words]) + \
-            (ss.upload_bytes(),)
+            (ss.upload_bytes(),) if args.full else None
         for t in range(1, 1 + args.warmup):
             launch(t)
         answers = []
@@ -712,7 +765,8 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device=device if capture else "cpu")
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             el = float(t.item())
-        check_answers(f"stream_answers_{dist}", answers, dist)
+        if args.full:
+            check_answers(f"stream_answers_{dist}", answers, dist)
         step_mode[dist] = "stream" if capture else "stream (stages launched eagerly: gloo)"
         scan_stats[dist] = {"timed_scans": len(scans), "mean_ms": round(float(np.mean(scans)), 4),
                             "median_ms": round(float(np.median(scans)), 4),
@@ -720,13 +774,15 @@ def main():
                             "max_ms": round(float(np.max(scans)), 4),
                             "how": "HIP events on the scan's stream around each scan graph the "
                                    "timed launches enqueued"} if scans else None
-        return el, (float(np.mean(scans)) if scans else kernel_ms(dist)), \
-            answer_of_batch0(answers, dist), h2d
+        return el, (float(np.mean(scans)) if scans else kernel_ms(dist) if args.full else None), \
+            answers, h2d
 
     def timed(dist):
         """W untimed warmup steps, then K steps bracketed by barrier +
-        synchronize; returns (max-over-ranks seconds, mean scan-kernel ms,
-        the last step's output, (H2D ms, GB/s, bytes) or None)."""
+        synchronize; returns (max-over-ranks seconds, mean scan-kernel ms or
+        None, the timed answers [(batch, (dists, anns))] in step order,
+        (H2D ms, GB/s, bytes) or None).  The checks of the answers, the H2D
+        alone and the scan time where it takes steps of its own: --full."""
         if use_stream:
             return timed_stream(dist)
         if use_graph:
@@ -766,19 +822,66 @@ def main():
                              device=device if torch.distributed.get_backend() == "nccl" else "cpu")
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             el = float(t.item())
-        return el, kms, out, None
+        return el, kms, [(0, out)], None
 
-    el, scan_ms, (dists, anns), h2d = timed(args.dist)
+    el, scan_ms, answers, h2d = timed(args.dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *answers[-1][1])
     ms_step = el / args.steps * 1e3
     # submission to answer: a streamed batch is answered by the fourth launch
     # that sees it (route, plan, scan, merge/replay), a graph-step batch by its own
     lat_ms = ms_step * (4 if step_mode.get(args.dist, "").startswith("stream") else
                         2 if step_mode.get(args.dist) == "graph" and not args.no_pipeline else 1)
     value = args.nq / (el / args.steps)
+    # the fields of every line: the headline figure and what was timed
+    base = {
+        "metric": METRIC, "value": round(value, 1), "unit": "queries/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": round(value / PUBLISHED_QPS_10M, 1) if args.scale == "10M" else None,
+        "dtype": ("f16" if args.dist == "f32" else "f16+f64") if args.corpus == "f16" else
+                 ("f16 scan + f64 re-score" if args.dist == "f32" else "f16 scan + f64"), "data": "synthetic",
+        "config": {"workload": f"{args.scale} {'random unit (configs[4])' if args.scale == '100M' else 'clip768-like'} synthetic ({'fp16-exact' if args.corpus == 'f16' else 'float32, not fp16-exact: split mode'}), {args.n_buckets} "
+                               f"buckets, R={args.R}, k={args.k}, {args.nq} queries, router "
+                               f"{args.arch}", "n": SCALES[args.scale], "d": 768, "nq": args.nq,
+                   "R": args.R, "k": args.k, "n_buckets": args.n_buckets, "router": args.arch,
+                   "parallelism": f"corpus striped over {world} GPU(s)",
+                   "chunk_rows": args.chunk_rows},
+        "full": args.full, "dist": args.dist,
+        "list_exchange": ("RCCL all-gather of the packed lists + K3 over a "
+                          f"{world}-rank group" + (" (LMI_FORCE_EXCHANGE=1: the G > 1 branch on "
+                                                   "one GPU)" if world == 1 else "")
+                          if searcher.exchange else None),
+        "latency_ms_per_batch": round(lat_ms, 3) if lat_ms is not None else None,
+        "batches": {"distinct": B, "held_as": "host numpy arrays (float32 rows; float16 for the "
+                                             "float64 arithmetic)",
+                    "staged": "every timed step stages a new batch (lmi_host_stage_f16 on the "
+                              "host cores into pinned memory) inside the timed region"},
+    }
+
+    def step_text():
+        mode = step_mode.get(args.dist, "eager")
+        return (STEP_TEXT[mode.split(" ")[0]](args) + mode[len(mode.split(" ")[0]):] +
+                (f" (batch stream not used: {stream_failed[0]})" if stream_failed and use_stream else "") +
+                (f" (graph not used: {graph_failed[0]})" if graph_failed else ""))
+
+    if not args.full:
+        # a plain run ends here: the figure, and the scan durations the timed
+        # launches recorded themselves
+        if rank == 0:
+            out = {**base, "step": step_text(),
+                   "scan_kernel_ms": None if scan_ms is None or math.isnan(scan_ms) else round(scan_ms, 4),
+                   "scan_kernel_ms_source": scan_stats.get(args.dist)}
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if world > 1:
+            torch.distributed.barrier()
+        return
+    dists, anns = answer_of_batch0(answers, args.dist)
     # the other arithmetic, timed the same way (float64: the reference's on
     # float16 data, e.g. the real clip768 'emb'; float32: on float32 data)
     other = "f64" if args.dist == "f32" else "f32"
-    el_o, scan_ms_o, (dists_o, anns_o), _ = timed(other)
+    el_o, scan_ms_o, answers_o, _ = timed(other)
+    dists_o, anns_o = answer_of_batch0(answers_o, other)
     # one batch at a time, as the reference's timer sees it (search.py:116-141):
     # the per-batch step graph with the upload inside the step -- H2D of a new
     # host batch, search, D2H of its answer -- nothing of another batch beside it
@@ -862,18 +965,7 @@ def main():
     if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(index, q, classes, lists[args.dist][0], args)
     out = {
-        "metric": METRIC, "value": round(value, 1), "unit": "queries/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-        "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": round(value / PUBLISHED_QPS_10M, 1) if args.scale == "10M" else None,
-        "dtype": ("f16" if args.dist == "f32" else "f16+f64") if args.corpus == "f16" else
-                 ("f16 scan + f64 re-score" if args.dist == "f32" else "f16 scan + f64"), "data": "synthetic",
-        "config": {"workload": f"{args.scale} {'random unit (configs[4])' if args.scale == '100M' else 'clip768-like'} synthetic ({'fp16-exact' if args.corpus == 'f16' else 'float32, not fp16-exact: split mode'}), {args.n_buckets} "
-                               f"buckets, R={args.R}, k={args.k}, {args.nq} queries, router "
-                               f"{args.arch}", "n": SCALES[args.scale], "d": 768, "nq": args.nq,
-                   "R": args.R, "k": args.k, "n_buckets": args.n_buckets, "router": args.arch,
-                   "parallelism": f"corpus striped over {world} GPU(s)",
-                   "chunk_rows": args.chunk_rows},
+        **base,
         "roofline": roof, "cpu_baseline": cpu,
         "recall": round(recall, 4), "recall_exact_semantics": round(recall_x, 4),
         "recall_sample": sample, "breakdown_ms": breakdown, "parity": parity,
@@ -883,21 +975,8 @@ def main():
                                          "in_step": True,
                                          "overlapped": step_mode.get(args.dist, "").startswith("stream") or (
                                              step_mode.get(args.dist) == "graph" and not args.no_pipeline)},
-        "dist": args.dist,
-        "list_exchange": ("RCCL all-gather of the packed lists + K3 over a "
-                          f"{world}-rank group" + (" (LMI_FORCE_EXCHANGE=1: the G > 1 branch on "
-                                                   "one GPU)" if world == 1 else "")
-                          if searcher.exchange else None),
-        "step": STEP_TEXT[step_mode.get(args.dist, "eager").split(" ")[0]](args) +
-                step_mode.get(args.dist, "eager")[len(step_mode.get(args.dist, "eager").split(" ")[0]):] +
-                (f" (batch stream not used: {stream_failed[0]})" if stream_failed and use_stream else "") +
-                (f" (graph not used: {graph_failed[0]})" if graph_failed else ""),
-        "latency_ms_per_batch": round(lat_ms, 3) if lat_ms is not None else None,
+        "step": step_text(),
         "single_batch": single,
-        "batches": {"distinct": B, "held_as": "host numpy arrays (float32 rows; float16 for the "
-                                             "float64 arithmetic)",
-                    "staged": "every timed step stages a new batch (lmi_host_stage_f16 on the "
-                              "host cores into pinned memory) inside the timed region"},
         "other_dist": {"dist": other, "value": round(args.nq / (el_o / args.steps), 1),
                        "ms_per_step": round(el_o / args.steps * 1e3, 3),
                        "scan_kernel_ms": round(scan_ms_o, 4),

@@ -3,18 +3,20 @@
 # WRITE_SIZE, each in its own rocprofv3 run, over its two scans -- the sample
 # scan (scan3_kernel<10, 0, false, 0> on the sample descriptor) and the collect
 # scan (scan3_kernel<10, 0, false, 2>) -- per step, summed (what the bench
-# line's kernel_ms sums too) -> gpurun_out/prof_split/split_pmc_traffic.json
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
-O=gpurun_out/prof_split; mkdir -p $O; export TMPDIR=/tmp
+# line's kernel_ms sums too) -> $OUT/split_pmc_traffic.json (default
+# profile_out/prof_split/ in the repository root)
+cd "$(dirname "$0")/.."
+export OUT=${OUT:-profile_out/prof_split}
+O=$OUT; mkdir -p "$O"; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 400 rocprofv3 --pmc $c --kernel-include-regex "scan3_kernel" --output-format csv \
-     -d $O/pmc_$c -o run -- python3 bench.py --corpus f32 --steps 5 --warmup 1 --no-cpu-baseline --no-single \
-     --recall-sample 20 > $O/pmc_$c.json 2> $O/pmc_$c.err
-  rc=$?; echo "pmc $c rc=$rc"; [ $rc -ne 0 ] && { tail -3 $O/pmc_$c.err; exit $rc; }
+     -d "$O/pmc_$c" -o run -- python3 bench.py --full --corpus f32 --steps 5 --warmup 1 --no-cpu-baseline --no-single \
+     --recall-sample 20 > "$O/pmc_$c.json" 2> "$O/pmc_$c.err"
+  rc=$?; echo "pmc $c rc=$rc"; [ $rc -ne 0 ] && { tail -3 "$O/pmc_$c.err"; exit $rc; }
 done
 python3 - <<'PY'
-import collections, csv, glob, json
-O = "gpurun_out/prof_split"
+import collections, csv, glob, json, os
+O = os.environ["OUT"]
 out = {"by_kernel": {}, "how": "per dispatch means; a split step launches one sample scan (MODE 0 over "
        "the sample descriptor) and one collect scan (MODE 2); FETCH_SIZE / WRITE_SIZE below are their sums"}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):

@@ -9,6 +9,6 @@ T=${TAG:-r06}
 bash tools/gpu_steps.sh \
   ${T}_smoke 300 'python -u -c "import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")"' \
   ${T}_tests 1500 "LMI_TIE_REPORT=gpurun_out/${T}_ties.json python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests/" \
-  ${T}_split 400 "python -u bench.py --corpus f32 --no-cpu-baseline --steps 10 --warmup 3 > gpurun_out/${T}_bench_split.json" \
+  ${T}_split 400 "mkdir -p profile_out && python -u bench.py --full --corpus f32 --no-cpu-baseline --steps 10 --warmup 3 > profile_out/${T}_bench_split.json" \
   && timeout -k 10 1200 bash tools/gpu_profile.sh > gpurun_out/${T}_profile.log 2>&1
 rc=$?; tail -8 gpurun_out/${T}_profile.log; exit $rc
