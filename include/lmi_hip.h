@@ -447,12 +447,14 @@ int lmi_replay_device_phase(int32_t phases, int32_t lists_f64, const int32_t* cl
  * lmi_kmeans_assign: labels_out[i] = argmin_j Σ_e (x[i][e] - cent[j][e])²
  *   (squared L2 in fp32, e ascending, no FMA contraction; ties -> lower j);
  *   dist_out (nullable) receives the minimum.  x [n][d], cent [k][d] f32,
- *   1 <= d <= LMI_KMEANS_MAX_D.
+ *   1 <= d <= LMI_KMEANS_MAX_D (d <= 128: a row in registers; wider rows, e.g.
+ *   the 768-d navigation, through a kernel that tiles the centroids instead;
+ *   the same arithmetic and the same bits).
  * lmi_kmeans_update: cent_out[c] = mean of the points labelled c (fp64 sums
  *   in a fixed order, rounded once), counts_out[c] = their number; rows of
  *   empty clusters are left untouched.  A label outside [0, k) ORs 1 into
  *   *status (device int32) and is skipped.  Deterministic. */
-#define LMI_KMEANS_MAX_D 128
+#define LMI_KMEANS_MAX_D 1024
 int lmi_kmeans_assign(const float* x, int64_t n, int32_t d, const float* cent, int32_t k,
                       int32_t* labels_out, float* dist_out, void* stream);
 size_t lmi_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t k);

@@ -24,6 +24,15 @@
 // The assignment is VALU-bound (3 fp32 ops per point·centroid·dim, 96·122
 // per point at the reference shape) with centroids broadcast from LDS and a
 // point's row held in registers; HBM traffic is one read of X.
+//
+// d > 128 (the 768-d navigation of `--emb emb`; up to LMI_KMEANS_MAX_D = 1024)
+// does not fit a row in registers, so kmeans_assign_wide_kernel tiles the
+// other way: a thread keeps kWideJT partial distances (one tile of centroids)
+// in registers and walks its row in ascending blocks of kWideEB columns, the
+// centroid tile's columns coming from LDS chunk by chunk.  Every (point,
+// centroid) sum is still taken over e ascending with the same three rounded
+// operations, so the result is the narrow kernel's bit for bit; X is read
+// ceil(k / kWideJT) times.
 #include "lmi_common.hpp"
 
 namespace lmi {
@@ -71,6 +80,83 @@ __global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(
             }
             if (acc < best) {  // strict: the first minimum wins
                 best = acc;
+                bi = t0 + j;
+            }
+        }
+    }
+    if (live) {
+        labels[p] = bi;
+        if (dist) dist[p] = best;
+    }
+}
+
+constexpr int kWideJT = 32;   // centroids per register tile (accumulators of a thread)
+constexpr int kWideEB = 32;   // columns of a row held in registers at a time (one 128-byte line)
+constexpr int kWideDC = 128;  // columns of the LDS centroid chunk: kWideJT x kWideDC floats = 16 KiB
+
+// VEC: rows are 16-byte aligned (d % 4 == 0 and x itself aligned) -> float4 loads
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void kmeans_assign_wide_kernel(
+    const float* __restrict__ x, int64_t n, int32_t d, const float* __restrict__ cent, int32_t k,
+    int32_t* __restrict__ labels, float* __restrict__ dist) {
+#pragma clang fp contract(off)
+    __shared__ float4 cs[kWideJT * kWideDC / 4];
+    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = p < n;
+    const float* xp = x + (live ? p : 0) * (int64_t)d;
+    float best = __builtin_inff();
+    int bi = 0;
+    for (int t0 = 0; t0 < k; t0 += kWideJT) {
+        const int nt = min(kWideJT, k - t0);
+        float acc[kWideJT];
+#pragma unroll
+        for (int j = 0; j < kWideJT; ++j) acc[j] = 0.0f;
+        for (int e0 = 0; e0 < d; e0 += kWideDC) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < kWideJT * kWideDC; i += kThreads) {
+                const int j = i / kWideDC, e = e0 + (i - j * kWideDC);
+                reinterpret_cast<float*>(cs)[i] =
+                    (j < nt && e < d) ? cent[(int64_t)(t0 + j) * d + e] : 0.0f;
+            }
+            __syncthreads();
+            const int ne = min(kWideDC, d - e0);  // live columns of this chunk
+            for (int b0 = 0; b0 < ne; b0 += kWideEB) {
+                float xr[kWideEB];
+                if constexpr (VEC) {
+#pragma unroll
+                    for (int e4 = 0; e4 < kWideEB / 4; ++e4) {
+                        const int e = e0 + b0 + 4 * e4;  // e % 4 == 0 and d % 4 == 0: e < d covers e + 3
+                        const float4 v = (live && e < d) ? *reinterpret_cast<const float4*>(xp + e)
+                                                         : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        xr[4 * e4 + 0] = v.x; xr[4 * e4 + 1] = v.y;
+                        xr[4 * e4 + 2] = v.z; xr[4 * e4 + 3] = v.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < kWideEB; ++e)
+                        xr[e] = (live && e0 + b0 + e < d) ? xp[e0 + b0 + e] : 0.0f;
+                }
+#pragma unroll
+                for (int j = 0; j < kWideJT; ++j) {
+                    const float4* cj = cs + (j * kWideDC + b0) / 4;
+                    float a = acc[j];
+#pragma unroll
+                    for (int e4 = 0; e4 < kWideEB / 4; ++e4) {
+                        const float4 c = cj[e4];  // one broadcast LDS read for the wave
+                        float t;
+                        t = xr[4 * e4 + 0] - c.x; a = a + t * t;
+                        t = xr[4 * e4 + 1] - c.y; a = a + t * t;
+                        t = xr[4 * e4 + 2] - c.z; a = a + t * t;
+                        t = xr[4 * e4 + 3] - c.w; a = a + t * t;
+                    }
+                    acc[j] = a;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kWideJT; ++j) {
+            if (j < nt && acc[j] < best) {  // strict: the first minimum wins
+                best = acc[j];
                 bi = t0 + j;
             }
         }
@@ -148,9 +234,15 @@ extern "C" int lmi_kmeans_assign(const float* x, int64_t n, int32_t d, const flo
     else if (d <= 96)
         hipLaunchKernelGGL(kmeans_assign_kernel<96>, grid, dim3(kThreads), 0, s, x, n, d, cent, k,
                            labels_out, dist_out);
-    else
+    else if (d <= 128)
         hipLaunchKernelGGL(kmeans_assign_kernel<128>, grid, dim3(kThreads), 0, s, x, n, d, cent, k,
                            labels_out, dist_out);
+    else if (d % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0)
+        hipLaunchKernelGGL(kmeans_assign_wide_kernel<true>, grid, dim3(kThreads), 0, s, x, n, d, cent,
+                           k, labels_out, dist_out);
+    else
+        hipLaunchKernelGGL(kmeans_assign_wide_kernel<false>, grid, dim3(kThreads), 0, s, x, n, d, cent,
+                           k, labels_out, dist_out);
     LMI_LAUNCH_CHECK("kmeans_assign_kernel");
     return LMI_OK;
 }

@@ -15,7 +15,8 @@ training rows, then ``niter`` Lloyd iterations — assignment
 split of empty clusters on the host (k rows, a few microseconds).  The
 random streams are numpy's, not faiss's mt19937, so samples and inits differ
 from faiss's; the arithmetic is reproduced bit for bit by
-oracle/lmi_oracle.py::kmeans_train (tests/test_gpu_kmeans.py).
+oracle/lmi_oracle.py::kmeans_train (tests/test_gpu_kmeans.py; rows wider than
+128 columns, up to LMI_KMEANS_MAX_D = 1024: tests/test_gpu_kmeans_wide.py).
 
 There is no CPU path: without a HIP device and liblmi_hip.so this raises.
 """

@@ -7,8 +7,10 @@ Same names, architectures and return types as the reference:
   data_X_to_torch  model.py:86-89
   data_to_torch    model.py:92-96
   get_device       model.py:99-111
-  NeuralNetwork    model.py:114-229  train / train_batch unchanged (torch;
-                                     index build is outside the hot path),
+  NeuralNetwork    model.py:114-229  train unchanged (torch); train_batch
+                                     computes only the minibatch the reference's
+                                     loop uses (each epoch's last), bitwise its
+                                     result; LMI_TRAIN_VERBATIM=1: its loop,
                                      predict / predict_proba on the GPU router
                                      kernel (lmi_router, liblmi_hip.so)
   LIDataset        model.py:232-240  (1-based __getitem__, as the reference)
@@ -21,6 +23,7 @@ There is no CPU fallback: on a host without a HIP device these raise.
 """
 from __future__ import annotations
 
+import os
 from typing import Tuple
 
 import numpy as np
@@ -84,6 +87,21 @@ def get_device() -> torch.device:
     return device
 
 
+def last_batch_indices(indices: torch.Tensor, batch_size: int, loader_gen=None,
+                       sampler_gen=None) -> torch.Tensor:
+    """The dataset ids of the LAST minibatch of one pass over
+    DataLoader(ds, batch_size, sampler=SubsetRandomSampler(indices)), drawn as
+    iter(DataLoader) draws them: first the iterator's base seed from the
+    loader's generator (one int64 `random_`), then the sampler's
+    `randperm(len(indices))` from the sampler's generator (None: the global CPU
+    generator); the pass's last batch is the permutation's last
+    `n % batch_size or batch_size` entries, in order."""
+    n = indices.shape[0]
+    torch.empty((), dtype=torch.int64).random_(generator=loader_gen)
+    perm = torch.randperm(n, generator=sampler_gen)
+    return indices[perm[n - (n % batch_size or batch_size):]] if n else indices[:0]
+
+
 class NeuralNetwork(Logger):
     """The router (model.py:114-229); inference runs on K1 (lmi_router)."""
 
@@ -129,17 +147,58 @@ class NeuralNetwork(Logger):
             self.optimizer.step()
         return losses
 
+    def _last_batch_plan(self, loader):
+        """(dataset, indices LongTensor, batch size) when `loader` is the
+        build's kind of DataLoader (LearnedIndex.build) and the model is made of
+        Linear and ReLU only, so that the forwards train_batch throws away have
+        no effect on the weights; None otherwise (the verbatim loop runs)."""
+        D = torch.utils.data
+        if os.environ.get("LMI_TRAIN_VERBATIM") == "1" or type(loader) is not D.DataLoader:
+            return None
+        ds, sampler = loader.dataset, loader.sampler
+        if (loader.num_workers != 0 or type(loader.batch_sampler) is not D.BatchSampler
+                or loader.batch_sampler.sampler is not sampler or loader.drop_last
+                or not loader.batch_size or loader.collate_fn is not D.default_collate
+                or type(sampler) is not D.SubsetRandomSampler
+                or not isinstance(ds, LIDataset) or type(ds).__getitem__ is not LIDataset.__getitem__
+                or hasattr(ds, "__getitems__") or len(sampler.indices) == 0):
+            return None
+        leaves = [m for m in self.model.modules() if not list(m.children())]
+        if not leaves or not all(type(m) in (torch.nn.Linear, torch.nn.ReLU) for m in leaves):
+            return None
+        try:
+            indices = torch.as_tensor(sampler.indices, dtype=torch.int64)
+        except (TypeError, ValueError, RuntimeError):
+            return None
+        return (ds, indices, int(loader.batch_size)) if indices.dim() == 1 else None
+
     def train_batch(self, dataset, epochs=5, logger=None):
         """model.py:174-199, including its behaviour of stepping once per
-        epoch on the last minibatch's loss."""
+        epoch on the last minibatch's loss.
+
+        The reference runs a forward over every minibatch of the loader and
+        uses only the last one's loss.  For the loader LearnedIndex.build makes
+        (see _last_batch_plan) an epoch here computes that last minibatch alone:
+        the same draws from the same generators (last_batch_indices), the same
+        rows, one forward -- bitwise the reference loop's weights, losses and
+        final RNG state (tests/test_train_fast.py).  Any other argument, or
+        LMI_TRAIN_VERBATIM=1, runs the reference's loop as it is."""
         step = max(epochs // 10, 1)
         losses = []
         if logger:
             logger.info(f"Epochs: {epochs}, step: {step}")
+        plan = self._last_batch_plan(dataset)
         for ep in range(epochs):
-            for data_X, data_y in iter(dataset):
-                pred_y = self.model(data_X.to(self.device))
-                curr_loss = self.loss(pred_y, data_y.to(self.device))
+            if plan is not None:
+                ds, indices, batch_size = plan
+                idx = last_batch_indices(indices, batch_size, dataset.generator,
+                                         dataset.sampler.generator) - 1   # LIDataset.__getitem__
+                pred_y = self.model(ds.dataset_x[idx].to(self.device))
+                curr_loss = self.loss(pred_y, ds.dataset_y[idx].to(self.device))
+            else:
+                for data_X, data_y in iter(dataset):
+                    pred_y = self.model(data_X.to(self.device))
+                    curr_loss = self.loss(pred_y, data_y.to(self.device))
             if ep % step == 0 and ep != 0 and logger:
                 logger.info(f"Epoch {ep} | Loss {curr_loss.item():.5f}")
             losses.append(curr_loss.item())
