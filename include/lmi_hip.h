@@ -462,6 +462,58 @@ int lmi_kmeans_update(const float* x, int64_t n, int32_t d, const int32_t* label
                       float* cent_out, int64_t* counts_out, int32_t* status, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* ---- router training on every minibatch (K6) ------------ */
+/* One optimizer step per minibatch of a Linear/ReLU stack under mean
+ * cross-entropy and torch.optim.Adam's defaults (no weight decay, no amsgrad):
+ * what the reference's NeuralNetwork.train does per step (model.py:150-172:
+ * forward, CrossEntropyLoss, backward, Adam.step), taken on every minibatch of
+ * a pass instead of train_batch's one step per epoch (model.py:174-199).
+ * Additions of this section do not change LMI_ABI_VERSION: nothing existing
+ * moves.
+ *
+ * The descriptor holds, per layer, the parameters and Adam's moments, all
+ * device float32, updated in place: W / W_exp_avg / W_exp_avg_sq [out][in]
+ * row-major (torch layout), b / b_exp_avg / b_exp_avg_sq [out].  Any width in
+ * 1..LMI_TRAIN_MAX_DIM, for the input, hidden layers and classes alike. */
+#define LMI_TRAIN_MAX_DIM 1024
+typedef struct lmi_mlp_train_desc {
+    int32_t n_layers;                 /* 1..LMI_MAX_LAYERS */
+    int32_t dims[LMI_MAX_LAYERS + 1]; /* dims[0]=input width ... dims[n_layers]=n_classes */
+    float* W[LMI_MAX_LAYERS];
+    float* b[LMI_MAX_LAYERS];
+    float* W_exp_avg[LMI_MAX_LAYERS];
+    float* W_exp_avg_sq[LMI_MAX_LAYERS];
+    float* b_exp_avg[LMI_MAX_LAYERS];
+    float* b_exp_avg_sq[LMI_MAX_LAYERS];
+} lmi_mlp_train_desc;
+/* Bytes of workspace for minibatches of up to `batch` rows (0 for an invalid
+ * descriptor or batch < 1).  The workspace needs no initialisation. */
+size_t lmi_mlp_train_workspace_bytes(const lmi_mlp_train_desc* desc, int32_t batch);
+/* Enqueues steps first_step .. first_step + n_steps - 1 of one pass on
+ * `stream`, two kernels per step, no host synchronisation.  Step s trains on
+ * the rows x[order[s*batch + i]], i < B_s = min(batch, n_order - s*batch) (the
+ * pass's last step may be short, down to one row; the loss is the mean over
+ * B_s, as DataLoader(drop_last=False) + CrossEntropyLoss() give), with Adam
+ * step count adam_t0 + (s - first_step) + 1:
+ *   m = beta1 m + (1-beta1) g;  v = beta2 v + (1-beta2) g^2;
+ *   p -= (lr / (1-beta1^t)) * m / (sqrt(v) / sqrt(1-beta2^t) + eps).
+ *   x        device [n][ldx] f32 rows;  y  device [n] int32 labels in [0, classes)
+ *   order    device [n_order] int64 row indices in [0, n) (an entry outside is
+ *            treated as a zero row without a label, never read)
+ *   loss_out device [n_steps] f32: the mean loss of step first_step + i at [i]
+ * Gradients and losses are reduced in a fixed order (no float atomics): equal
+ * inputs give bitwise equal results, and a call of n steps equals n calls of
+ * one step.  LMI_E_INVALID for a null pointer, batch < 1, n_layers or a dim out
+ * of range, ldx < dims[0], first_step*batch >= n_order or steps past the end
+ * of order; LMI_E_WORKSPACE for a workspace smaller than
+ * lmi_mlp_train_workspace_bytes(desc, batch) or not 16-byte aligned.  All of
+ * these are checked before any device call. */
+int lmi_mlp_train_steps(const lmi_mlp_train_desc* desc, const float* x, int64_t n, int32_t ldx,
+                        const int32_t* y, const int64_t* order, int64_t n_order, int32_t batch,
+                        int64_t first_step, int64_t n_steps, int64_t adam_t0, double lr,
+                        double beta1, double beta2, double eps, float* loss_out, void* workspace,
+                        size_t ws_bytes, void* stream);
+
 /* ---- kernel timing (measurement only) -------------------------------------- */
 /* While enabled, lmi_bucket_topk records a HIP event pair on its stream around
  * its scan kernel (the roofline kernel).  lmi_timing_read waits for the pairs

@@ -353,9 +353,18 @@ class LearnedIndex(Logger):
         return col
 
     # ---- build (outside the hot path) -------------------------------------
-    def build(self, data, n_categories=100, epochs=100, lr=0.1, model_type='MLP'):
+    def build(self, data, n_categories=100, epochs=100, lr=0.1, model_type='MLP',
+              train_mode='reference'):
         """LearnedIndex.py:197-240: cluster, train the router, label the data
-        with the router's argmax (predict on the GPU router kernel)."""
+        with the router's argmax (predict on the GPU router kernel).
+
+        train_mode 'reference': the reference's train_batch, one optimizer step
+        per epoch on the epoch's last minibatch.  'minibatch' (not in the
+        reference): a step on every minibatch of every epoch, on the fused
+        training kernels (NeuralNetwork.train_minibatch), over the same
+        LIDataset rows and labels."""
+        if train_mode not in ('reference', 'minibatch'):
+            raise ValueError(f"train_mode {train_mode!r}: 'reference' or 'minibatch'")
         s = time.time()
         pg = self._proc_group()
         if pg is None or pg[1] == 0:
@@ -367,7 +376,16 @@ class LearnedIndex(Logger):
                     sampler=torch.utils.data.SubsetRandomSampler(data.index.values.tolist()))
                 nn = NeuralNetwork(input_dim=data.shape[1], output_dim=n_categories, lr=lr,
                                    model_type=model_type)
-                nn.train_batch(train_loader, epochs=epochs, logger=self.logger)
+                if train_mode == 'minibatch':
+                    # the sampler's ids are the frame's labels; LIDataset's
+                    # __getitem__ maps id -> row id - 1
+                    rows = torch.as_tensor(data.index.values, dtype=torch.int64) - 1
+                    whole = torch.equal(rows, torch.arange(len(dataset)))
+                    nn.train_minibatch(dataset.dataset_x if whole else dataset.dataset_x[rows],
+                                       dataset.dataset_y if whole else dataset.dataset_y[rows],
+                                       epochs=epochs, batch_size=256, logger=self.logger)
+                else:
+                    nn.train_batch(train_loader, epochs=epochs, logger=self.logger)
                 self.model = nn
                 pred = nn.predict(data_X_to_torch(data))
             except BaseException as e:

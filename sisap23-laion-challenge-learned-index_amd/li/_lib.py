@@ -48,6 +48,7 @@ LMI_MAX_K_F64 = 240
 LMI_REPLAY_DEVICE_MAX_KR = 32
 LMI_REPLAY_DEVICE_MAX_K = 64
 LMI_KMEANS_MAX_D = 1024
+LMI_TRAIN_MAX_DIM = 1024
 LMI_REFINE_EPS = 2.0 ** -16
 
 # every symbol include/lmi_hip.h declares (tests check the export table)
@@ -78,6 +79,8 @@ EXPORTS = (
     "lmi_kmeans_assign",
     "lmi_kmeans_workspace_bytes",
     "lmi_kmeans_update",
+    "lmi_mlp_train_workspace_bytes",
+    "lmi_mlp_train_steps",
     "lmi_timing_enable",
     "lmi_timing_read",
     "lmi_last_error",
@@ -106,6 +109,20 @@ class MlpDesc(C.Structure):
         ("dims", C.c_int32 * (LMI_MAX_LAYERS + 1)),
         ("W", C.c_void_p * LMI_MAX_LAYERS),
         ("b", C.c_void_p * LMI_MAX_LAYERS),
+    ]
+
+
+class MlpTrainDesc(C.Structure):
+    """lmi_mlp_train_desc: parameters and Adam moments of a Linear/ReLU stack."""
+    _fields_ = [
+        ("n_layers", C.c_int32),
+        ("dims", C.c_int32 * (LMI_MAX_LAYERS + 1)),
+        ("W", C.c_void_p * LMI_MAX_LAYERS),
+        ("b", C.c_void_p * LMI_MAX_LAYERS),
+        ("W_exp_avg", C.c_void_p * LMI_MAX_LAYERS),
+        ("W_exp_avg_sq", C.c_void_p * LMI_MAX_LAYERS),
+        ("b_exp_avg", C.c_void_p * LMI_MAX_LAYERS),
+        ("b_exp_avg_sq", C.c_void_p * LMI_MAX_LAYERS),
     ]
 
 
@@ -177,6 +194,10 @@ _SIGNATURES = {
     "lmi_kmeans_assign": (C.c_int, [_P, _I64, _I32, _P, _I32, _P, _P, _P]),
     "lmi_kmeans_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "lmi_kmeans_update": (C.c_int, [_P, _I64, _I32, _P, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_mlp_train_workspace_bytes": (C.c_size_t, [C.POINTER(MlpTrainDesc), _I32]),
+    "lmi_mlp_train_steps": (C.c_int, [C.POINTER(MlpTrainDesc), _P, _I64, _I32, _P, _P, _I64, _I32, _I64,
+                                      _I64, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _P,
+                                      _P, C.c_size_t, _P]),
     "lmi_timing_enable": (C.c_int, [_I32]),
     "lmi_timing_read": (C.c_int32, [_P, _I32]),
     "lmi_last_error": (C.c_char_p, []),

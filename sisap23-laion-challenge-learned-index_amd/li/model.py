@@ -12,7 +12,10 @@ Same names, architectures and return types as the reference:
                                      loop uses (each epoch's last), bitwise its
                                      result; LMI_TRAIN_VERBATIM=1: its loop,
                                      predict / predict_proba on the GPU router
-                                     kernel (lmi_router, liblmi_hip.so)
+                                     kernel (lmi_router, liblmi_hip.so);
+                                     train_minibatch (not in the reference):
+                                     an Adam step on EVERY minibatch, on the
+                                     fused training kernels (K6, lmi_train)
   LIDataset        model.py:232-240  (1-based __getitem__, as the reference)
 
 predict_proba returns (probs f32 ndarray, classes int64 ndarray), both
@@ -205,6 +208,143 @@ class NeuralNetwork(Logger):
             self.model.zero_grad()
             curr_loss.backward()
             self.optimizer.step()
+        return losses
+
+    # ---- training that steps on every minibatch (K6) --------------------------
+    def _minibatch_linears(self):
+        """The model's Linear layers when train_minibatch's kernels compute
+        exactly what torch would for this object's model, loss and optimizer;
+        ValueError otherwise (there is no torch fallback)."""
+        from . import _lib
+        loss = self.loss
+        if type(loss) is not torch.nn.CrossEntropyLoss:
+            raise ValueError(f"train_minibatch needs CrossEntropyLoss(), not {type(loss).__name__}")
+        if loss.weight is not None:
+            raise ValueError("train_minibatch does not take a loss with class_weight")
+        if loss.reduction != "mean" or loss.ignore_index != -100 or loss.label_smoothing != 0.0:
+            raise ValueError("train_minibatch needs CrossEntropyLoss's default arguments")
+        opt = self.optimizer
+        if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
+            raise ValueError("train_minibatch needs one torch.optim.Adam parameter group")
+        g = opt.param_groups[0]
+        if (tuple(g["betas"]) != (0.9, 0.999) or g["eps"] != 1e-8 or g["weight_decay"] != 0
+                or g["amsgrad"] or g.get("maximize") or g.get("capturable") or g.get("differentiable")
+                or g.get("fused") or isinstance(g["lr"], torch.Tensor)):
+            raise ValueError("train_minibatch needs Adam's default hyperparameters (any lr)")
+        seq = getattr(self.model, "layers", None)
+        mods = list(seq.children()) if isinstance(seq, torch.nn.Sequential) else []
+        linears = [m for m in mods if type(m) is torch.nn.Linear]
+        chain = bool(linears) and len(mods) == 2 * len(linears) - 1 and all(
+            type(m) is (torch.nn.ReLU if i % 2 else torch.nn.Linear) for i, m in enumerate(mods))
+        if not chain or any(m.bias is None for m in linears) or any(
+                a.out_features != b.in_features for a, b in zip(linears, linears[1:])):
+            raise ValueError("train_minibatch needs a plain chain of Linear layers with ReLU between "
+                             "them (not MLP-9)")
+        if len(linears) > _lib.LMI_MAX_LAYERS:
+            raise ValueError(f"more than {_lib.LMI_MAX_LAYERS} Linear layers")
+        dims = [linears[0].in_features] + [m.out_features for m in linears]
+        if max(dims) > _lib.LMI_TRAIN_MAX_DIM:
+            raise ValueError(f"layer width {max(dims)} above LMI_TRAIN_MAX_DIM = {_lib.LMI_TRAIN_MAX_DIM}")
+        params = [p for m in linears for p in (m.weight, m.bias)]
+        if len(params) != len(g["params"]) or any(a is not b for a, b in zip(params, g["params"])):
+            raise ValueError("the optimizer does not hold exactly the model's parameters")
+        if any(p.dtype != torch.float32 for p in params):
+            raise ValueError("train_minibatch trains float32 parameters")
+        return linears
+
+    def _minibatch_desc(self, linears):
+        """(lmi_mlp_train_desc over the parameters and Adam's moments, steps
+        taken so far); creates the optimizer state as Adam._init_group does."""
+        from . import _lib
+        opt = self.optimizer
+        desc = _lib.MlpTrainDesc()
+        desc.n_layers = len(linears)
+        desc.dims[0] = linears[0].in_features
+        t0 = None
+        for i, m in enumerate(linears):
+            desc.dims[i + 1] = m.out_features
+            for p, names in ((m.weight, ("W", "W_exp_avg", "W_exp_avg_sq")),
+                             (m.bias, ("b", "b_exp_avg", "b_exp_avg_sq"))):
+                if not p.is_contiguous() or p.device.type != "cuda":
+                    raise ValueError("parameters must be contiguous on the model's HIP device")
+                st = opt.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if not (st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()):
+                    raise ValueError("Adam's moments must be contiguous")
+                t = int(st["step"])
+                if t0 is not None and t != t0:
+                    raise ValueError("the parameters' Adam step counts differ")
+                t0 = t
+                for name, ten in zip(names, (p, st["exp_avg"], st["exp_avg_sq"])):
+                    getattr(desc, name)[i] = ten.data_ptr()
+        return desc, t0
+
+    def train_minibatch(self, data_X, data_y, epochs=1, batch_size=256, generator=None, logger=None):
+        """`epochs` passes over (data_X, data_y) with one Adam step per
+        minibatch of `batch_size` rows -- what train_batch's loop would do if it
+        stepped inside its inner loop (model.py:185-199) -- on the fused
+        training kernels (lmi_mlp_train_steps; float32).  Each pass visits the
+        rows in the order torch.randperm(n, generator=generator) (None: the
+        global CPU generator, as SubsetRandomSampler draws it); its last
+        minibatch is short when n % batch_size != 0.  Returns the per-epoch
+        mean loss over the rows (each step's loss taken before its update).
+
+        The weights are trained in place, and Adam's moments and step count
+        live in self.optimizer.state in torch's own layout, so train /
+        train_batch / another train_minibatch continue from them."""
+        import ctypes as C
+        from . import _lib
+        linears = self._minibatch_linears()
+        if int(batch_size) < 1 or int(epochs) < 0:
+            raise ValueError("batch_size < 1 or epochs < 0")
+        data_X = torch.as_tensor(data_X)
+        data_y = torch.as_tensor(data_y)
+        n_cls = linears[-1].out_features
+        if data_X.dim() != 2 or data_X.shape[1] != linears[0].in_features or data_X.shape[0] < 1:
+            raise ValueError("data_X must be (n >= 1, input_dim)")
+        if data_y.shape != (data_X.shape[0],) or data_y.is_floating_point():
+            raise ValueError("data_y must be n integer labels")
+        if int(data_y.min()) < 0 or int(data_y.max()) >= n_cls:
+            raise ValueError("a label lies outside [0, n_classes)")
+        if self.device.type != "cuda":
+            raise RuntimeError("train_minibatch runs on the GPU training kernels (no CPU fallback): "
+                               "no HIP device")
+        lib = _lib.load()
+        opt, group = self.optimizer, self.optimizer.param_groups[0]
+        n, batch = int(data_X.shape[0]), int(batch_size)
+        steps = -(-n // batch)
+        losses = []
+        with torch.cuda.device(self.device), torch.no_grad():
+            x = data_X.to(self.device, torch.float32).contiguous()
+            y = data_y.to(self.device).to(torch.int32)
+            desc, t0 = self._minibatch_desc(linears)
+            need = lib.lmi_mlp_train_workspace_bytes(C.byref(desc), batch)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            weights = torch.full((steps,), float(batch), dtype=torch.float64)
+            weights[-1] = n - (steps - 1) * batch
+            try:
+                for ep in range(int(epochs)):
+                    order = torch.randperm(n, generator=generator).to(self.device)
+                    loss = torch.empty(steps, dtype=torch.float32, device=self.device)
+                    _lib.check("lmi_mlp_train_steps", lib.lmi_mlp_train_steps(
+                        C.byref(desc), x.data_ptr(), n, x.stride(0), y.data_ptr(), order.data_ptr(), n,
+                        batch, 0, steps, t0, float(group["lr"]), 0.9, 0.999, 1e-8, loss.data_ptr(),
+                        ws.data_ptr(), need, _lib.stream_handle(self.device)))
+                    t0 += steps
+                    losses.append(float((loss.cpu().double() * weights).sum() / n))  # waits for the epoch
+                    if logger:
+                        logger.info(f"Epoch {ep} | Loss {losses[-1]:.5f}")
+            finally:
+                for m in linears:
+                    for p in (m.weight, m.bias):
+                        opt.state[p]["step"] = torch.tensor(float(t0), dtype=torch.float32)
+                # the kernels wrote the parameters behind torch's back
+                # (p._version did not move): drop the cached device router
+                self._router = None
+                self._router_version = None
         return losses
 
     # ---- inference on the GPU --------------------------------------------------

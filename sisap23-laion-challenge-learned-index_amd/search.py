@@ -71,7 +71,7 @@ def _synthetic(n, nq=10_000):
 
 def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc=None,
         n_categories=None, epochs=100, model_type='MLP', lr=0.1, preprocess=False, save=False,
-        synthetic=0, semantics='reference', index_path=None):
+        synthetic=0, semantics='reference', index_path=None, train_mode='reference'):
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # one rank of `--gpus N` / torchrun: the process group (and this
@@ -116,7 +116,8 @@ def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc
         build_t = time.time() - t0
     else:
         li = LearnedIndex()
-        pred_categories, build_t = li.build(data, n_categories=n_categories, epochs=epochs, lr=lr)
+        pred_categories, build_t = li.build(data, n_categories=n_categories, epochs=epochs, lr=lr,
+                                            train_mode=train_mode)
     LOG.info(f'Pure build time: {build_t}')
     LOG.info(f'Overall build time: {time.time() - s}')
     # the bucket-sorted corpus goes to HBM here, before the timed loop, and
@@ -157,12 +158,7 @@ def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc
                       identifier, size)
 
 
-if __name__ == "__main__":
-    from li.dist import gpus_arg, launch_ranks
-    if gpus_arg(sys.argv[1:]) > 1 and "WORLD_SIZE" not in os.environ:
-        # before anything touches a GPU: the ranks are child processes
-        sys.exit(launch_ranks(gpus_arg(sys.argv[1:]), sys.argv[1:], os.path.abspath(__file__),
-                              relay_stdout=False))
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--dataset", default="pca96v2")
     parser.add_argument("--emb", default="pca96")
@@ -188,9 +184,22 @@ if __name__ == "__main__":
     parser.add_argument("--index", default=None,
                         help='load a pickled LearnedIndex (save_as_pickle format) instead of '
                              'building one; its router labels the data')
-    args = parser.parse_args()
+    parser.add_argument("--train-mode", default="reference", choices=["reference", "minibatch"],
+                        help='reference: one optimizer step per epoch, on its last minibatch '
+                             '(the reference\'s train_batch); minibatch: a step on every '
+                             'minibatch, on the fused GPU training kernels')
+    return parser
+
+
+if __name__ == "__main__":
+    from li.dist import gpus_arg, launch_ranks
+    if gpus_arg(sys.argv[1:]) > 1 and "WORLD_SIZE" not in os.environ:
+        # before anything touches a GPU: the ranks are child processes
+        sys.exit(launch_ranks(gpus_arg(sys.argv[1:]), sys.argv[1:], os.path.abspath(__file__),
+                              relay_stdout=False))
+    args = build_parser().parse_args()
     assert args.size in ['100K', '300K', '10M', '30M', '100M']
     run(args.dataset, args.emb, args.size, args.k, 'learned-index',
         [int(b) for b in args.buckets_perc], args.n_categories, args.epochs, args.model_type,
         args.lr, args.preprocess, args.save, synthetic=args.synthetic, semantics=args.semantics,
-        index_path=args.index)
+        index_path=args.index, train_mode=args.train_mode)
