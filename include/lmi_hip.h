@@ -96,7 +96,16 @@ typedef struct lmi_mlp_desc {
     const float* b[LMI_MAX_LAYERS];   /* device, [out] */
 } lmi_mlp_desc;
 
+/* Widest layer (input, hidden or classes) lmi_router evaluates; it equals
+ * LMI_TRAIN_MAX_DIM, so every stack lmi_mlp_train_steps trains also routes. */
+#define LMI_ROUTER_MAX_DIM 1024
+
 /* Router inference on nq rows of x (device, [nq][dims[0]] f32, row stride ldx).
+ * Any Linear/ReLU stack of 1..LMI_MAX_LAYERS layers whose widths lie in
+ * 1..LMI_ROUTER_MAX_DIM, whatever the alignment of its weights (an MFMA kernel
+ * when the input and hidden widths are multiples of 16 and the weights 16-B
+ * aligned, an FMA-chain kernel otherwise).  A wider layer returns
+ * LMI_E_UNSUPPORTED before any device call.
  * mode LMI_ROUTER_TOPR — replaces NeuralNetwork.predict_proba
  *   (reference model.py:214-229 = softmax(dim=1) then topk(C)):
  *   classes_out (device, [nq][R] int32) = classes by descending probability,

@@ -15,6 +15,9 @@ Every function restates a piece of TerkaSlan/sisap23-laion-challenge-learned-ind
   blas32_*             utils.py:10-11's float32 arithmetic operation by
                        operation (numpy einsum + OpenBLAS sgemm orders, round 6)
   mlp_forward / predict_proba / predict   model.py:15-83, :201-229
+  mlp_forward64 / check_router_rows      the same stack in float64 with an
+                       a-priori bound on any float32 evaluation: the checker
+                       of the router kernels (tests/test_gpu_router.py)
   search_single_direct / search_direct   LearnedIndex.py:22-195, restated
                        line by line (full distance matrices, no shortcut)
   bucket_lists + replay  the decomposition the GPU path implements
@@ -221,6 +224,122 @@ def predict_proba(x, layers):
 def predict(x, layers):
     """model.py:201-212: argmax of the logits (first index on ties)."""
     return np.argmax(mlp_forward(x, layers), axis=1).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------
+# router checker: float64 forward with an a-priori bound on any float32 one
+# ---------------------------------------------------------------------------
+U32 = 2.0 ** -24  # unit roundoff of float32
+ROUTER_PROB_CONST = 16  # two expf and the division, in units of u (check_router_rows)
+
+
+def mlp_forward64(x, layers):
+    """The Linear/ReLU stack in float64 on the float32 inputs and weights:
+    (logits64, err).  err[q, c] bounds |logit32 - logit64| for every float32
+    evaluation of the stack (fused or not, any summation order), u = 2^-24:
+    a dot product of din terms plus the bias, each operation rounded once,
+    errs by at most (din + 2) u (|W| |h32| + |b|) (first order, gamma_n <= n u
+    with one spare u for the second-order terms), and the error e_in of its
+    inputs passes through |W|; ReLU is 1-Lipschitz and passes it on:
+
+        e_out = |W| e_in + (din + 2) u (|W| (|h| + e_in) + |b|)
+    """
+    h = np.asarray(x, np.float32).astype(np.float64)
+    e = np.zeros_like(h)
+    for i, (w, b) in enumerate(layers):
+        w = np.asarray(w, np.float32).astype(np.float64)
+        b = np.asarray(b, np.float32).astype(np.float64)
+        aw = np.abs(w).T
+        z = h @ w.T + b
+        e = e @ aw + (w.shape[1] + 2) * U32 * ((np.abs(h) + e) @ aw + np.abs(b))
+        h = np.maximum(z, 0.0) if i + 1 < len(layers) else z
+    return h, e
+
+
+def softmax64(logits64):
+    z = np.exp(logits64 - logits64.max(axis=1, keepdims=True))
+    return z / z.sum(axis=1, keepdims=True)
+
+
+def router_clear_rows(logits64, err):
+    """(mask, argmax64): rows whose float64 top-1 gap exceeds e[c0] + e[c1],
+    so that every float32 evaluation has the float64 argmax (all rows when
+    there is one class)."""
+    n, c = logits64.shape
+    order = rank_classes(logits64)
+    if c == 1:
+        return np.ones(n, bool), order[:, 0]
+    rows = np.arange(n)
+    c0, c1 = order[:, 0], order[:, 1]
+    gap = logits64[rows, c0] - logits64[rows, c1]
+    return gap > err[rows, c0] + err[rows, c1], c0
+
+
+def check_router_rows(classes, probs, logits64, err, R, prob_const=ROUTER_PROB_CONST,
+                      prob_cols=None):
+    """Every row of a router answer that no float32 evaluation within `err`
+    of logits64 could give: a list of (row, reason), empty when all pass.  No
+    row is excused.  classes [n, R] (or [n] with R = 1), probs [n, R] or None.
+    A row's picks c_0 .. c_{R-1} are valid iff they are distinct and in range,
+    l[c_r] + e[c_r] >= l[c_{r+1}] - e[c_{r+1}] for consecutive picks, and every
+    unpicked j has l[j] - e[j] <= l[c_{R-1}] + e[c_{R-1}].  A probability p of
+    class c is valid iff
+
+        |p - p64| <= p64 (2 max_j e_j + |l_c - max l| u + (C + prob_const) u)
+
+    with p64 = softmax64(l)[c]: the logits' shifts in the numerator and the
+    denominator, the rounding of l_c - max, C additions, and a constant for
+    the two expf and the division.  prob_cols restricts the probability check
+    to those columns (the picks are always checked in full)."""
+    l = np.asarray(logits64, np.float64)
+    e = np.asarray(err, np.float64)
+    n, C = l.shape
+    cls = np.asarray(classes).astype(np.int64).reshape(n, -1)
+    bad = []
+    if cls.shape[1] != R:
+        return [(-1, f"classes have {cls.shape[1]} columns, R = {R}")]
+    rows = np.arange(n)[:, None]
+    inr = ((cls >= 0) & (cls < C)).all(axis=1)
+    cc = np.clip(cls, 0, C - 1)
+    srt = np.sort(cc, axis=1)
+    distinct = (np.diff(srt, axis=1) != 0).all(axis=1) if R > 1 else np.ones(n, bool)
+    hi = l[rows, cc] + e[rows, cc]
+    lo = l[rows, cc] - e[rows, cc]
+    ordered = (hi[:, :-1] >= lo[:, 1:]).all(axis=1) if R > 1 else np.ones(n, bool)
+    rest = l - e
+    rest[rows, cc] = -np.inf
+    cut = rest.max(axis=1) <= hi[:, -1]
+    for name, ok in (("class out of range", inr), ("repeated class", distinct),
+                     ("picks out of order", ordered), ("a better class left out", cut)):
+        bad += [(int(i), name) for i in np.nonzero(~ok)[0]]
+    if probs is not None:
+        p = np.asarray(probs).astype(np.float64).reshape(n, R)
+        p64 = softmax64(l)[rows, cc]
+        lc = l[rows, cc]
+        tol = p64 * (2.0 * e.max(axis=1, keepdims=True)
+                     + np.abs(lc - l.max(axis=1, keepdims=True)) * U32 + (C + prob_const) * U32)
+        okp = np.abs(p - p64) <= tol  # (False for NaN)
+        if prob_cols is not None:
+            keep = np.zeros(R, bool)
+            keep[list(prob_cols)] = True
+            okp |= ~keep[None, :]
+        bad += [(int(i), "probability off") for i in np.nonzero(~okp.all(axis=1) & inr)[0]]
+    return sorted(bad)
+
+
+def router_prob_excess(classes, probs, logits64, err):
+    """Largest (|p - p64| / p64 - the rule's other terms) / u over a router
+    answer: what the rule's constant has to cover (measurement aid)."""
+    l = np.asarray(logits64, np.float64)
+    e = np.asarray(err, np.float64)
+    n, C = l.shape
+    cls = np.asarray(classes).astype(np.int64).reshape(n, -1)
+    rows = np.arange(n)[:, None]
+    p64 = softmax64(l)[rows, cls]
+    rel = np.abs(np.asarray(probs, np.float64).reshape(cls.shape) - p64) / p64
+    other = (2.0 * e.max(axis=1, keepdims=True)
+             + np.abs(l[rows, cls] - l.max(axis=1, keepdims=True)) * U32 + C * U32)
+    return float(((rel - other) / U32).max())
 
 
 # ---------------------------------------------------------------------------

@@ -10,9 +10,13 @@
 // aligned at a pitch of 4 mod 64 floats so per-lane float4 reads are
 // conflict-free); every lane owns one query and kOB output neurons.  A layer is
 // computed in passes of NG * kOB outputs whose weight rows are first staged in
-// LDS (one coalesced copy per pass, shared by the whole tile) and then read as
-// broadcasts.  Each output is the fp32 FMA chain b[o] + sum_i h[i] * W[o][i] in
-// ascending i, i.e. torch's Linear up to summation order.  The last layer's
+// LDS (coalesced copies shared by the whole tile: the whole rows at once when
+// they fit beside the activations, else blocks of their columns one after
+// another while the chains stay in registers) and then read as broadcasts.
+// Tiles are 32 queries while the widest layer is at most 576, else 16: every
+// width up to LMI_ROUTER_MAX_DIM fits the 160 KiB of LDS.  Each output is
+// the fp32 FMA chain b[o] + sum_i h[i] * W[o][i] in ascending i, i.e.
+// torch's Linear up to summation order.  The last layer's
 // logits stay in LDS and are reduced to the top-R classes (descending logit,
 // ties to the lower class index) and their softmax probabilities, or to the
 // argmax.
@@ -33,6 +37,7 @@ struct RouterArgs {
     int32_t stride;  // LDS row stride in floats
     int32_t w_vec4;  // every weight matrix 16-B aligned with din % 4 == 0 rows
     int32_t wpitch;  // LDS pitch of a staged weight row, floats
+    int32_t kblk;    // columns of the weight rows staged at a time (a multiple of 4)
     int32_t R, mode;
     int32_t* classes;
     float* probs;
@@ -157,7 +162,8 @@ __global__ __launch_bounds__(kThreads) void router_kernel(RouterArgs a) {
     constexpr int NG = 4 * G;     // output groups per workgroup
     const int S = a.stride;
     const int WP = a.wpitch;                    // staged weight row pitch (floats)
-    float* wt = smem + 2 * TQ * S;              // [NG * kOB][WP] weights of one pass
+    const int KB = a.kblk;                      // staged columns per block
+    float* wt = smem + 2 * TQ * S;              // [NG * kOB][WP] one column block of a pass's rows
     float* stat = wt + NG * kOB * WP;           // [TQ][2]: max, sum
 
     const int tid = threadIdx.x;
@@ -198,40 +204,8 @@ __global__ __launch_bounds__(kThreads) void router_kernel(RouterArgs a) {
         const float* hin = smem + cur * TQ * S + ql * S;
         float* hout = smem + (cur ^ 1) * TQ * S + ql * S;
         const bool relu = (l + 1 < a.n_layers);
-        const int din4 = din & ~3;
         for (int ob = 0; ob < dout; ob += NG * kOB) {
-            // stage rows ob .. ob + NG*kOB - 1 (clamped) of W: contiguous in HBM
             const int nrow = min(NG * kOB, dout - ob);
-            __syncthreads();  // the previous pass's readers are done with wt
-            if (a.w_vec4) {
-                // all of a thread's loads in flight before its LDS stores (a
-                // load-store loop would pay one L2 round trip per element)
-                constexpr int kU = 8;
-                const int n4 = din >> 2, tot = nrow * n4;
-                const float4* src = reinterpret_cast<const float4*>(W + (size_t)ob * din);
-                for (int e0 = tid; e0 < tot; e0 += kU * kThreads) {
-                    float4 v[kU];
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        const int e = e0 + u * kThreads;
-                        if (e < tot) v[u] = src[e];
-                    }
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        const int e = e0 + u * kThreads;
-                        if (e < tot) {
-                            const int r = e / n4, c4 = e - r * n4;
-                            *reinterpret_cast<float4*>(wt + r * WP + 4 * c4) = v[u];
-                        }
-                    }
-                }
-            } else {
-                for (int e = tid; e < nrow * din; e += kThreads) {
-                    const int r = e / din, c = e - r * din;
-                    wt[r * WP + c] = W[(size_t)ob * din + e];
-                }
-            }
-            __syncthreads();
             float acc[kOB];
             const float* wr[kOB];
 #pragma unroll
@@ -240,24 +214,64 @@ __global__ __launch_bounds__(kThreads) void router_kernel(RouterArgs a) {
                 acc[j] = bias[ob + r];
                 wr[j] = wt + r * WP;
             }
-            // ascending i, one fmaf per term: the same chain as a scalar loop
-            int i = 0;
-#pragma unroll 2
-            for (; i < din4; i += 4) {
-                const float4 h4 = *reinterpret_cast<const float4*>(hin + i);
+            // columns k0 .. k1 - 1 of rows ob .. ob + nrow - 1 of W at a time
+            // (the whole rows when they fit: one block); the chains stay in
+            // registers from block to block
+            for (int k0 = 0; k0 < din; k0 += KB) {
+                const int k1 = min(din, k0 + KB), kw = k1 - k0;
+                __syncthreads();  // the previous block's readers are done with wt
+                if (a.w_vec4) {
+                    // all of a thread's loads in flight before its LDS stores (a
+                    // load-store loop would pay one L2 round trip per element)
+                    constexpr int kU = 8;
+                    const int n4 = kw >> 2, tot = nrow * n4;
+                    const float* src = W + (size_t)ob * din + k0;
+                    for (int e0 = tid; e0 < tot; e0 += kU * kThreads) {
+                        float4 v[kU];
 #pragma unroll
-                for (int j = 0; j < kOB; ++j) {
-                    const float4 w4 = *reinterpret_cast<const float4*>(wr[j] + i);
-                    acc[j] = fmaf(h4.x, w4.x, acc[j]);
-                    acc[j] = fmaf(h4.y, w4.y, acc[j]);
-                    acc[j] = fmaf(h4.z, w4.z, acc[j]);
-                    acc[j] = fmaf(h4.w, w4.w, acc[j]);
+                        for (int u = 0; u < kU; ++u) {
+                            const int e = e0 + u * kThreads;
+                            const int r = e / n4, c4 = e - r * n4;
+                            if (e < tot)
+                                v[u] = *reinterpret_cast<const float4*>(src + (size_t)r * din + 4 * c4);
+                        }
+#pragma unroll
+                        for (int u = 0; u < kU; ++u) {
+                            const int e = e0 + u * kThreads;
+                            if (e < tot) {
+                                const int r = e / n4, c4 = e - r * n4;
+                                *reinterpret_cast<float4*>(wt + r * WP + 4 * c4) = v[u];
+                            }
+                        }
+                    }
+                } else {
+                    for (int e = tid; e < nrow * kw; e += kThreads) {
+                        const int r = e / kw, c = e - r * kw;
+                        wt[r * WP + c] = W[(size_t)(ob + r) * din + k0 + c];
+                    }
                 }
-            }
-            for (; i < din; ++i) {
-                const float h = hin[i];
+                __syncthreads();
+                // ascending i, one fmaf per term: the same chain as a scalar loop
+                const int kw4 = kw & ~3;
+                const float* hk = hin + k0;
+                int i = 0;
+#pragma unroll 2
+                for (; i < kw4; i += 4) {
+                    const float4 h4 = *reinterpret_cast<const float4*>(hk + i);
 #pragma unroll
-                for (int j = 0; j < kOB; ++j) acc[j] = fmaf(h, wr[j][i], acc[j]);
+                    for (int j = 0; j < kOB; ++j) {
+                        const float4 w4 = *reinterpret_cast<const float4*>(wr[j] + i);
+                        acc[j] = fmaf(h4.x, w4.x, acc[j]);
+                        acc[j] = fmaf(h4.y, w4.y, acc[j]);
+                        acc[j] = fmaf(h4.z, w4.z, acc[j]);
+                        acc[j] = fmaf(h4.w, w4.w, acc[j]);
+                    }
+                }
+                for (; i < kw; ++i) {  // (only the last block: KB is a multiple of 4)
+                    const float h = hk[i];
+#pragma unroll
+                    for (int j = 0; j < kOB; ++j) acc[j] = fmaf(h, wr[j][i], acc[j]);
+                }
             }
 #pragma unroll
             for (int j = 0; j < kOB; ++j) {
@@ -511,6 +525,13 @@ extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp
     LMI_CHECK_ARG(C >= 1, "no classes");
     if (mode == LMI_ROUTER_ARGMAX) LMI_CHECK_ARG(R == 1, "ARGMAX needs R == 1");
     LMI_CHECK_ARG(R >= 1 && R <= C, "R out of range");
+    for (int l = 0; l <= mlp->n_layers; ++l) {
+        if (mlp->dims[l] > LMI_ROUTER_MAX_DIM) {
+            set_error("router layer width dims[%d]=%d above LMI_ROUTER_MAX_DIM=%d", l, mlp->dims[l],
+                      LMI_ROUTER_MAX_DIM);
+            return LMI_E_UNSUPPORTED;
+        }
+    }
     if (nq == 0) return LMI_OK;
 
     RouterArgs a{};
@@ -577,18 +598,23 @@ extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp
             return LMI_OK;
         }
     }
-    a.wpitch = ((maxdim + 3) / 4) * 4 + 4;  // two rows read together sit 4 banks apart
-    const size_t lds_limit = 160 * 1024;
-    for (int tq : {32, 16, 8}) {
-        const int ng = 4 * (64 / tq);
-        const size_t lds =
-            (size_t)(2 * tq * a.stride + ng * kOB * a.wpitch + 2 * tq) * sizeof(float);
-        if (lds > lds_limit) continue;
-        switch (tq) {
-            case 32: return launch_router<32>(a, lds, s);
-            case 16: return launch_router<16>(a, lds, s);
-            default: return launch_router<8>(a, lds, s);
-        }
+    // 32 queries per workgroup while their two activation buffers leave room
+    // for a column block of kMinKB floats of a pass's weight rows, else 16
+    // (which holds for every width up to LMI_ROUTER_MAX_DIM); the block is
+    // the whole rows when they fit, else what is left of the LDS
+    const int lds_floats = 160 * 1024 / (int)sizeof(float);
+    constexpr int kMinKB = 32;
+    for (int tq : {32, 16}) {
+        const int rows = 4 * (64 / tq) * kOB;  // weight rows of a pass
+        const int left = lds_floats - 2 * tq * a.stride - 2 * tq;
+        if (left < rows * (kMinKB + 4)) continue;
+        const int whole = ((maxdim + 3) / 4) * 4;
+        const int fit = (left / rows - 4) & ~3;
+        a.kblk = whole < fit ? whole : fit;
+        a.wpitch = a.kblk + 4;  // two rows read together sit 4 banks apart
+        const size_t lds = (size_t)(2 * tq * a.stride + rows * a.wpitch + 2 * tq) * sizeof(float);
+        if (tq == 32) return launch_router<32>(a, lds, s);
+        return launch_router<16>(a, lds, s);
     }
     set_error("router layer width %d too large for LDS", maxdim);
     return LMI_E_UNSUPPORTED;

@@ -49,6 +49,7 @@ LMI_REPLAY_DEVICE_MAX_KR = 32
 LMI_REPLAY_DEVICE_MAX_K = 64
 LMI_KMEANS_MAX_D = 1024
 LMI_TRAIN_MAX_DIM = 1024
+LMI_ROUTER_MAX_DIM = 1024
 LMI_REFINE_EPS = 2.0 ** -16
 
 # every symbol include/lmi_hip.h declares (tests check the export table)

@@ -178,10 +178,15 @@ def test_router_mfma_matches_fma_path(hidden, monkeypatch):
     r = DeviceRouter(layers)
     xt = torch.from_numpy(x).cuda()
     cls_m, p_m = r.topr(xt, 7, with_probs=True)
+    # (the library reads its knobs once: reload after every change)
     monkeypatch.setenv("LMI_ROUTER_FMA", "1")
-    cls_f, p_f = r.topr(xt, 7, with_probs=True)
-    am_f = r.argmax(xt).cpu().numpy()
-    monkeypatch.delenv("LMI_ROUTER_FMA")
+    _lib.load().lmi_config_reload()
+    try:
+        cls_f, p_f = r.topr(xt, 7, with_probs=True)
+        am_f = r.argmax(xt).cpu().numpy()
+    finally:
+        monkeypatch.delenv("LMI_ROUTER_FMA")
+        _lib.load().lmi_config_reload()
     am_m = r.argmax(xt).cpu().numpy()
     for cls in (cls_m.cpu().numpy(), cls_f.cpu().numpy()):
         assert _router_mismatch(cls, logits, 7) == 0

@@ -57,6 +57,32 @@ def test_invalid_arguments_fail_loudly_without_a_device():
     assert rc == _lib.LMI_E_INVALID and b"null pointer" in lib.lmi_last_error()
 
 
+def test_router_refuses_layers_above_its_width_limit_without_a_device():
+    """lmi_router takes widths 1..LMI_ROUTER_MAX_DIM (= the trainer's limit);
+    a wider layer is LMI_E_UNSUPPORTED before any device call (the pointers
+    here are host memory that is never read)."""
+    lib = _lib.load()
+    assert _lib.LMI_ROUTER_MAX_DIM == _lib.LMI_TRAIN_MAX_DIM == 1024
+    hdr = open(os.path.join(ROOT, "include", "lmi_hip.h")).read()
+    assert re.search(r"#define LMI_ROUTER_MAX_DIM 1024\b", hdr)
+    buf = np.zeros(16, np.float32)
+    out = np.zeros(16, np.int32)
+    over = _lib.LMI_ROUTER_MAX_DIM + 1
+    for dims in ((over, 8, 10), (96, over, 10), (96, 8, over), (over,) * 2):
+        m = _lib.MlpDesc()
+        m.n_layers = len(dims) - 1
+        for i, v in enumerate(dims):
+            m.dims[i] = v
+        for i in range(m.n_layers):
+            m.W[i] = buf.ctypes.data
+            m.b[i] = buf.ctypes.data
+        rc = lib.lmi_router(buf.ctypes.data, 4, over, C.byref(m), 1, _lib.LMI_ROUTER_TOPR,
+                            out.ctypes.data, None, None)
+        assert rc == _lib.LMI_E_UNSUPPORTED, dims
+        assert b"LMI_ROUTER_MAX_DIM" in lib.lmi_last_error()
+    assert not out.any()
+
+
 def test_plan_chunks():
     lib = _lib.load()
     off = np.array([0, 0, 5, 70, 70, 200], np.int64)
