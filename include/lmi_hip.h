@@ -118,6 +118,27 @@ int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp,
                int32_t R, int32_t mode, int32_t* classes_out, float* probs_out,
                void* stream);
 
+/* Adaptive probing: LMI_ROUTER_TOPR followed by a probability-mass stop rule,
+ * in the same launch (an addition: LMI_ABI_VERSION does not change).
+ *   p_r   = the float32 softmax probability of pick r (what probs_out receives)
+ *   S_0   = 0,  S_{r+1} = fl32(S_r + p_r), summed in ascending r
+ *   probe r is kept  <=>  r < min_probes  or  S_r < stop_mass
+ * The kept probes are a prefix of the R picks.  classes_out[q][r] is the TOPR
+ * class where kept and LMI_PROBE_NONE where dropped; every consumer of the
+ * classes (the scan's plan, both replays) treats a class outside [0, C) as a
+ * probe with no bucket: its list is (+inf, -1) and its round merges nothing.
+ * probs_out (nullable) holds the TOPR probabilities of every r, kept or not,
+ * so a caller can recompute the rule exactly; n_probes_out (device, [nq]
+ * int32, nullable) the number of probes kept.
+ * 0 < stop_mass <= 1 (a NaN is invalid); 1 <= min_probes, a value above R
+ * means R; everything else as for lmi_router.  stop_mass = 1 with
+ * min_probes = R keeps every probe.  Asynchronous, no allocation, capturable. */
+#define LMI_PROBE_NONE (-1)   /* class of a probe the stop rule dropped */
+int lmi_router_stop(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp,
+                    int32_t R, float stop_mass, int32_t min_probes,
+                    int32_t* classes_out, float* probs_out /*nullable*/,
+                    int32_t* n_probes_out /*nullable, [nq]*/, void* stream);
+
 /* ---- bucket-sorted corpus (one shard) -------------------------------- */
 /* Rows of the search corpus (reference: data_search, clip768 'emb',
  * search.py:79-84) ordered by bucket label, stable in row order, i.e. the

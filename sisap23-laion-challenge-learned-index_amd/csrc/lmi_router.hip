@@ -19,7 +19,10 @@
 // torch's Linear up to summation order.  The last layer's
 // logits stay in LDS and are reduced to the top-R classes (descending logit,
 // ties to the lower class index) and their softmax probabilities, or to the
-// argmax.
+// argmax.  lmi_router_stop adds, where the picks are written, the
+// probability-mass stop rule of adaptive probing: pick r is kept iff
+// r < min_probes or the float32 sum of the picks' probabilities before it is
+// below stop_mass; a dropped pick's class is LMI_PROBE_NONE.
 #include "lmi_common.hpp"
 
 #include <mutex>
@@ -41,6 +44,10 @@ struct RouterArgs {
     int32_t R, mode;
     int32_t* classes;
     float* probs;
+    // the probability-mass stop rule (lmi_router_stop); stop == 0: every pick is kept
+    int32_t stop, min_probes;
+    float stop_mass;
+    int32_t* n_probes;
 };
 
 constexpr int kThreads = 256;
@@ -120,6 +127,8 @@ __device__ inline void select_classes(const RouterArgs& a, const float* logit, i
             const float m = stat[2 * qq], sum = stat[2 * qq + 1];
             float pl = __builtin_inff();
             int pi = -1;
+            float mass = 0.0f;  // S_r: fl32 sum of the picks' probabilities before r (lane 0)
+            int kept = 0;
             for (int r = 0; r < R; ++r) {
                 float bl = -__builtin_inff();
                 int bi = INT32_MAX;
@@ -130,12 +139,22 @@ __device__ inline void select_classes(const RouterArgs& a, const float* logit, i
                 wave_best(bl, bi);
                 if (lane == 0) {
                     const size_t o = (size_t)(q0 + qq) * R + r;
-                    a.classes[o] = bi;
-                    if (a.probs) a.probs[o] = expf(bl - m) / sum;
+                    if (a.stop) {
+                        const float p = expf(bl - m) / sum;
+                        const bool keep = r < a.min_probes || mass < a.stop_mass;
+                        a.classes[o] = keep ? bi : LMI_PROBE_NONE;
+                        if (a.probs) a.probs[o] = p;
+                        kept += keep ? 1 : 0;
+                        mass += p;
+                    } else {
+                        a.classes[o] = bi;
+                        if (a.probs) a.probs[o] = expf(bl - m) / sum;
+                    }
                 }
                 pl = bl;
                 pi = bi;
             }
+            if (a.stop && a.n_probes && lane == 0) a.n_probes[q0 + qq] = kept;
         }
     } else {
         // Rank of every class: its position in (desc logit, asc index) order.
@@ -151,6 +170,29 @@ __device__ inline void select_classes(const RouterArgs& a, const float* logit, i
                 a.classes[o] = j;
                 if (a.probs) a.probs[o] = expf(v - stat[2 * qq]) / stat[2 * qq + 1];
             }
+        }
+        if (!a.stop) return;  // (uniform over the workgroup)
+        // the stop rule: a second pass over the R picks just written (this
+        // workgroup's own stores, visible after the barrier), one thread per
+        // query; a pick's probability is recomputed from its logit, the same
+        // expression as above
+        __threadfence_block();
+        __syncthreads();
+        for (int qq = tid; qq < TQ && q0 + qq < a.nq; qq += NT) {
+            const float* lr = logit + qq * S;
+            const float m = stat[2 * qq], sum = stat[2 * qq + 1];
+            float mass = 0.0f;
+            int kept = 0;
+            for (int r = 0; r < R; ++r) {
+                const size_t o = (size_t)(q0 + qq) * R + r;
+                const int j = a.classes[o];
+                const bool keep = r < a.min_probes || mass < a.stop_mass;
+                if (!keep) a.classes[o] = LMI_PROBE_NONE;
+                kept += keep ? 1 : 0;
+                // (NaN logits leave ranks unwritten: no LDS read from such an entry)
+                mass += (unsigned)j < (unsigned)C ? expf(lr[j] - m) / sum : 0.0f;
+            }
+            if (a.n_probes) a.n_probes[q0 + qq] = kept;
         }
     }
 }
@@ -476,6 +518,24 @@ __global__ __launch_bounds__(256) void router_mfma_kernel(RouterArgs a) {
     sum += __shfl_xor(sum, 32);
     if (g == 0) {
         const int R = a.R;
+        if (a.stop) {
+            float mass = 0.0f;  // S_r, summed in ascending r
+            int kept = 0;
+#pragma unroll
+            for (int r = 0; r < kRT; ++r) {
+                if (r < R) {
+                    const size_t o = (size_t)qi * R + r;
+                    const float p = expf(bl[r] - m) / sum;
+                    const bool keep = r < a.min_probes || mass < a.stop_mass;
+                    a.classes[o] = keep ? bi[r] : LMI_PROBE_NONE;
+                    if (a.probs) a.probs[o] = p;
+                    kept += keep ? 1 : 0;
+                    mass += p;
+                }
+            }
+            if (a.n_probes) a.n_probes[qi] = kept;
+            return;
+        }
 #pragma unroll
         for (int r = 0; r < kRT; ++r) {
             if (r < R) {
@@ -509,13 +569,16 @@ int launch_router(const RouterArgs& a, size_t lds, hipStream_t s) {
     return LMI_OK;
 }
 
-}  // namespace
-}  // namespace lmi
+// The stop rule of a call (lmi_router_stop); on == 0 for lmi_router.
+struct StopRule {
+    int32_t on, min_probes;
+    float stop_mass;
+    int32_t* n_probes;
+};
 
-extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp,
-                          int32_t R, int32_t mode, int32_t* classes_out, float* probs_out,
-                          void* stream) {
-    using namespace lmi;
+int run_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp, int32_t R,
+               int32_t mode, int32_t* classes_out, float* probs_out, const StopRule& rule,
+               void* stream) {
     LMI_CHECK_ARG(mlp != nullptr && x != nullptr && classes_out != nullptr, "null pointer");
     LMI_CHECK_ARG(nq >= 0, "nq < 0");
     LMI_CHECK_ARG(mlp->n_layers >= 1 && mlp->n_layers <= LMI_MAX_LAYERS, "n_layers out of range");
@@ -560,6 +623,10 @@ extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp
     a.mode = mode;
     a.classes = classes_out;
     a.probs = probs_out;
+    a.stop = rule.on;
+    a.min_probes = rule.min_probes;
+    a.stop_mass = rule.stop_mass;
+    a.n_probes = rule.n_probes;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // MFMA path: hidden and input widths multiples of 16 (k quarters of
     // float4 runs), 16-B aligned weights; the classes may be any width
@@ -618,4 +685,26 @@ extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp
     }
     set_error("router layer width %d too large for LDS", maxdim);
     return LMI_E_UNSUPPORTED;
+}
+
+}  // namespace
+}  // namespace lmi
+
+extern "C" int lmi_router(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp,
+                          int32_t R, int32_t mode, int32_t* classes_out, float* probs_out,
+                          void* stream) {
+    return lmi::run_router(x, nq, ldx, mlp, R, mode, classes_out, probs_out,
+                           lmi::StopRule{0, 0, 0.0f, nullptr}, stream);
+}
+
+extern "C" int lmi_router_stop(const float* x, int32_t nq, int32_t ldx, const lmi_mlp_desc* mlp,
+                               int32_t R, float stop_mass, int32_t min_probes,
+                               int32_t* classes_out, float* probs_out, int32_t* n_probes_out,
+                               void* stream) {
+    using namespace lmi;
+    // (a NaN fails the first comparison)
+    LMI_CHECK_ARG(stop_mass > 0.0f && stop_mass <= 1.0f, "stop_mass outside (0, 1]");
+    LMI_CHECK_ARG(min_probes >= 1, "min_probes < 1");
+    return run_router(x, nq, ldx, mlp, R, LMI_ROUTER_TOPR, classes_out, probs_out,
+                      StopRule{1, min_probes < R ? min_probes : R, stop_mass, n_probes_out}, stream);
 }

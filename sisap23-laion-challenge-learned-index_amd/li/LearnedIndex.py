@@ -275,10 +275,21 @@ class LearnedIndex(Logger):
 
     # ---- search -------------------------------------------------------------
     def search(self, data_navigation, queries_navigation, data_search, queries_search,
-               pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference"):
+               pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference",
+               stop_mass=None, min_buckets=1, timings=None):
         """Search for k nearest neighbors of each query (LearnedIndex.py:22-101).
         `semantics="exact"` (an addition; default off) returns the exact top-k of
-        the union of the probed buckets instead of the reference's round merge."""
+        the union of the probed buckets instead of the reference's round merge.
+        `stop_mass` (an addition; default off): adaptive probing -- `n_buckets`
+        is the cap, and a query stops probing once the router's probability
+        mass over the buckets it has probed reaches `stop_mass`, but probes at
+        least `min_buckets` (li.index.probe_stop_mask is the rule).  A round a
+        query does not probe is a round whose `pred_categories` entry matches
+        no category (:75-:80): it keeps what it had.  `timings` (measurement
+        only): Searcher.search's per-stage times, and `mean_probes` with the
+        rule on."""
+        from .index import check_stop
+        check_stop(stop_mass, min_buckets)
         assert self.model is not None, 'Model is not trained, call `build` first.'
         if _AUTO_ATTACH and self._trusted is None:
             self.attach(data_navigation, data_search, pred_categories)
@@ -288,7 +299,19 @@ class LearnedIndex(Logger):
         return self._get_searcher(index).search(q_nav, _upload_queries(queries_search, index.device),
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
-                                                dist=dist_dtype(data_search, queries_search))
+                                                dist=dist_dtype(data_search, queries_search),
+                                                stop_mass=stop_mass, min_probes=min_buckets,
+                                                timings=timings)
+
+    def mean_probes(self, data_navigation, queries_navigation, data_search, pred_categories,
+                    n_buckets, stop_mass, min_buckets=1):
+        """Mean number of buckets `search(..., stop_mass, min_buckets)` probes
+        per query (measurement only: one more router call and a read-back)."""
+        index = self._device_index(data_navigation, data_search, pred_categories)
+        q_nav = data_X_to_torch(queries_navigation).to(index.device)
+        cls = self._get_searcher(index).route(q_nav, n_buckets, stop_mass=stop_mass,
+                                              min_probes=min_buckets)
+        return float((cls >= 0).sum().item()) / max(1, cls.shape[0])
 
     def search_single(self, data_navigation, data_search, queries_search, pred_categories,
                       k=10, threshold_dist=None):

@@ -32,6 +32,7 @@ LMI_F32 = 0
 LMI_F16 = 1
 LMI_ROUTER_TOPR = 0
 LMI_ROUTER_ARGMAX = 1
+LMI_PROBE_NONE = -1
 LMI_Q_F16 = 0
 LMI_Q_F32 = 1
 LMI_Q_SEED_ROUND0 = 0x100
@@ -55,6 +56,7 @@ LMI_REFINE_EPS = 2.0 ** -16
 # every symbol include/lmi_hip.h declares (tests check the export table)
 EXPORTS = (
     "lmi_router",
+    "lmi_router_stop",
     "lmi_plan_chunks",
     "lmi_scan_workspace_bytes",
     "lmi_bucket_topk",
@@ -159,6 +161,8 @@ _I64 = C.c_int64
 
 _SIGNATURES = {
     "lmi_router": (C.c_int, [_P, _I32, _I32, C.POINTER(MlpDesc), _I32, _I32, _P, _P, _P]),
+    "lmi_router_stop": (C.c_int, [_P, _I32, _I32, C.POINTER(MlpDesc), _I32, C.c_float, _I32, _P, _P,
+                                  _P, _P]),
     "lmi_plan_chunks": (C.c_int32, [_P, _I32, _I32, _P]),
     "lmi_scan_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,

@@ -270,10 +270,12 @@ def gather_merge_packed(buf: torch.Tensor, rows: int, k: int, f64: bool, group=N
     return md, mp, st
 
 
-def route_sharded(router, q_nav: torch.Tensor, R: int, group=None) -> torch.Tensor:
+def route_sharded(router, q_nav: torch.Tensor, R: int, group=None, stop_mass=None,
+                  min_probes: int = 1) -> torch.Tensor:
     """K1 on this rank's contiguous slice of the queries, then an all-gather of
     the classes: [nq, R] int32 on every rank, equal to router.topr(q_nav, R)
-    (the router is per-query: a query's classes do not depend on its batch)."""
+    (the router is per-query: a query's classes do not depend on its batch;
+    neither does the stop rule of `stop_mass`, `min_probes`)."""
     G = dist.get_world_size(group)
     g = dist.get_rank(group)
     nq = q_nav.shape[0]
@@ -282,7 +284,9 @@ def route_sharded(router, q_nav: torch.Tensor, R: int, group=None) -> torch.Tens
     hi = min(nq, lo + per)
     part = torch.zeros((per, R), dtype=torch.int32, device=q_nav.device)
     if hi > lo:
-        c, _ = router.topr(q_nav[lo:hi], R)
+        # (the rule's arguments only when it is on: any router with topr(x, R) routes)
+        rule = {} if stop_mass is None else dict(stop_mass=stop_mass, min_probes=min_probes)
+        c, _ = router.topr(q_nav[lo:hi], R, **rule)
         part[: hi - lo] = c
     out = torch.empty((G * per, R), dtype=torch.int32, device=q_nav.device)
     _all_gather(out, part, group)

@@ -56,7 +56,13 @@ class GraphedSearch:
 
     def __init__(self, searcher: "Searcher", q_nav, q_search, R: int,
                  k: int = 10, *, k_round: int = 10, use_threshold: bool = True, dist: str = "f32",
-                 capture: bool = True, pipeline: bool = False):
+                 capture: bool = True, pipeline: bool = False, stop_mass=None,
+                 min_probes: int = 1):
+        from .index import check_stop
+        check_stop(stop_mass, min_probes)
+        # the router's stop rule (DeviceRouter.topr), inside the captured step
+        rule = {} if stop_mass is None else dict(stop_mass=stop_mass, min_probes=min_probes)
+        self.stop_mass, self.min_probes = stop_mass, min_probes
         s = searcher
         ix = s.index
         dev = ix.device
@@ -146,7 +152,8 @@ class GraphedSearch:
                     copy_stream.wait_stream(main)
                     with torch.cuda.stream(copy_stream):
                         d_blk[per * dn:].copy_(self.h_blk[0, per * dn:], non_blocking=True)
-                classes = s.router.topr(d_blk[:per * dn].view(torch.float32).view(per, dn), R)[0]
+                classes = s.router.topr(d_blk[:per * dn].view(torch.float32).view(per, dn), R,
+                                        **rule)[0]
                 if not self.pipeline:
                     main.wait_stream(copy_stream)
                 sv = d_blk[per * dn:per * dn + per * wq]
@@ -162,7 +169,7 @@ class GraphedSearch:
                 if not self.pipeline:
                     d_blk.copy_(self.h_blk[g], non_blocking=True)
                 s.router.topr(d_blk[:per * dn].view(torch.float32).view(per, dn), R,
-                              out=d_blk[per * (dn + wq):])
+                              out=d_blk[per * (dn + wq):], **rule)
                 _all_gather(self.d_all.view(-1), d_blk, s.group)
                 sv = self.d_all[:, per * dn:per * (dn + wq)]
                 if self.f16_up:
@@ -439,4 +446,5 @@ class GraphedSearch:
                                     _as_torch(qs, dev, torch.float64 if qs.dtype == np.float64
                                               else torch.float32),
                                     self.R, k=self.k, k_round=self.k_round,
-                                    use_threshold=self.use_threshold, dist=self.dist)
+                                    use_threshold=self.use_threshold, dist=self.dist,
+                                    stop_mass=self.stop_mass, min_probes=self.min_probes)

@@ -478,6 +478,41 @@ class IndexDescHolder:
 # ---------------------------------------------------------------------------
 # router
 # ---------------------------------------------------------------------------
+def check_stop(stop_mass, min_probes=1) -> None:
+    """Arguments of the probability-mass stop rule (None: the rule is off), as
+    lmi_router_stop checks them, raised as ValueError before any device call."""
+    if stop_mass is None:
+        return
+    # (the float32 value the kernel compares with; a NaN fails both comparisons)
+    if not 0.0 < float(np.float32(stop_mass)) <= 1.0:
+        raise ValueError(f"stop_mass must lie in (0, 1], got {stop_mass}")
+    if int(min_probes) != min_probes or int(min_probes) < 1:
+        raise ValueError(f"min_probes must be an integer >= 1, got {min_probes}")
+
+
+def probe_stop_mask(probs, stop_mass, min_probes: int = 1) -> np.ndarray:
+    """The stop rule of lmi_router_stop, restated in numpy: `probs` [nq, R] are
+    the float32 probabilities of the picks in rank order; the result [nq, R]
+    (bool) is True where probe r is kept:
+
+        S_0 = 0,  S_{r+1} = fl32(S_r + p_r)   (float32, ascending r)
+        keep[r]  <=>  r < min_probes  or  S_r < stop_mass
+
+    The kept probes are a prefix (the S_r do not decrease)."""
+    check_stop(stop_mass, min_probes)
+    p = np.asarray(probs, dtype=np.float32)
+    if p.ndim != 2:
+        raise ValueError("probs must be [nq, R]")
+    nq, R = p.shape
+    keep = np.zeros((nq, R), dtype=bool)
+    mass = np.zeros((nq,), dtype=np.float32)
+    sm = np.float32(stop_mass)
+    for r in range(R):
+        keep[:, r] = (mass < sm) if r >= min_probes else True
+        mass = (mass + p[:, r]).astype(np.float32)
+    return keep
+
+
 class DeviceRouter:
     """Weights of a Linear/ReLU stack in HBM, evaluated by K1 (lmi_router)."""
 
@@ -527,10 +562,22 @@ class DeviceRouter:
                 raise ValueError("expected ReLU after every hidden Linear")
         return cls(layers, device)
 
-    def topr(self, x: torch.Tensor, R: int, with_probs: bool = False, stream=None, out=None):
+    def topr(self, x: torch.Tensor, R: int, with_probs: bool = False, stream=None, out=None,
+             stop_mass=None, min_probes: int = 1, n_probes_out=None):
         """K1 TOPR: classes [nq, R] int32 (into `out` when given, a contiguous
         int32 tensor of nq*R elements) and, with `with_probs`, their softmax
-        probabilities."""
+        probabilities.
+
+        `stop_mass` (None: off, lmi_router exactly as without the argument):
+        the probability-mass stop rule of lmi_router_stop, in the same launch
+        -- probe r is kept iff r < min_probes or the float32 sum of the
+        probabilities of the picks before it is below stop_mass
+        (probe_stop_mask); a dropped probe's class is LMI_PROBE_NONE (-1), the
+        probabilities are those of the plain call for every r.  `n_probes_out`
+        (a contiguous int32 tensor of nq elements) receives the probes kept."""
+        check_stop(stop_mass, min_probes)
+        if stop_mass is None and n_probes_out is not None:
+            raise ValueError("n_probes_out needs stop_mass")
         x = _rows_f32(x, self.device)
         nq = x.shape[0]
         if out is not None:
@@ -541,6 +588,15 @@ class DeviceRouter:
             classes = torch.empty((nq, R), dtype=torch.int32, device=self.device)
         probs = torch.empty((nq, R), dtype=torch.float32, device=self.device) if with_probs else None
         s = stream if stream is not None else _lib.stream_handle(self.device)
+        if stop_mass is not None:
+            if n_probes_out is not None and (n_probes_out.dtype != torch.int32
+                                             or n_probes_out.numel() != nq
+                                             or not n_probes_out.is_contiguous()):
+                raise ValueError("n_probes_out must be a contiguous int32 tensor of nq elements")
+            check("lmi_router_stop", _lib.load().lmi_router_stop(
+                ptr(x), nq, x.stride(0), C.byref(self._desc), R, float(stop_mass), int(min_probes),
+                ptr(classes), ptr(probs), ptr(n_probes_out), s))
+            return classes, probs
         check("lmi_router", _lib.load().lmi_router(ptr(x), nq, x.stride(0), C.byref(self._desc), R,
                                                    _lib.LMI_ROUTER_TOPR, ptr(classes), ptr(probs), s))
         return classes, probs
@@ -931,21 +987,31 @@ class Searcher:
         return d, pos, status
 
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
-              classes: Optional[torch.Tensor] = None, dist: str = "f32"):
-        """Device part: router + scan (+ RCCL merge).  Returns device tensors."""
+              classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
+              min_probes: int = 1):
+        """Device part: router + scan (+ RCCL merge).  Returns device tensors.
+        `stop_mass`, `min_probes`: the router's stop rule (DeviceRouter.topr);
+        a dropped probe's list is (+inf, -1)."""
+        check_stop(stop_mass, min_probes)
         if classes is None:
-            classes = self.route(q_nav, R)
+            classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
         d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64")
         return classes, d, pos, status
 
-    def route(self, q_nav, R: int) -> torch.Tensor:
+    def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
         """K1 classes [nq, R]; with G > 1 ranks each routes nq/G queries and
-        the classes are all-gathered (li.dist.route_sharded)."""
+        the classes are all-gathered (li.dist.route_sharded).  `stop_mass`,
+        `min_probes`: the stop rule of DeviceRouter.topr (dropped probes are
+        -1; the rule is per query, so sharding the queries does not change it)."""
+        check_stop(stop_mass, min_probes)
         if self.exchange:
             from .dist import route_sharded
-            return route_sharded(self.router, _rows_f32(q_nav, self.index.device), R, self.group)
-        return self.router.topr(q_nav, R)[0]
+            return route_sharded(self.router, _rows_f32(q_nav, self.index.device), R, self.group,
+                                 stop_mass=stop_mass, min_probes=min_probes)
+        if stop_mass is None:
+            return self.router.topr(q_nav, R)[0]
+        return self.router.topr(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)[0]
 
     def _device_tables(self):
         """bucket sizes and position -> id map in HBM for the device replay."""
@@ -973,8 +1039,19 @@ class Searcher:
     def search(self, q_nav, q_search, R: int, k: int = 10, *, k_round: int = 10,
                use_threshold: bool = True, classes: Optional[torch.Tensor] = None,
                timings: Optional[dict] = None, replay_on: str = "device",
-               semantics: str = "reference", dist: str = "f32"):
+               semantics: str = "reference", dist: str = "f32", stop_mass=None,
+               min_probes: int = 1):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `stop_mass` (None: off): adaptive probing -- R is the cap, and each
+        query stops at the first probe before which the router's probability
+        mass reached stop_mass, but not before `min_probes` probes
+        (DeviceRouter.topr, probe_stop_mask).  A dropped probe is a round in
+        which the query matches no bucket: under the reference semantics it
+        keeps the fillers for that round and the merge keeps what it had.
+        Everything after the router is unchanged; the answer is that of
+        search(classes=<the masked classes>).  `timings` then also receives
+        `mean_probes` (read back after the answer).
 
         semantics="reference" (default) reproduces LearnedIndex.search's round
         merge (thresholds, fillers, the <k quirk).
@@ -994,6 +1071,7 @@ class Searcher:
         replay).  `timings` (measurement only) receives per-stage wall times in
         ms; the stages are then separated by stream synchronisations."""
         import time
+        check_stop(stop_mass, min_probes)
         if replay_on not in ("device", "host"):
             raise ValueError("replay_on must be 'device' or 'host'")
         if semantics not in ("reference", "exact"):
@@ -1022,8 +1100,13 @@ class Searcher:
         q_search = _rows_q(q_search, dev)
         qmode = self.qmode(q_search)
         if classes is None:
-            classes = self.route(q_nav, R)
+            classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         t0 = lap("router", t0)
+
+        def done(out):
+            if timings is not None and stop_mass is not None:
+                timings["mean_probes"] = float((classes >= 0).sum().item()) / max(1, classes.shape[0])
+            return out
         tl = [t0]
 
         def lap_at(name):
@@ -1082,7 +1165,7 @@ class Searcher:
                 h_a.copy_(ra)
                 h_st[0:1].copy_(status)
                 check_status(int(h_st[0]) & ~_lib.LMI_STATUS_QUERY_NOT_F16)
-            return h_d.numpy().copy(), h_a.numpy().view(np.uint32).copy()
+            return done((h_d.numpy().copy(), h_a.numpy().view(np.uint32).copy()))
         if replay_on == "device":
             bsz, p2id = self._device_tables()
 
@@ -1110,7 +1193,7 @@ class Searcher:
                 torch.cuda.current_stream(dev).synchronize()
                 hd, ha, st0, st1 = answer_views(h, nq, w_ans)
                 check_status(st0 & ~_lib.LMI_STATUS_QUERY_NOT_F16, st1)
-            return hd, ha
+            return done((hd, ha))
         h_cls = self._host("cls", (nq, R), torch.int32)
         h_d = self._host("d", tuple(d.shape), d.dtype)
         h_pos = self._host("pos", tuple(pos.shape), torch.int32)
@@ -1131,4 +1214,4 @@ class Searcher:
                      bucket_size=self.index.bucket_size, pos_to_id=self.index.pos_to_id,
                      use_threshold=use_threshold)
         lap("replay", t0) if sync else None
-        return out
+        return done(out)

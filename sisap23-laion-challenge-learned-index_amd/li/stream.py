@@ -150,7 +150,12 @@ class StreamedSearch:
     def __init__(self, searcher, q_nav, q_search, R: int, k: int = 10, *,
                  k_round: int = 10, use_threshold: bool = True, dist: str = "f32",
                  capture: bool = True, lookahead: bool = True, kth_peers=None,
-                 reserve_cus: Optional[int] = None):
+                 reserve_cus: Optional[int] = None, stop_mass=None, min_probes: int = 1):
+        from .index import check_stop
+        check_stop(stop_mass, min_probes)
+        # the router's stop rule (DeviceRouter.topr), inside the route stage
+        rule = {} if stop_mass is None else dict(stop_mass=stop_mass, min_probes=min_probes)
+        self.stop_mass, self.min_probes = stop_mass, min_probes
         s = searcher
         ix = s.index
         dev = ix.device
@@ -276,9 +281,9 @@ class StreamedSearch:
             blk = self.d_blk[j]
             nav_d = blk[:self.o_q].view(torch.float32).view(per, dn)
             if not X:
-                s.router.topr(nav_d, R, out=self.cls[j])
+                s.router.topr(nav_d, R, out=self.cls[j], **rule)
             else:
-                s.router.topr(nav_d, R, out=blk[self.o_cls:self.o_cls + per * R])
+                s.router.topr(nav_d, R, out=blk[self.o_cls:self.o_cls + per * R], **rule)
 
         def xgather(j):
             from .dist import _all_gather
@@ -653,7 +658,8 @@ class StreamedSearch:
         nav, qs = host_array(batch[0]), host_array(batch[1])
         return s.search(torch.from_numpy(np.ascontiguousarray(nav, dtype=np.float32)).to(dev),
                         torch.from_numpy(np.ascontiguousarray(qs)).to(dev), self.R, k=self.k,
-                        k_round=self.k_round, use_threshold=self.use_threshold, dist=self.dist)
+                        k_round=self.k_round, use_threshold=self.use_threshold, dist=self.dist,
+                        stop_mass=self.stop_mass, min_probes=self.min_probes)
 
     def _take(self, j, batch):
         try:

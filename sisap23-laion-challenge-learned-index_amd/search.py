@@ -9,6 +9,11 @@ result/{kind}/{size}/learned-index-...h5 (utils.py:85-97) read by eval/.
 Differences: the data must already be under data/ (no network here), and
 `--synthetic N` runs the same flow on an N-row synthetic clip768-like set.
 
+`--stop-mass P` (an addition, default off) turns on adaptive probing: the
+bucket count is the cap, and a query stops once the router's probability mass
+over the buckets it probed reaches P, after at least `--min-buckets M`
+(LearnedIndex.search).  The result identifier then ends in `-stop=P`.
+
 `--gpus N` (an addition) shards the index over N GPUs of one node: without a
 launcher the script starts its own N rank processes before any GPU call
 (li.dist.launch_ranks; under torchrun it runs as one of the ranks).  Every
@@ -69,9 +74,19 @@ def _synthetic(n, nq=10_000):
     return x @ P, q @ P, x, q
 
 
+def result_identifier(kind, size, epochs, lr, n_categories, model_type, bucket, stop_mass=None):
+    """utils.py:85-97's identifier (search.py:153-155); `-stop=P` only with --stop-mass."""
+    ident = (f'learned-index-{kind}-{size}-ep={epochs}-lr={lr}-cat='
+             f'{n_categories}-model={model_type}-buck={bucket}')
+    return ident if stop_mass is None else f'{ident}-stop={stop_mass}'
+
+
 def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc=None,
         n_categories=None, epochs=100, model_type='MLP', lr=0.1, preprocess=False, save=False,
-        synthetic=0, semantics='reference', index_path=None, train_mode='reference'):
+        synthetic=0, semantics='reference', index_path=None, train_mode='reference',
+        stop_mass=None, min_buckets=1):
+    from li.index import check_stop
+    check_stop(stop_mass, min_buckets)
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # one rank of `--gpus N` / torchrun: the process group (and this
@@ -141,7 +156,8 @@ def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc
             dists, nns = li.search(data_navigation=data, queries_navigation=queries,
                                    data_search=data_search, queries_search=queries_search,
                                    pred_categories=pred_categories, n_buckets=bucket, k=k,
-                                   use_threshold=True, semantics=semantics)
+                                   use_threshold=True, semantics=semantics,
+                                   stop_mass=stop_mass, min_buckets=min_buckets)
         else:
             _, pred_proba_categories = li.model.predict_proba(data_X_to_torch(queries))
             data['category'] = pred_categories
@@ -150,9 +166,15 @@ def run(kind, key, size='100K', k=10, index_type='learned-index', n_buckets_perc
                                           pred_categories=pred_proba_categories[:, 0], k=k)
         search_t = time.time() - s
         LOG.info(f'Search time: {search_t}')
+        if stop_mass is not None and bucket > 1:
+            # (outside the timed span: one more router call)
+            mean = li.mean_probes(data, queries, data_search, pred_categories, bucket,
+                                  stop_mass, min_buckets)
+            LOG.info(f'Mean buckets probed: {mean:.3f} of {bucket} (stop mass {stop_mass}, '
+                     f'at least {min_buckets})')
         short_identifier = 'learned-index'
-        identifier = (f'{short_identifier}-{kind}-{size}-ep={epochs}-lr={lr}-cat='
-                      f'{n_categories}-model={model_type}-buck={bucket}')
+        identifier = result_identifier(kind, size, epochs, lr, n_categories, model_type, bucket,
+                                       stop_mass)
         store_results(os.path.join("result/", kind, size, f"{identifier}.h5"),
                       short_identifier.capitalize(), kind, dists, nns, build_t, search_t,
                       identifier, size)
@@ -188,6 +210,12 @@ def build_parser():
                         help='reference: one optimizer step per epoch, on its last minibatch '
                              '(the reference\'s train_batch); minibatch: a step on every '
                              'minibatch, on the fused GPU training kernels')
+    parser.add_argument("--stop-mass", default=None, type=float,
+                        help='adaptive probing: stop a query once the router\'s probability mass '
+                             'over its probed buckets reaches P in (0, 1]; the bucket count is '
+                             'the cap (default: off, every query probes every bucket)')
+    parser.add_argument("--min-buckets", default=1, type=int,
+                        help='with --stop-mass: probe at least M buckets per query')
     return parser
 
 
@@ -202,4 +230,5 @@ if __name__ == "__main__":
     run(args.dataset, args.emb, args.size, args.k, 'learned-index',
         [int(b) for b in args.buckets_perc], args.n_categories, args.epochs, args.model_type,
         args.lr, args.preprocess, args.save, synthetic=args.synthetic, semantics=args.semantics,
-        index_path=args.index, train_mode=args.train_mode)
+        index_path=args.index, train_mode=args.train_mode, stop_mass=args.stop_mass,
+        min_buckets=args.min_buckets)
