@@ -25,7 +25,7 @@
 // It differs from the reference's BLAS dgemm only in summation order (a few
 // ulp of 1.0), so ids agree except where the reference's own float64 values
 // tie to that level.
-#include "lmi_common.hpp"
+#include "lmi_scan_internal.hpp"
 
 #include <algorithm>
 #include <mutex>
@@ -1911,16 +1911,20 @@ int bucket_topk_f64_impl(const lmi_index_desc* idx, const float* q, int32_t nq, 
         a.kth_stride = kth_stride;
     }
     if (phases & kPhasePlan) LMI_TRY(fill_u32(ws + w.nfailed, 0u, 1, s));
-    int rc = phases == 0 ? LMI_OK : w.passes
-        ? bucket_topk_wide(idx, q, nq, ldq, classes, R, k + 5, qmode, (float*)(ws + w.ld),
-                             (int32_t*)(ws + w.lpos), (int32_t*)(ws + w.lrow), kl, status,
-                             ws + w.scan, w.total - w.scan, s)
-        : bucket_topk_impl(idx, q, nq, ldq, classes, R, kl, qmode, (float*)(ws + w.ld),
-                           (int32_t*)(ws + w.lpos), (int32_t*)(ws + w.lrow), status,
-                           ws + w.scan, w.total - w.scan, s, nullptr, 0, true, seed,
-                           (float)(2.0 * eps), phases, nullptr, band ? (float*)(ws + w.lbound) : nullptr,
-                           global ? kth_send : nullptr, k);
-    if (rc != LMI_OK) return rc;
+    // the lists: k + 5 entries by the wide path (ldo = kl), else one scan of kl
+    ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R,
+               .k = w.passes ? k + 5 : kl, .qmode = qmode, .out_d = (float*)(ws + w.ld),
+               .out_pos = (int32_t*)(ws + w.lpos), .out_row = (int32_t*)(ws + w.lrow), .status = status,
+               .workspace = ws + w.scan, .ws_bytes = w.total - w.scan, .stream = s, .ldo = kl};
+    if (!w.passes) {  // (one scan: the seed, the phases and the band lists are its options)
+        c.seed_r0 = seed;
+        c.seed_margin = (float)(2.0 * eps);
+        c.phases = phases;
+        c.out_bound = band ? (float*)(ws + w.lbound) : nullptr;
+        c.kth_out = global ? kth_send : nullptr;
+        c.kth_k = k;
+    }
+    if (phases != 0) LMI_TRY(w.passes ? bucket_topk_wide(c) : bucket_topk_impl(c));
     const int64_t P = (int64_t)nq * R;
     if (!do_refine) return LMI_OK;
     if (global && P > 0) {

@@ -15,26 +15,31 @@
 //                      list: tile = (bucket, chunk of <= chunk_rows rows,
 //                      block of <= QB pairs), chunk-major so the query blocks
 //                      that re-read one chunk run back to back (L2 / MALL)
-//   scan_kernel        persistent; each workgroup dequeues tiles.  The QB
-//                      query rows of a tile sit in LDS; each wave streams
-//                      32-row sub-tiles of the chunk from HBM straight into
-//                      MFMA A fragments and multiplies them against all QB
-//                      queries (v_mfma_f32_32x32x16_f16: exact fp16 products,
-//                      fp32 accumulation; or v_mfma_f32_32x32x2_f32 for fp32
-//                      data).  The top-k epilogue runs on the accumulators:
-//                      d = 1 - dot/(|q||y|), a threshold filter against the
-//                      query's current k-th key (shared by all partial lists
-//                      of the query through an LDS atomic-min), survivors
-//                      appended to a per-lane LDS queue and inserted into a
-//                      per-lane register list in lockstep.  At the end of the
-//                      tile the 8 partial lists of each query are merged and
-//                      written as the tile's chunk list.
+//                      (with chunk centroids: nearest chunk first, pref_kernel
+//                      .. tile3_fill_kernel; else tail_split_kernel cuts each
+//                      queue's last tiles into row parts)
+//   scan3_kernel       (lmi_scan3.hpp) persistent, 8 waves; each workgroup
+//                      dequeues tiles.  The tile's queries live in registers
+//                      as MFMA B fragments, the chunk's rows are staged once
+//                      per workgroup through an LDS ring by DMA and shared by
+//                      the waves (v_mfma_f32_32x32x16_f16: exact fp16
+//                      products, fp32 accumulation).  The top-k epilogue runs
+//                      on the accumulators: d = 1 - dot/(|q||y|), a filter
+//                      against the pair's bound (thr_g, shared by the pair's
+//                      tiles), survivors inserted into per-lane register
+//                      lists; the tile's list is written as its chunk list.
+//                      It takes an fp16 corpus, fp16-exact queries and
+//                      d_pad == 768 with 10- or 15-entry lists; every other
+//                      shape runs scan2_kernel (the 4-wave ring) or
+//                      scan_kernel (general) of lmi_scan_v12.hip.
 //   chunk_merge_kernel per pair: merge its bucket's chunk lists -> top-k,
 //                      positions -> global positions.
+// scan_plan() makes every choice of one scan (kernel family, list length, tile
+// width, split parts, workspace offsets) and bucket_topk_impl runs it; k > 16
+// is lmi_scan_wide.hip, the split mode lmi_scan_split.hip.
 #include "lmi_scan_internal.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <mutex>
 #include <utility>
@@ -790,171 +795,6 @@ __global__ __launch_bounds__(kMergeBlock) void chunk_merge_band_kernel(
     if (sub == 0) out_bound[pid] = ub == 0xffffffffu ? __builtin_inff() : ord2f(ub);
 }
 
-// ---------------------------------------------------------------------------
-// k > 16: lower-bound passes
-// ---------------------------------------------------------------------------
-// After pass j (entries [j*kp, (j+1)*kp) of every pair's list): the next
-// pass's lower bound is the (distance, global position) key of the pass's last
-// entry; a pair whose pass came back short is exhausted (a key above every
-// real key: nothing passes).
-__global__ __launch_bounds__(256) void next_lo_kernel(const float* __restrict__ d,
-                                                      const int32_t* __restrict__ pos, int32_t P,
-                                                      int32_t ldo, int32_t last,
-                                                      unsigned long long* __restrict__ lo) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    const size_t o = (size_t)p * ldo + last;
-    const int32_t g = pos[o];
-    lo[p] = g < 0 ? ~0ull : (((unsigned long long)f2ord(d[o]) << 32) | (uint32_t)g);
-}
-
-// ---------------------------------------------------------------------------
-// k > 16: bound + collect (bucket_topk_wide)
-// ---------------------------------------------------------------------------
-// slot of the j-th list of a pair in the partial lists: chunks first, then
-// parts 1..S-1 of every split chunk (bit of sm) in ascending order (the order
-// chunk_merge_kernel reads them in; X = max_chunks / S)
-__device__ inline int wide_slot(int j, int nch_c, uint32_t sm, int S, int X) {
-    if (j < nch_c) return j;
-    const int jj = j - nch_c;
-    int nth = jj / (S - 1);
-    const int part = 1 + jj % (S - 1);
-    for (; nth > 0; --nth) sm &= sm - 1u;
-    return part * X + __builtin_ctz(sm);
-}
-
-// The bound pass's lists (one workgroup): bucket c of n_c rows gets L =
-// min(lists, n_c / 32) lists of r_c = n_c / L rows (up to a multiple of 32),
-// each scanning its first take_c = max(128, r_c / 4) rows (a sample); chunk_first
-// is the prefix of the list counts (a thread per contiguous run of buckets, then
-// a prefix over the threads).
-__global__ __launch_bounds__(256) void bound_lists_kernel(const int64_t* __restrict__ bucket_off, int32_t C,
-                                                          int32_t lists, int32_t* __restrict__ chunk_first,
-                                                          int32_t* __restrict__ sub_rows,
-                                                          int32_t* __restrict__ sub_take) {
-    __shared__ int32_t part[256];
-    const int t = threadIdx.x;
-    const int per = (C + 255) / 256;
-    const int c0 = min(C, t * per), c1 = min(C, c0 + per);
-    auto count = [&](int c) {
-        const int64_t n = bucket_off[c + 1] - bucket_off[c];
-        if (n <= 0) return 0;
-        const int64_t L = std::max<int64_t>(1, std::min<int64_t>(lists, n / 32));
-        const int64_t r = (n + L - 1) / L;
-        const int32_t rr = (int32_t)((r + 31) / 32 * 32);
-        sub_rows[c] = rr;
-        sub_take[c] = std::min(rr, std::max(128, (rr / 4 + 31) / 32 * 32));
-        return (int)((n + rr - 1) / rr);
-    };
-    int32_t acc = 0;
-    for (int c = c0; c < c1; ++c) acc += count(c);
-    part[t] = acc;
-    __syncthreads();
-    if (t == 0) {
-        int32_t run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    acc = part[t];
-    for (int c = c0; c < c1; ++c) {
-        chunk_first[c] = acc;
-        const int64_t n = bucket_off[c + 1] - bucket_off[c];
-        acc += n <= 0 ? 0 : (int32_t)((n + sub_rows[c] - 1) / sub_rows[c]);
-    }
-    if (c0 < C && c1 == C) chunk_first[C] = acc;
-}
-
-// outputs padded (+inf, -1), bounds and the fix-up flags cleared
-__global__ __launch_bounds__(256) void wide_init_kernel(int64_t P, int32_t ldo, float* __restrict__ d,
-                                                        int32_t* __restrict__ pos, int32_t* __restrict__ row,
-                                                        uint32_t* __restrict__ bound_ord,
-                                                        int32_t* __restrict__ fix) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < P * ldo) {
-        d[t] = __builtin_inff();
-        pos[t] = -1;
-        if (row) row[t] = -1;
-    }
-    if (t < P) {
-        bound_ord[t] = 0u;
-        fix[t] = 0;
-    }
-}
-
-// Per grouped pair of the chunk-list scan (one 64-lane workgroup): the kw-th
-// smallest distance ordinal over its chunk lists (each the part's own top-15,
-// so at least kw rows lie within it) by a 4-digit radix select; fewer than
-// kw entries: no bound, the pair goes to the fix-up passes.
-__global__ __launch_bounds__(64) void kth_bound_kernel(
-    const uint64_t* __restrict__ partial, int32_t max_chunks, int32_t S,
-    const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_bucket,
-    const int32_t* __restrict__ chunk_first, const uint32_t* __restrict__ split_mask, int32_t P,
-    int32_t kw, const int64_t* __restrict__ bucket_off, int32_t cap, uint32_t* __restrict__ bound_ord,
-    int32_t* __restrict__ fix) {
-    constexpr int KL = 15;
-    const int pp = blockIdx.x;
-    const int c = pair_bucket[pp];
-    if (c < 0) return;
-    const int p = pair_q[pp];
-    if (p < 0 || p >= P) return;
-    const uint32_t sm = split_mask != nullptr ? split_mask[pp] : 0u;
-    const int nch_c = chunk_first[c + 1] - chunk_first[c];
-    const int nl = nch_c + (S - 1) * __popc(sm);
-    const int X = max_chunks / S;
-    const uint64_t* base = partial + (size_t)pp * max_chunks * KL;
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_prefix, s_mask, s_rem, s_n;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_n = 0u;
-    __syncthreads();
-    uint32_t n = 0;
-    for (int e = tid; e < nl * KL; e += 64) {
-        const uint64_t key = base[(size_t)wide_slot(e / KL, nch_c, sm, S, X) * KL + e % KL];
-        n += key != kEmptyKey ? 1u : 0u;
-    }
-    atomicAdd(&s_n, n);
-    if (tid == 0) {
-        s_prefix = 0u;
-        s_mask = 0u;
-        s_rem = (uint32_t)kw;
-    }
-    __syncthreads();
-    if (s_n < (uint32_t)kw) {
-        // too few list entries: a bucket of no more rows than the slots is
-        // collected whole (no bound), else the pair takes the fix-up passes
-        // (bound_ord stays 0: the collect takes nothing)
-        if (tid == 0) {
-            if (bucket_off[c + 1] - bucket_off[c] <= cap) bound_ord[p] = 0xffffffffu;
-            else fix[p] = 1;
-        }
-        return;
-    }
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = tid; i < 256; i += 64) hist[i] = 0u;
-        __syncthreads();
-        const uint32_t prefix = s_prefix, mask = s_mask;
-        for (int e = tid; e < nl * KL; e += 64) {
-            const uint64_t key = base[(size_t)wide_slot(e / KL, nch_c, sm, S, X) * KL + e % KL];
-            const uint32_t h = (uint32_t)(key >> 32);
-            if (key != kEmptyKey && (h & mask) == prefix) atomicAdd(&hist[(h >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t rem = s_rem, dg = 0;
-            for (; dg < 255u && hist[dg] < rem; ++dg) rem -= hist[dg];
-            s_rem = rem;
-            s_prefix = prefix | (dg << shift);
-            s_mask = mask | (255u << shift);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) bound_ord[p] = s_prefix;
-}
-
 // the collect scan's per-grouped-pair bound (thr_g: the distance ordinal in
 // the high word) and candidate count; a pair whose bucket has skipped rows in
 // front of it (WideScan::app_d) starts with the skipped rows' own list
@@ -985,311 +825,61 @@ __global__ __launch_bounds__(256) void set_bound_kernel(const int32_t* __restric
     ccount[pp] = n;
 }
 
-// Per grouped pair of the collect scan (one 256-lane workgroup): its
-// candidates sorted by (distance, row) -- rows ascend with global position
-// inside a bucket, so this is the reference's (distance, g.index) order --
-// and the first kw written as (d, global position, row).  A pair whose
-// candidates overflowed (or, never for a sound scan, came back short) goes to
-// the fix-up passes.
-__global__ __launch_bounds__(256) void collect_select_kernel(
-    const uint64_t* __restrict__ cand, const uint32_t* __restrict__ ccount, int32_t cap,
-    const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_bucket,
-    const int32_t* __restrict__ gpos, int32_t P, int32_t kw, int32_t ldo,
-    const uint32_t* __restrict__ bound_ord, int32_t* __restrict__ fix, float* __restrict__ out_d,
-    int32_t* __restrict__ out_pos, int32_t* __restrict__ out_row) {
-    extern __shared__ uint64_t keys[];
-    const int pp = blockIdx.x;
-    if (pair_bucket[pp] < 0) return;
-    const int p = pair_q[pp];
-    if (p < 0 || p >= P || fix[p]) return;
-    const uint32_t n = ccount[pp];
-    const int tid = threadIdx.x;
-    // (fewer than kw: only a bucket collected whole, every row under the
-    // all-ones bound; never for a sound scan otherwise)
-    if (n > (uint32_t)cap || (n < (uint32_t)kw && bound_ord[p] != 0xffffffffu)) {
-        if (tid == 0) fix[p] = 1;
-        return;
-    }
-    uint32_t m = 1;
-    while (m < n) m <<= 1;
-    const uint64_t* src = cand + (size_t)pp * cap;
-    for (uint32_t i = tid; i < m; i += 256) keys[i] = i < n ? src[i] : kEmptyKey;
-    __syncthreads();
-    for (uint32_t k2 = 2; k2 <= m; k2 <<= 1) {
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = tid; i < m; i += 256) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = keys[i], y = keys[l];
-                    const bool up = (i & k2) == 0;
-                    if ((x > y) == up) {
-                        keys[i] = y;
-                        keys[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const size_t o = (size_t)p * ldo;
-    for (int i = tid; i < kw && i < (int)n; i += 256) {
-        const uint64_t key = keys[i];
-        const uint32_t r = (uint32_t)key;
-        out_d[o + i] = ord2f((uint32_t)(key >> 32));
-        out_pos[o + i] = gpos[r];
-        if (out_row) out_row[o + i] = (int32_t)r;
-    }
-}
-
-// the fix-up passes' classes: the pair's class where it needs them, else -1
-// (out of range: the plan skips the pair)
-__global__ __launch_bounds__(256) void fix_classes_kernel(const int32_t* __restrict__ classes,
-                                                          const int32_t* __restrict__ fix, int32_t P,
-                                                          int32_t* __restrict__ cls_fix) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < P) cls_fix[p] = fix[p] ? classes[p] : -1;
-}
-
-// the fix-up passes' lists over the outputs of the pairs that took them
-__global__ __launch_bounds__(256) void fix_combine_kernel(const int32_t* __restrict__ fix, int64_t P,
-                                                          int32_t ldo, const float* __restrict__ fd,
-                                                          const int32_t* __restrict__ fpos,
-                                                          const int32_t* __restrict__ frow,
-                                                          float* __restrict__ d, int32_t* __restrict__ pos,
-                                                          int32_t* __restrict__ row) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= P * ldo) return;
-    if (!fix[t / ldo]) return;
-    d[t] = fd[t];
-    pos[t] = fpos[t];
-    if (row) row[t] = frow[t];
-}
-
-// first k of every pair's pass list -> the caller's [P][k] outputs
-__global__ __launch_bounds__(256) void take_k_kernel(const float* __restrict__ d,
-                                                     const int32_t* __restrict__ pos, int64_t P,
-                                                     int32_t ldo, int32_t k, float* __restrict__ out_d,
-                                                     int32_t* __restrict__ out_pos) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= P * k) return;
-    const int64_t p = t / k;
-    const int j = (int)(t - p * k);
-    out_d[t] = d[(size_t)p * ldo + j];
-    out_pos[t] = pos[(size_t)p * ldo + j];
-}
-
-// ---------------------------------------------------------------------------
-// the split mode (ABI 9, idx->corpus32; bucket_topk_x below)
-// ---------------------------------------------------------------------------
-// One wave per query: q^ = q / |q| (float64 norm, sklearn's zero rule) rounded
-// to fp16, written as float32 rows of d_pad (zero-padded) -- the fp16-exact
-// queries the fp16 scan takes; float64 queries (q64) are rounded the same way.
-__global__ __launch_bounds__(kThreads) void x_round_queries_kernel(const float* __restrict__ q, int32_t ldq,
-                                                                   const double* __restrict__ q64,
-                                                                   int32_t ldq64, int32_t nq, int32_t d,
-                                                                   int32_t d_pad, float* __restrict__ out) {
-    const int row = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= nq) return;
-    double ss = 0.0;
-    for (int e = lane; e < d; e += 64) {
-        const double v = q64 ? q64[(size_t)row * ldq64 + e] : (double)q[(size_t)row * ldq + e];
-        ss = fma(v, v, ss);
-    }
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    double n = sqrt(ss);
-    if (n < 10.0 * 1.1920928955078125e-07) n = 1.0;
-    for (int e = lane; e < d_pad; e += 64) {
-        float h = 0.0f;
-        if (e < d) {
-            const double v = q64 ? q64[(size_t)row * ldq64 + e] : (double)q[(size_t)row * ldq + e];
-            h = (float)(_Float16)(float)(v / n);
-        }
-        out[(size_t)row * d_pad + e] = h;
-    }
-}
-
-// (+inf, -1) over every output entry (pairs whose class is out of range keep it)
-__global__ __launch_bounds__(256) void x_prefill_kernel(int64_t n, void* __restrict__ out_d, int32_t out_f64,
-                                                        int32_t* __restrict__ out_pos) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    if (out_f64) reinterpret_cast<double*>(out_d)[t] = __builtin_inf();
-    else reinterpret_cast<float*>(out_d)[t] = __builtin_inff();
-    out_pos[t] = -1;
-}
-
-// Per pair (by id): the collect bound d~_k + 2 eps as a distance ordinal,
-// rounded up (every row whose rounded distance is at most the real sum
-// passes); a list with fewer than k entries (a bucket shard of fewer rows)
-// collects its whole shard.
-__global__ __launch_bounds__(256) void x_bound_kernel(int64_t P, int32_t k, const float* __restrict__ ld,
-                                                      double two_eps, uint32_t* __restrict__ bound_ord) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    const float dk = ld[(size_t)p * k + k - 1];
-    if (!(dk < __builtin_inff())) {
-        bound_ord[p] = 0xffffffffu;
-        return;
-    }
-    const double b = (double)dk + two_eps;
-    const float f = (float)b;
-    // (the ordinal of the next float up when the float rounded the sum down)
-    bound_ord[p] = f2ord(f) + ((double)f < b ? 1u : 0u);
-}
-
-// The split mode's sampled bound (k <= 15): the kw-th distance ordinal of the
-// pair's sampled lists (kth_bound_kernel) + 2 eps, rounded up; all ones (a
-// bucket collected whole) and 0 (no bound: fix[p], the whole shard exactly)
-// stay as they are.
-__global__ __launch_bounds__(256) void x_margin_kernel(int64_t P, double two_eps, uint32_t* __restrict__ bound_ord) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    const uint32_t b = bound_ord[p];
-    if (b == 0u || b == 0xffffffffu) return;
-    const double v = (double)ord2f(b) + two_eps;
-    const float f = (float)v;
-    bound_ord[p] = f2ord(f) + ((double)f < v ? 1u : 0u);
-}
-
-// The split mode's sample (k <= 10): a descriptor of 2C buckets over the same
-// rows -- bucket 2c = the first s_c rows of bucket c, s_c = min(n_c,
-// max(chunk_rows, n_c / kXSampleDiv rounded up to 32 rows)), bucket 2c + 1 =
-// the rest (no chunks, never probed) -- so the product scan gives every pair
-// the k-th of its bucket's sample, an upper bound of its own (and the collect
-// then finds about k n_c / s_c <= k kXSampleDiv rows under it, far inside
-// its buffer at any bucket size).
-//
-// The collect scan's descriptor (x_collect_desc) skips the sample where it is
-// at most a quarter of the bucket (LMI_X_SKIP_SHARE): bucket 2c = the sample (no chunks, never
-// probed), 2c + 1 = the rest; a bucket with a larger sample is collected whole
-// (2c empty, 2c + 1 = the bucket).  The skipped rows' candidates are the
-// sample scan's own list (set_bound_kernel appends it): every skipped row the
-// select needs is in it unless the pair's band reaches the sample's k-th
-// (x_select_wave_kernel checks; 0.03% of the pairs on the 10M mixture,
-// tools/x_sample_cover.py), and those pairs are scored exactly over their
-// sample rows and candidates (x_fallback_kernel).
-constexpr int kXSampleDiv = 16;
-__global__ __launch_bounds__(64) void x_sample_desc_kernel(const int64_t* __restrict__ bucket_off, int32_t C,
-                                                           int64_t chunk_rows, const int32_t* __restrict__ classes,
-                                                           int32_t P, int64_t* __restrict__ off2,
-                                                           int32_t* __restrict__ cf2, int32_t* __restrict__ classes2,
-                                                           int64_t* __restrict__ off2b, int32_t* __restrict__ cf2b,
-                                                           int32_t* __restrict__ classes2b, int32_t skip_share) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        int32_t nch = 0, nchb = 0;
-        for (int c = 0; c < C; ++c) {
-            const int64_t a = bucket_off[c], n = bucket_off[c + 1] - a;
-            const int64_t want = std::max(chunk_rows, (n / kXSampleDiv + 31) / 32 * 32);
-            const int64_t sc = n < want ? n : want;
-            off2[2 * c] = a;
-            off2[2 * c + 1] = a + sc;
-            cf2[2 * c] = nch;
-            nch += (int32_t)((sc + chunk_rows - 1) / chunk_rows);
-            cf2[2 * c + 1] = nch;
-            // (a sample of at most 1 / skip_share of the bucket, LMI_X_SKIP_SHARE)
-            const int64_t skip = (skip_share > 0 && sc < n && sc * skip_share <= n) ? sc : 0;
-            off2b[2 * c] = a;
-            off2b[2 * c + 1] = a + skip;
-            cf2b[2 * c] = nchb;
-            cf2b[2 * c + 1] = nchb;
-            nchb += (int32_t)((n - skip + chunk_rows - 1) / chunk_rows);
-        }
-        off2[2 * C] = bucket_off[C];
-        cf2[2 * C] = nch;
-        off2b[2 * C] = bucket_off[C];
-        cf2b[2 * C] = nchb;
-    }
-    for (int i = blockIdx.x * 64 + threadIdx.x; i < P; i += gridDim.x * 64) {
-        const int32_t c = classes[i];
-        classes2[i] = c < 0 ? c : (c < C ? 2 * c : 2 * C);
-        classes2b[i] = c < 0 ? c : (c < C ? 2 * c + 1 : 2 * C);
-    }
-}
-
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct WsLayout {
-    size_t qbuf, invq, counts, pair_q, pair_bucket, tiles, ntiles, work, partial, thr_g, pref,
-        pref_tmp, pref_tmp2, n_seed, total;
-    int32_t max_tiles;
-    size_t ext_off, split_mask;  // tail split (scan v3)
-    size_t pair_pos;  // LMI_Q_SEED_ROUND0: grouped position of every pair id
-    size_t seed_pos;  //   and of every grouped pair's (q, 0)
-    int32_t qb;      // queries per tile
-    bool use_v2;     // scan2_kernel
-    bool use_v3;     // scan3_kernel
-    int32_t split_s; // row parts of a tail-split chunk (1: the tail split is off)
-};
+}  // namespace
 
-bool v2_eligible(const lmi_index_desc* idx, int qmode) {
-    if (env_config().scan_v1) return false;  // diagnostic switch: force the general kernel
-    return idx->dtype == LMI_F16 && qmode == LMI_Q_F16 && idx->d_pad == v2::D;
+int split_parts() {
+    return std::max(2, std::min(kSplitMaxParts, env_config().scan_split_parts));
 }
 
-bool v3_capable(const lmi_index_desc* idx, int qmode) {
-    if (env_config().scan_v2) return false;  // diagnostic switch: force the 4-wave ring
-    return v2_eligible(idx, qmode);
-}
-
-// list length of the scan: 10 (k <= 10), 15 (k <= 15 on scan v3: the float64
-// mode's 10 + 5 guard entries), else 16
-int pick_kl(const lmi_index_desc* idx, int qmode, int k) {
-    if (k <= 10) return 10;
-    if (k <= 15 && v3_capable(idx, qmode)) return 15;
-    return 16;
-}
-
-bool v3_eligible(const lmi_index_desc* idx, int qmode, int k) {
-    const int kl = pick_kl(idx, qmode, k);
-    return v3_capable(idx, qmode) && (kl == 10 || kl == 15);
-}
-
-WsLayout ws_layout(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false) {
-    WsLayout w{};
-    const int KL = pick_kl(idx, qmode, k);
-    const bool f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
-    w.use_v3 = v3_eligible(idx, qmode, k);
-    // the lower-bound passes (k > 16) run on v3 or the general kernel
-    w.use_v2 = !w.use_v3 && !lo && v2_eligible(idx, qmode);
-    const int QB = w.use_v3 ? v3::QB : w.use_v2 ? v2::QB : (f16math ? 64 : 32);
-    w.qb = QB;
+ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo) {
+    ScanPlan w{};
+    w.f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
+    // the rings take an fp16 corpus, fp16-exact queries and d_pad == 768; the
+    // diagnostic switches LMI_SCAN_V1 / LMI_SCAN_V2 force the general kernel /
+    // the 4-wave ring.  The 8-wave ring has 10- and 15-entry lists; the
+    // lower-bound passes (k > 16) run on it or on the general kernel
+    const bool ring4 = w.f16math && idx->d_pad == v2::D && !env_config().scan_v1;
+    const bool ring8 = ring4 && !env_config().scan_v2;
+    w.kl = k <= 10 ? 10 : (k <= 15 && ring8) ? 15 : 16;
+    w.family = ring8 && w.kl != 16 ? ScanKernel::Ring8 : ring4 && !lo ? ScanKernel::Ring4 : ScanKernel::General;
+    const bool v3 = w.family == ScanKernel::Ring8;
+    w.qb = v3 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math ? 64 : 32);
     const size_t P = (size_t)nq * R;
-    const size_t esz = f16math ? 2 : 4;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t at = off;
         off = align_up(off + bytes, 256);
         return at;
     };
-    w.qbuf = take((size_t)nq * idx->d_pad * esz);
+    w.qbuf = take((size_t)nq * idx->d_pad * (w.f16math ? 2 : 4));
     w.invq = take((size_t)nq * 4);
     w.counts = take((size_t)idx->n_buckets * 4);
     w.pair_q = take(P * 4);
     w.pair_bucket = take(P * 4);
     // tiles <= sum_c nch_c * ceil(cnt_c/QB) <= sum_c nch_c * (cnt_c/QB + 1)
-    const size_t mt = (P / QB + 1) * (size_t)std::max(idx->max_chunks, 1) + (size_t)idx->n_chunks;
+    const size_t X = (size_t)std::max(idx->max_chunks, 1);
+    const size_t mt = (P / w.qb + 1) * X + (size_t)idx->n_chunks;
     w.max_tiles = (int32_t)std::min<size_t>(mt, (size_t)INT32_MAX);
-    // (+ K (S - 1) free slots after every queue: the tail split's parts, in
-    // place; S = 1 when the split is off: not scan v3, the nearest-chunk-first
-    // plan, or LMI_SCAN_SPLIT < 0 -- the same predicate as bucket_topk_impl's
-    // split_k)
-    const bool nearest_first = w.use_v3 && idx->chunk_centroid && !env_config().scan_no_pref;
-    const bool split_on = w.use_v3 && !nearest_first && env_config().scan_split >= 0;
-    w.split_s = split_on ? split_parts() : 1;
-    // (the buffers are sized for split_parts() on scan v3 whether the split
-    // is on or not, so the total and every offset do not depend on the
+    // the tail split is off (one part) off the 8-wave ring, under the
+    // nearest-chunk-first plan and with LMI_SCAN_SPLIT < 0
+    w.nearest_first = v3 && idx->chunk_centroid && !env_config().scan_no_pref;
+    w.split_s = v3 && !w.nearest_first && env_config().scan_split >= 0 ? split_parts() : 1;
+    w.list_stride = w.split_s * (int32_t)X;
+    // (the buffers are sized for split_parts() on the 8-wave ring whether the
+    // split is on or not, so the total and every offset do not depend on the
     // LMI_SCAN_SPLIT / LMI_SCAN_NO_PREF knobs or on the index's centroids:
     // a workspace sized once fits every call)
-    const size_t S = w.use_v3 ? (size_t)split_parts() : 1;
+    const size_t S = v3 ? (size_t)split_parts() : 1;
+    // (+ K (S - 1) free slots after every queue: the tail split's parts, in place)
     w.tiles = take(((size_t)w.max_tiles + (size_t)kGroups * kSplitMaxK * (S - 1)) * sizeof(Tile));
     w.ntiles = take(4 * (3 * kGroups + 1));
     w.work = take(4 * (kGroups + 1));
     // (x S: the other parts of tail-split chunks, slot s * max_chunks + j)
     // (15-entry lists: room for the float64 mode's band slots, kBandSlot)
-    w.partial = take(P * (size_t)(S * std::max(idx->max_chunks, 1)) * (KL == 15 ? kBandSlot : KL) *
-                     sizeof(uint64_t));
+    w.partial = take(P * (S * X) * (w.kl == 15 ? kBandSlot : w.kl) * sizeof(uint64_t));
     w.ext_off = take(((size_t)idx->n_buckets + 1 + 2 * S * (size_t)kGroups * kSplitMaxK) * 8);
     w.split_mask = take(P * 4);
     w.thr_g = take(P * sizeof(uint64_t));
@@ -1303,12 +893,8 @@ WsLayout ws_layout(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     return w;
 }
 
-}  // namespace
-
-bool band_capable(const lmi_index_desc* idx, int qmode) { return v3_capable(idx, qmode); }
-
-int split_parts() {
-    return std::max(2, std::min(kSplitMaxParts, env_config().scan_split_parts));
+bool band_capable(const lmi_index_desc* idx, int qmode) {
+    return scan_plan(idx, 0, 1, 10, qmode).family == ScanKernel::Ring8;
 }
 
 namespace {
@@ -1366,6 +952,41 @@ int launch_scan3(const Scan2Args& b, hipStream_t s) {
     return launch_scan3_v<KL, 0>(b, s);
 }
 
+// The kernel of one call: the instantiation that serves the plan's family and
+// list length, the wide mode (WideScan::mode, 0: none), lower bounds (lo) and
+// band lists (band); neither where none does -- a caller's mistake: the wide
+// scans and the band lists take the 8-wave ring with 15 entries (10: the
+// collect), the lower-bound passes its 15 or the general kernel's 16
+struct ScanLaunch {
+    int (*ring)(const Scan2Args&, hipStream_t);
+    int (*general)(const ScanArgs&, int, hipStream_t);
+};
+ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
+    const int kl = p.kl, mode = c.wide ? c.wide->mode : 0;
+    const bool lo = c.lo_g != nullptr, band = c.out_bound != nullptr, corpus_f16 = c.idx->dtype == LMI_F16;
+    const bool plain = mode == 0 && !lo && !band;
+    if (p.family == ScanKernel::Ring8) {
+        if (mode == 1 && !lo && !band && kl == 15) return {launch_scan3_v<15, 0, false, 1>, nullptr};
+        if (mode == 2 && !lo && !band && kl == 10) return {launch_scan3_v<10, 0, false, 2>, nullptr};
+        if (mode == 0 && lo && !band && kl == 15) return {launch_scan3_v<15, 0, true>, nullptr};
+        if (mode == 0 && !lo && band && kl == 15) return {launch_scan3_v<10, 0, false, 3>, nullptr};
+        if (plain) return {kl == 10 ? launch_scan3<10> : launch_scan3<15>, nullptr};
+    } else if (p.family == ScanKernel::Ring4) {
+        if (plain) return {kl == 10 ? launch_scan2<10> : launch_scan2<16>, nullptr};
+    } else if (mode == 0 && lo && !band && kl == 16) {
+        return {nullptr, p.f16math                  ? launch_scan<16, true, _Float16, true>
+                         : corpus_f16   ? launch_scan<16, false, _Float16, true>
+                                        : launch_scan<16, false, float, true>};
+    } else if (plain && p.f16math) {
+        return {nullptr, kl == 10 ? launch_scan<10, true, _Float16> : launch_scan<16, true, _Float16>};
+    } else if (plain && corpus_f16) {
+        return {nullptr, kl == 10 ? launch_scan<10, false, _Float16> : launch_scan<16, false, _Float16>};
+    } else if (plain) {
+        return {nullptr, kl == 10 ? launch_scan<10, false, float> : launch_scan<16, false, float>};
+    }
+    return {nullptr, nullptr};
+}
+
 }  // namespace
 }  // namespace lmi
 
@@ -1396,7 +1017,7 @@ extern "C" int32_t lmi_plan_chunks(const int64_t* bucket_off_host, int32_t n_buc
 size_t lmi::scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
                                  int32_t qmode, bool lo) {
     if (!idx || nq < 0 || R < 1 || k < 1) return 0;
-    return lmi::ws_layout(idx, nq, R, k, qmode, lo).total;
+    return scan_plan(idx, nq, R, k, qmode, lo).total;
 }
 
 extern "C" size_t lmi_scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R,
@@ -1429,48 +1050,24 @@ extern "C" int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_
     if (idx && idx->corpus32)  // (phases: k <= 10, ABI 11)
         return bucket_topk_x(idx, q, nq, ldq, nullptr, 0, classes, R, k, out_d, 0, out_pos, status, workspace,
                              ws_bytes, s, phases);
-    if (k <= LMI_MAX_K)
-        return bucket_topk_impl(idx, q, nq, ldq, classes, R, k, qmode, out_d, out_pos, nullptr,
-                                status, workspace, ws_bytes, s, nullptr, 0, true, seed, 0.0f, phases);
-    if (phases != kPhaseAll) {
-        set_error("phase flags need k <= %d (one scan pass)", LMI_MAX_K);
-        return LMI_E_UNSUPPORTED;
-    }
-    LMI_CHECK_ARG(idx != nullptr, "null index");
-    LMI_CHECK_ARG(k <= LMI_MAX_K_PASSES, "k=%d outside [1, %d]", k, LMI_MAX_K_PASSES);
-    LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "bad nq/R");
-    if (nq == 0) return LMI_OK;
-    LMI_CHECK_ARG(out_d && out_pos && workspace, "null pointer");
-    int kp;
-    const int ldo = passes_of(idx, qmode, k, &kp) * kp;
-    const size_t P = (size_t)nq * R;
-    const size_t lists = align_up(P * ldo * 4, 256);
-    if (ws_bytes < 2 * lists) {
-        set_error("workspace %zu B < required %zu B", ws_bytes, 2 * lists);
-        return LMI_E_WORKSPACE;
-    }
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    float* ld = reinterpret_cast<float*>(ws);
-    int32_t* lp = reinterpret_cast<int32_t*>(ws + lists);
-    const int rc = bucket_topk_wide(idx, q, nq, ldq, classes, R, k, qmode, ld, lp, nullptr, ldo,
-                                    status, ws + 2 * lists, ws_bytes - 2 * lists, s);
-    if (rc != LMI_OK) return rc;
-    hipLaunchKernelGGL(take_k_kernel, dim3((unsigned)((P * k + 255) / 256)), dim3(256), 0, s, ld, lp,
-                       (int64_t)P, ldo, k, out_d, out_pos);
-    LMI_LAUNCH_CHECK("take_k_kernel");
-    return LMI_OK;
+    const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
+                     .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
+                     .workspace = workspace, .ws_bytes = ws_bytes, .stream = s, .seed_r0 = seed,
+                     .phases = phases};
+    return k <= LMI_MAX_K ? bucket_topk_impl(c) : bucket_topk_wide_k(c);
 }
 
-int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq,
-                          const int32_t* classes, int32_t R, int32_t k, int32_t qmode, float* out_d,
-                          int32_t* out_pos, int32_t* out_row, int32_t* status, void* workspace,
-                          size_t ws_bytes, hipStream_t s, const unsigned long long* lo_g, int32_t ldo,
-                          bool prefill, bool seed_r0, float seed_margin, int phases,
-                          const WideScan* wide, float* out_bound, float* kth_out, int32_t kth_k) {
-    const bool do_plan = phases & kPhasePlan, do_scan = phases & kPhaseScan,
-               do_merge = phases & kPhaseMerge;
+int lmi::bucket_topk_impl(const ScanCall& c) {
     using namespace lmi;
-    if (ldo <= 0) ldo = k;
+    const lmi_index_desc* idx = c.idx;
+    const int32_t nq = c.nq, ldq = c.ldq, R = c.R, k = c.k, qmode = c.qmode, ldo = c.ldo > 0 ? c.ldo : k;
+    const int32_t* classes = c.classes;
+    const unsigned long long* lo_g = c.lo_g;
+    const WideScan* wide = c.wide;
+    float *out_d = c.out_d, *out_bound = c.out_bound, *kth_out = c.kth_out;
+    int32_t *out_pos = c.out_pos, *out_row = c.out_row, *status = c.status;
+    hipStream_t s = c.stream;
+    const bool do_plan = c.phases & kPhasePlan, do_scan = c.phases & kPhaseScan, do_merge = c.phases & kPhaseMerge;
     LMI_CHECK_ARG(idx != nullptr, "null index");
     LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32, "bad corpus dtype");
     LMI_CHECK_ARG(idx->d >= 1 && idx->d_pad >= idx->d && idx->d_pad % 32 == 0, "bad d/d_pad");
@@ -1482,66 +1079,58 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32, "bad qmode");
     LMI_CHECK_ARG(ldq >= idx->d, "ldq < d");
     if (nq == 0) return LMI_OK;
-    LMI_CHECK_ARG(q && classes && out_d && out_pos && status && workspace, "null pointer");
+    LMI_CHECK_ARG(c.q && classes && out_d && out_pos && status && c.workspace, "null pointer");
     LMI_CHECK_ARG(idx->n_rows == 0 || (idx->corpus && idx->inv_norm && idx->gpos), "null corpus arrays");
     LMI_CHECK_ARG(idx->bucket_off && idx->chunk_first, "null bucket tables");
 
-    const bool LOP = lo_g != nullptr;
-    const WsLayout w = ws_layout(idx, nq, R, k, qmode, LOP);
-    if (ws_bytes < w.total) {
-        set_error("workspace %zu B < required %zu B", ws_bytes, w.total);
+    const ScanPlan w = c.plan ? *c.plan : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr);
+    if (c.ws_bytes < w.total) {
+        set_error("workspace %zu B < required %zu B", c.ws_bytes, w.total);
         return LMI_E_WORKSPACE;
     }
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    const bool f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
-    const int QB = w.qb;
+    const bool ring = w.family != ScanKernel::General, v3 = w.family == ScanKernel::Ring8;
+    const ScanLaunch launch = pick_launch(w, c);
+    if (!launch.ring && !launch.general) {
+        set_error("no scan kernel takes this call's wide mode, lower bounds or band lists with %d-entry lists", w.kl);
+        return LMI_E_UNSUPPORTED;
+    }
+    auto* ws = reinterpret_cast<unsigned char*>(c.workspace);
     const int P = nq * R;
-    const int KL = pick_kl(idx, qmode, k);
 
     // the plan's per-pair initial values, written by prep: pair_bucket = -1
     // (pairs whose class is out of range are never filled), pair_pos = -1 (the
     // seed), split_mask = 0, the per-pair bounds thr_g = all ones (scan v2/v3)
     PrepFills fills{};
-    const bool seed_plan = seed_r0 && w.use_v3 && !(lo_g != nullptr) && R > 1;
+    const bool seed = c.seed_r0 && v3 && !(lo_g != nullptr) && R > 1;
     // the float64 mode's band lists (out_bound: every pair's bound of its
     // unlisted rows, +inf until the merge writes it)
     const bool band = out_bound != nullptr;
-    if (band && !(w.use_v3 && KL == 15 && lo_g == nullptr && wide == nullptr)) {
-        set_error("internal: band lists need scan v3 with 15-entry lists");
-        return LMI_E_INVALID;
-    }
-    if (band) {
-        fills.p[fills.n] = reinterpret_cast<uint32_t*>(out_bound);
-        fills.v[fills.n] = 0x7f800000u;
-        fills.per_q[fills.n] = R;
+    auto add = [&](void* ptr, uint32_t v, int per_q) {
+        fills.p[fills.n] = reinterpret_cast<uint32_t*>(ptr);
+        fills.v[fills.n] = v;
+        fills.per_q[fills.n] = per_q;
         ++fills.n;
-
-    }
+    };
+    if (band) add(out_bound, 0x7f800000u, R);
     if (idx->n_rows > 0) {
-        auto add = [&](void* ptr, uint32_t v, int per_q) {
-            fills.p[fills.n] = reinterpret_cast<uint32_t*>(ptr);
-            fills.v[fills.n] = v;
-            fills.per_q[fills.n] = per_q;
-            ++fills.n;
-        };
         add(ws + w.pair_bucket, 0xffffffffu, R);
-        if (seed_plan) add(ws + w.pair_pos, 0xffffffffu, R);
+        if (seed) add(ws + w.pair_pos, 0xffffffffu, R);
         add(ws + w.split_mask, 0u, R);
-        if (w.use_v2 || w.use_v3) add(ws + w.thr_g, 0xffffffffu, 2 * R);
+        if (ring) add(ws + w.thr_g, 0xffffffffu, 2 * R);
     }
     if (do_plan) {
         const dim3 pg((nq + kThreads / 64 - 1) / (kThreads / 64));
-        const bool vec = ((uintptr_t)q % 16 == 0) && (ldq % 4 == 0);
-        auto* kp = f16math ? (vec ? prep_kernel<true, true> : prep_kernel<true, false>)
-                           : (vec ? prep_kernel<false, true> : prep_kernel<false, false>);
-        hipLaunchKernelGGL(kp, pg, dim3(kThreads), 0, s, q, nq, ldq, idx->d, idx->d_pad,
+        const bool vec = ((uintptr_t)c.q % 16 == 0) && (ldq % 4 == 0);
+        auto* kp = w.f16math ? (vec ? prep_kernel<true, true> : prep_kernel<true, false>)
+                             : (vec ? prep_kernel<false, true> : prep_kernel<false, false>);
+        hipLaunchKernelGGL(kp, pg, dim3(kThreads), 0, s, c.q, nq, ldq, idx->d, idx->d_pad,
                            (void*)(ws + w.qbuf), (float*)(ws + w.invq), status, out_d, out_pos,
-                           out_row, prefill ? R * ldo : 0, fills);
+                           out_row, c.prefill ? R * ldo : 0, fills);
         LMI_LAUNCH_CHECK("prep_kernel");
     }
     if (idx->n_rows == 0) {
         // (an empty shard lists nothing: its kth block is all +inf)
-        if (kth_out != nullptr && do_merge) LMI_TRY(fill_u32(kth_out, 0x7f800000u, (size_t)P * kth_k, s));
+        if (kth_out != nullptr && do_merge) LMI_TRY(fill_u32(kth_out, 0x7f800000u, (size_t)P * c.kth_k, s));
         return LMI_OK;
     }
 
@@ -1562,24 +1151,17 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     }
     // (the seed reads the pair position of every (q, 0); pairs whose class is
     // out of range keep -1)
-    const bool seed = seed_plan;
     int32_t* pair_pos = seed ? (int32_t*)(ws + w.pair_pos) : nullptr;
-    const bool nearest_first = w.use_v3 && idx->chunk_centroid && !env_config().scan_no_pref;
-    // tail split (scan v3): K = the queue's share of the grid; plan_fill leaves
-    // K (S - 1) free slots after every queue for its parts
+    // tail split (where the plan has parts): K = the queue's share of the grid;
+    // plan_fill leaves K (S - 1) free slots after every queue for its parts
     // (not in the wide path's bound scan: its lists are the bucket's own)
-    const int split_k = !w.use_v3 || nearest_first || env_config().scan_split < 0 ||
-                        (wide && wide->mode == 1) ? 0
+    const int split_k = w.split_s < 2 || (wide && wide->mode == 1) ? 0
                         : std::min(kSplitMaxK, env_config().scan_split > 0 ? env_config().scan_split
                                                                             : (num_cus() + ng - 1) / ng);
-    if (split_k > 0 && w.split_s < 2) {
-        set_error("internal: tail split and workspace layout disagree");
-        return LMI_E_INVALID;
-    }
     const int qpad = split_k * (w.split_s - 1);
     if (do_plan) {
         hipLaunchKernelGGL(plan_fill_kernel, dim3(C), dim3(kPlanThreads), 0, s, classes, P, C, counts,
-                           idx->chunk_first, QB, pair_q, pair_bucket, tiles, meta, work, ng, pair_pos,
+                           idx->chunk_first, w.qb, pair_q, pair_bucket, tiles, meta, work, ng, pair_pos,
                            qpad);
         LMI_LAUNCH_CHECK("plan_fill_kernel");
     }
@@ -1589,7 +1171,7 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
                            P, R, seed_pos);
         LMI_LAUNCH_CHECK("seed_pos_kernel");
     }
-    if (do_plan && nearest_first) {
+    if (do_plan && w.nearest_first) {
         int32_t* pref = (int32_t*)(ws + w.pref);
         int32_t* n_seed = (int32_t*)(ws + w.n_seed);
         hipLaunchKernelGGL(pref_kernel, dim3((P + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads),
@@ -1597,14 +1179,14 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
                            (const _Float16*)(ws + w.qbuf), pair_q, R, P, pref);
         LMI_LAUNCH_CHECK("pref_kernel");
         hipLaunchKernelGGL(pref_sort_kernel, dim3(C), dim3(kThreads), 0, s, counts, idx->chunk_first,
-                           pair_q, pref, (int32_t*)(ws + w.pref_tmp), (int32_t*)(ws + w.pref_tmp2), QB,
+                           pair_q, pref, (int32_t*)(ws + w.pref_tmp), (int32_t*)(ws + w.pref_tmp2), w.qb,
                            n_seed);
         LMI_LAUNCH_CHECK("pref_sort_kernel");
         hipLaunchKernelGGL(tile3_fill_kernel, dim3(C), dim3(kThreads), 0, s, counts, idx->chunk_first,
-                           pref, n_seed, C, QB, tiles, meta, work);
+                           pref, n_seed, C, w.qb, tiles, meta, work);
         LMI_LAUNCH_CHECK("tile3_fill_kernel");
     }
-    if (nearest_first) ng = 1;  // one queue: seed tiles strictly first
+    if (w.nearest_first) ng = 1;  // one queue: seed tiles strictly first
 
     // tail split (scan v3; not after the nearest-chunk-first plan: its queue
     // has no seed count)
@@ -1634,7 +1216,7 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     a.inv_norm = idx->inv_norm;
     a.bucket_off = idx->bucket_off;
     a.chunk_rows = idx->chunk_rows;
-    a.max_chunks = w.split_s * std::max(idx->max_chunks, 1);  // the partial-list stride (+ split parts)
+    a.max_chunks = w.list_stride;  // the partial-list stride (+ split parts)
     a.qbuf = ws + w.qbuf;
     a.invq = (const float*)(ws + w.invq);
     a.pair_q = pair_q;
@@ -1646,12 +1228,11 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     a.gpos = idx->gpos;
     a.lo_g = lo_g;
 
-    int rc;
-    if (phases != kPhaseAll && !(w.use_v2 || w.use_v3)) {
+    if (c.phases != kPhaseAll && !ring) {
         set_error("phase flags need the fp16 scan (scan v2/v3: fp16 corpus and fp16-exact queries)");
         return LMI_E_UNSUPPORTED;
     }
-    if (w.use_v2 || w.use_v3) {
+    if (ring && do_scan) {
         Scan2Args b{};
         b.corpus = reinterpret_cast<const _Float16*>(idx->corpus);
         b.inv_norm = idx->inv_norm;
@@ -1666,24 +1247,17 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
         b.meta = meta;
         b.work = work;
         b.partial = a.partial;
-        b.thr_g = reinterpret_cast<unsigned long long*>(ws + w.thr_g);
+        b.thr_g = reinterpret_cast<unsigned long long*>(ws + w.thr_g);  // (reset by prep)
         b.gpos = idx->gpos;
         b.lo_g = lo_g;
         b.pair_pos = seed_pos;
-        b.seed_margin = seed_margin;
+        b.seed_margin = c.seed_margin;
         // (MODE 3: 2 eps = the seed margin of the float64 mode, rounded up,
         // + 2^-22 for the rounding of bound + band, distances being < 4)
-        b.band = band ? seed_margin * (1.0f + 0x1p-20f) + 0x1p-22f : 0.0f;
+        b.band = band ? c.seed_margin * (1.0f + 0x1p-20f) + 0x1p-22f : 0.0f;
         b.ng = ng;
         b.lag = std::max(0, std::min(3, env_config().scan_lag));
-        // (thr_g was reset by prep)
-        if (!do_scan) rc = LMI_OK;
-        else
         if (wide) {
-            if (!w.use_v3 || LOP || (wide->mode == 1 ? KL != 15 : KL != 10)) {
-                set_error("internal: the wide scans take scan v3 with 15 (chunk lists) or 10 (collect) entries");
-                return LMI_E_INVALID;
-            }
             b.cand = wide->cand;
             b.ccount = wide->ccount;
             b.cap = wide->cap;
@@ -1691,49 +1265,18 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
             b.nbins = wide->nbins;
             b.sub_rows = wide->sub_rows;
             b.sub_take = wide->sub_take;
-            rc = wide->mode == 1 ? launch_scan3_v<15, 0, false, 1>(b, s) : launch_scan3_v<10, 0, false, 2>(b, s);
         }
-        else if (w.use_v3 && LOP) {
-            // the passes' lists are 15 entries on v3 (passes_of)
-            if (KL != 15) {
-                set_error("lower-bound scan passes take 15-entry lists on scan v3");
-                return LMI_E_UNSUPPORTED;
-            }
-            rc = launch_scan3_v<15, 0, true>(b, s);
-        }
-        else if (w.use_v3 && band)
-            rc = launch_scan3_v<10, 0, false, 3>(b, s);
-        else if (w.use_v3)
-            rc = (KL == 10) ? launch_scan3<10>(b, s) : launch_scan3<15>(b, s);
-        else
-            rc = (KL == 10) ? launch_scan2<10>(b, s) : launch_scan2<16>(b, s);
-    } else if (LOP) {
-        // lower-bound passes off v3: the general kernel, 16-entry lists
-        if (KL != 16) {
-            set_error("lower-bound scan passes need 16-entry lists off scan v3");
-            return LMI_E_UNSUPPORTED;
-        }
-        rc = f16math ? launch_scan<16, true, _Float16, true>(a, idx->d_pad, s)
-           : (idx->dtype == LMI_F16) ? launch_scan<16, false, _Float16, true>(a, idx->d_pad, s)
-                                     : launch_scan<16, false, float, true>(a, idx->d_pad, s);
-    } else if (f16math) {
-        rc = (KL == 10) ? launch_scan<10, true, _Float16>(a, idx->d_pad, s)
-                        : launch_scan<16, true, _Float16>(a, idx->d_pad, s);
-    } else if (idx->dtype == LMI_F16) {
-        rc = (KL == 10) ? launch_scan<10, false, _Float16>(a, idx->d_pad, s)
-                        : launch_scan<16, false, _Float16>(a, idx->d_pad, s);
-    } else {
-        rc = (KL == 10) ? launch_scan<10, false, float>(a, idx->d_pad, s)
-                        : launch_scan<16, false, float>(a, idx->d_pad, s);
+        LMI_TRY(launch.ring(b, s));
+    } else if (!ring) {
+        LMI_TRY(launch.general(a, idx->d_pad, s));
     }
-    if (rc != LMI_OK) return rc;
     if (!do_merge) return LMI_OK;
 
     const int grid = (int)(((int64_t)P * kMergeLanes + kMergeBlock - 1) / kMergeBlock);
     if (band) {
         hipLaunchKernelGGL(chunk_merge_band_kernel, dim3(grid), dim3(kMergeBlock), 0, s, a.partial, a.max_chunks,
                            pair_q, pair_bucket, idx->chunk_first, idx->gpos, P, k, ldo, out_d, out_pos,
-                           out_row, out_bound, idx->n_rows, status, split_mask, w.split_s, kth_out, kth_k,
+                           out_row, out_bound, idx->n_rows, status, split_mask, w.split_s, kth_out, c.kth_k,
                            classes, C);
         LMI_LAUNCH_CHECK("chunk_merge_band_kernel");
         return LMI_OK;
@@ -1742,9 +1285,9 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     hipLaunchKernelGGL((chunk_merge_kernel<KLV, ROWSV>), dim3(grid), dim3(kMergeBlock), 0, s, a.partial, \
                        a.max_chunks, pair_q, pair_bucket, idx->chunk_first, idx->gpos, P, k, ldo,  \
                        out_d, out_pos, out_row, idx->n_rows, status, split_mask, w.split_s)
-    if (KL == 10) {
+    if (w.kl == 10) {
         if (out_row) LMI_CM(10, true); else LMI_CM(10, false);
-    } else if (KL == 15) {
+    } else if (w.kl == 15) {
         if (out_row) LMI_CM(15, true); else LMI_CM(15, false);
     } else {
         if (out_row) LMI_CM(16, true); else LMI_CM(16, false);
@@ -1754,606 +1297,11 @@ int lmi::bucket_topk_impl(const lmi_index_desc* idx, const float* q, int32_t nq,
     return LMI_OK;
 }
 
-namespace lmi {
-// |d~ - d| for every (query, row) of the split mode, d~ the fp16 scan's
-// distance on the normalised, fp16-rounded vectors and d the exact one:
-// rounding a unit vector to fp16 moves it by delta <= 2^-11 (relative, normal
-// range; + 2^-22 for the float32 step before it) + sqrt(d) 2^-25 (absolute,
-// the subnormal range), i.e. by an angle <= asin(delta); the angle between
-// query and row moves by at most the two angles, and a cosine by at most the
-// angle.  Plus the fp16 scan's own arithmetic on the rounded vectors
-// (refine_eps of li/index.py, the fp16 path: gamma(2 (d_pad/16 + 16)) for the
-// dot, the two norms, the scale and the final fma) and 2^-24 for rounding the
-// exact value to float32 (ties of the rounded values then order by position).
-double split_eps(int d_pad) {
-    const double u = std::ldexp(1.0, -24);
-    auto gamma = [&](double n) { return n * u / (1.0 - n * u); };
-    const double delta = std::ldexp(1.0, -11) + std::ldexp(1.0, -22) + std::sqrt((double)d_pad) * std::ldexp(1.0, -25);
-    const double h = 2.0 * (d_pad / 16 + 16), hq = 4.0 * ((d_pad + 255) / 256) + 6.0;
-    const double scan = gamma(h) + gamma(2 * hq) / 2 + 4 * u + u + 2 * u + 2 * u;
-    return 2.0 * std::asin(delta) + scan + u;
-}
-
-namespace {
-struct XWs {
-    size_t qr, ld, lpos, srow, bound, ccount, cand, failed, nfailed, wgl, sfl, spd, spg, fix, bins, sub_first, sub_rows, sub_take,
-        off2, cf2, classes2, off2b, cf2b, classes2b, qn32, grp, tailq, goff, region, region_bytes, region_s,
-        region_s_bytes, total;
-    int32_t cap;
-};
-// k <= 10: the k-th of a per-bucket sample (the product scan over
-// x_sample_desc); the device tables are filled by x_sample_desc_kernel
-inline bool x_sample(int k) { return k <= 10; }
-lmi_index_desc x_sample_desc(const lmi_index_desc* idx, const int64_t* off2, const int32_t* cf2) {
-    lmi_index_desc d = *idx;
-    d.n_buckets = 2 * idx->n_buckets;
-    d.bucket_off = off2;
-    d.chunk_first = cf2;
-    // (host-side bounds for the workspace: a sample of at most n_c / 16 + 32
-    // rows beyond one chunk)
-    d.max_chunks = 2 + std::max(idx->max_chunks, 1) / kXSampleDiv;
-    d.n_chunks = idx->n_buckets * d.max_chunks;
-    d.chunk_centroid = nullptr;
-    return d;
-}
-// the collect scan's: the rest of every bucket whose sample is skipped, the
-// others whole (x_sample_desc_kernel)
-lmi_index_desc x_collect_desc(const lmi_index_desc* idx, const int64_t* off2b, const int32_t* cf2b) {
-    lmi_index_desc d = *idx;
-    d.n_buckets = 2 * idx->n_buckets;
-    d.bucket_off = off2b;
-    d.chunk_first = cf2b;
-    d.chunk_centroid = nullptr;
-    return d;
-}
-// k <= 15: the k-th comes from a sampled bound scan (the wide path's chunk-list
-// scan over two lists per bucket, each the first quarter of its rows), not a
-// whole first scan
-constexpr int kXLists = 2;
-inline bool x_sampled(int k) { return k <= 15; }
-lmi_index_desc bound_desc(const lmi_index_desc* idx, int lists, const int32_t* sub_first);
-
-XWs x_ws(const lmi_index_desc* idx, int nq, int R, int k) {
-    XWs w{};
-    const size_t P = (size_t)nq * R;
-    // collect slots per pair: 2048 (the rows within 2 eps of the k-th, ~20 on
-    // the clip768-like mixture), fewer for huge batches (<= 2 GiB of slots)
-    int cap = 2048;
-    while (cap > 256 && P * (size_t)cap * 8 > (size_t(2) << 30)) cap >>= 1;
-    w.cap = cap;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    w.qr = take((size_t)nq * idx->d_pad * 4);
-    w.ld = take(P * std::max(k, 15) * 4);
-    w.lpos = take(P * std::max(k, 15) * 4);
-    w.srow = take(P * std::max(k, 15) * 4);
-    w.fix = take(P * 4);
-    w.bins = take(P * 4);
-    w.sub_first = take(((size_t)idx->n_buckets + 1) * 4);
-    w.sub_rows = take((size_t)idx->n_buckets * 4);
-    w.sub_take = take((size_t)idx->n_buckets * 4);
-    w.off2 = take(((size_t)2 * idx->n_buckets + 1) * 8);
-    w.cf2 = take(((size_t)2 * idx->n_buckets + 1) * 4);
-    w.classes2 = take(P * 4);
-    w.off2b = take(((size_t)2 * idx->n_buckets + 1) * 8);
-    w.cf2b = take(((size_t)2 * idx->n_buckets + 1) * 4);
-    w.classes2b = take(P * 4);
-    w.qn32 = take((size_t)nq * idx->d_pad * 4);
-    w.grp = take((size_t)R * idx->n_buckets * 4);
-    w.tailq = take(P);
-    w.goff = take(((size_t)idx->n_buckets + 1) * 8);
-    w.bound = take(P * 4);
-    w.ccount = take(P * 4);
-    w.cand = take(P * (size_t)cap * 8);
-    w.failed = take(P * 4);
-    w.nfailed = take(256);  // (word 0: the failed pairs; word 8: the sfl pairs; word 16: the wgl pairs)
-    w.wgl = take(P * 4);
-    w.sfl = take(P * 4);
-    // (the sliced sample fallback's lists)
-    w.spd = take((size_t)kXSlicedPairs * kXSlices * k * 8);
-    w.spg = take((size_t)kXSlicedPairs * kXSlices * k * 4);
-    const lmi_index_desc bd = bound_desc(idx, kXLists, nullptr);
-    const lmi_index_desc sd = x_sample_desc(idx, nullptr, nullptr);
-    const lmi_index_desc cd = x_collect_desc(idx, nullptr, nullptr);
-    w.region_bytes = std::max({ws_layout(idx, nq, R, k, LMI_Q_F16).total, ws_layout(idx, nq, R, 10, LMI_Q_F16).total,
-                               ws_layout(&bd, nq, R, 15, LMI_Q_F16).total, ws_layout(&sd, nq, R, k, LMI_Q_F16).total,
-                               ws_layout(&cd, nq, R, 10, LMI_Q_F16).total});
-    w.region = take(w.region_bytes);
-    // k <= 10: the sample scan's own region (ABI 11), so the plans of both
-    // scans are laid down in one PLAN phase and the batch stream can run the
-    // phases of one batch apart
-    if (x_sample(k)) {
-        w.region_s_bytes = ws_layout(&sd, nq, R, k, LMI_Q_F16).total;
-        w.region_s = take(w.region_s_bytes);
-    }
-    w.total = off;
-    return w;
-}
-}  // namespace
-
-size_t x_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k) { return x_ws(idx, nq, R, k).total; }
-size_t x_nfailed_offset(const lmi_index_desc* idx, int nq, int R, int k) { return x_ws(idx, nq, R, k).nfailed; }
-
-// The split mode: see lmi_index_desc.corpus32 (include/lmi_hip.h).  out_d is
-// float (out_f64 = 0) or double [nq*R][k]; qmode is ignored (the queries are
-// rounded here whatever their class).
-int bucket_topk_x(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq, const double* q64,
-                  int32_t ldq64, const int32_t* classes, int32_t R, int32_t k, void* out_d, int out_f64,
-                  int32_t* out_pos, int32_t* status, void* workspace, size_t ws_bytes, hipStream_t s,
-                  int phases) {
-    LMI_CHECK_ARG(idx != nullptr, "null index");
-    LMI_CHECK_ARG(idx->corpus32 != nullptr && idx->dtype == LMI_F16 && idx->d_pad == v2::D,
-                  "split mode needs corpus32, an fp16 scan corpus and d_pad %d", v2::D);
-    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "split mode: k=%d outside [1, %d]", k, LMI_MAX_K);
-    LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "bad nq/R");
-    if (nq == 0) return LMI_OK;
-    LMI_CHECK_ARG((q || q64) && classes && out_d && out_pos && status && workspace, "null pointer");
-    LMI_CHECK_ARG(q64 ? ldq64 >= idx->d : ldq >= idx->d, "ldq < d");
-    if (phases != kPhaseAll && !x_sample(k)) {
-        set_error("split mode: phase flags need k <= 10 (the sample's bound)");
-        return LMI_E_UNSUPPORTED;
-    }
-    const XWs w = x_ws(idx, nq, R, k);
-    if (ws_bytes < w.total) {
-        set_error("workspace %zu B < required %zu B", ws_bytes, w.total);
-        return LMI_E_WORKSPACE;
-    }
-    const int P = nq * R;
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    float* qr = (float*)(ws + w.qr);
-    float* ld = (float*)(ws + w.ld);
-    int32_t* lpos = (int32_t*)(ws + w.lpos);
-    auto* bound = (uint32_t*)(ws + w.bound);
-    auto* ccount = (uint32_t*)(ws + w.ccount);
-    auto* cand = (uint64_t*)(ws + w.cand);
-    unsigned char* region = ws + w.region;
-    const double two_eps = 2.0 * split_eps(idx->d_pad);
-    const bool sampled = x_sampled(k);
-    int32_t* fix = (int32_t*)(ws + w.fix);
-    int rc;
-    WideScan m2{2, bound, cand, ccount, w.cap, nullptr, 0, nullptr, nullptr};
-    int32_t* srow = (int32_t*)(ws + w.srow);
-    auto* off2b = (int64_t*)(ws + w.off2b);
-    const lmi_index_desc cd = x_collect_desc(idx, off2b, (int32_t*)(ws + w.cf2b));
-    if (x_sample(k)) {
-        // (PLAN: the rounded queries and both scans' plans; SCAN: the sample
-        // scan and its merge, the bound, the collect scan; MERGE: step 3)
-        auto* off2 = (int64_t*)(ws + w.off2);
-        auto* cf2 = (int32_t*)(ws + w.cf2);
-        auto* classes2 = (int32_t*)(ws + w.classes2);
-        const lmi_index_desc sd = x_sample_desc(idx, off2, cf2);
-        unsigned char* region_s = ws + w.region_s;
-        auto* classes2b = (int32_t*)(ws + w.classes2b);
-        // (the collect skips the samples it can: their candidates are the
-        // sample scan's lists, appended by set_bound_kernel)
-        m2.app_d = ld;
-        m2.app_row = srow;
-        m2.app_k = k;
-        if (phases & kPhasePlan) {
-            hipLaunchKernelGGL(x_round_queries_kernel, dim3((nq + kThreads / 64 - 1) / (kThreads / 64)),
-                               dim3(kThreads), 0, s, q, ldq, q64, ldq64, nq, idx->d, idx->d_pad, qr);
-            LMI_LAUNCH_CHECK("x_round_queries_kernel");
-            LMI_TRY(fill_u32(ws + w.nfailed, 0u, 32, s));
-            hipLaunchKernelGGL(x_sample_desc_kernel, dim3((unsigned)std::min(1024, (P + 63) / 64)), dim3(64), 0, s,
-                               idx->bucket_off, idx->n_buckets, (int64_t)idx->chunk_rows, classes, P, off2, cf2,
-                               classes2, off2b, (int32_t*)(ws + w.cf2b), classes2b,
-                               std::max(0, env_config().x_skip));
-            LMI_LAUNCH_CHECK("x_sample_desc_kernel");
-            rc = bucket_topk_impl(&sd, qr, nq, idx->d_pad, classes2, R, k, LMI_Q_F16, ld, lpos, srow, status,
-                                  region_s, w.region_s_bytes, s, nullptr, 0, true, false, 0.0f, kPhasePlan);
-            if (rc != LMI_OK) return rc;
-            rc = bucket_topk_impl(&cd, qr, nq, idx->d_pad, classes2b, R, 10, LMI_Q_F16, ld, lpos, nullptr, status,
-                                  region, w.region_bytes, s, nullptr, 0, false, false, 0.0f, kPhasePlan, &m2);
-            if (rc != LMI_OK) return rc;
-        }
-        if (phases & kPhaseScan) {
-            // 1. the k-th of every pair's bucket sample (its first chunk_rows
-            //    rows): the product scan over the 2C-bucket sample descriptor,
-            //    then that k-th + 2 eps as the collect bound
-            rc = bucket_topk_impl(&sd, qr, nq, idx->d_pad, classes2, R, k, LMI_Q_F16, ld, lpos, srow, status,
-                                  region_s, w.region_s_bytes, s, nullptr, 0, true, false, 0.0f,
-                                  kPhaseScan | kPhaseMerge);
-            if (rc != LMI_OK) return rc;
-            hipLaunchKernelGGL(x_bound_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (int64_t)P, k, ld, two_eps,
-                               bound);
-            LMI_LAUNCH_CHECK("x_bound_kernel");
-            // 2. every row under the bound (the collect scan, as the wide path's,
-            //    over the rest of the buckets whose sample it skips)
-            rc = bucket_topk_impl(&cd, qr, nq, idx->d_pad, classes2b, R, 10, LMI_Q_F16, ld, lpos, nullptr, status,
-                                  region, w.region_bytes, s, nullptr, 0, false, false, 0.0f, kPhaseScan, &m2);
-            if (rc != LMI_OK) return rc;
-        }
-        if (!(phases & kPhaseMerge)) return LMI_OK;
-    } else {
-    hipLaunchKernelGGL(x_round_queries_kernel, dim3((nq + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads),
-                       0, s, q, ldq, q64, ldq64, nq, idx->d, idx->d_pad, qr);
-    LMI_LAUNCH_CHECK("x_round_queries_kernel");
-    LMI_TRY(fill_u32(ws + w.nfailed, 0u, 32, s));
-    if (sampled) {
-        // 1. a bound per pair from a sample: the wide path's chunk-list scan
-        //    (two lists per bucket, each scanning the first quarter of its
-        //    rows, every list its part's own top-15), the 15th smallest entry
-        //    (>= the pair's 15th >= its k-th), + 2 eps
-        hipLaunchKernelGGL(wide_init_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (int64_t)P, 0,
-                           nullptr, nullptr, nullptr, bound, fix);
-        LMI_LAUNCH_CHECK("wide_init_kernel");
-        auto* sub_first = (int32_t*)(ws + w.sub_first);
-        auto* sub_rows = (int32_t*)(ws + w.sub_rows);
-        auto* sub_take = (int32_t*)(ws + w.sub_take);
-        hipLaunchKernelGGL(bound_lists_kernel, dim3(1), dim3(256), 0, s, idx->bucket_off, idx->n_buckets, kXLists,
-                           sub_first, sub_rows, sub_take);
-        LMI_LAUNCH_CHECK("bound_lists_kernel");
-        const lmi_index_desc bd = bound_desc(idx, kXLists, sub_first);
-        auto* bins = (uint32_t*)(ws + w.bins);
-        LMI_TRY(fill_u32(bins, 0xffffffffu, (size_t)P, s));
-        const WideScan m1{1, nullptr, nullptr, nullptr, 0, bins, 1, sub_rows, sub_take};
-        rc = bucket_topk_impl(&bd, qr, nq, idx->d_pad, classes, R, 15, LMI_Q_F16, ld, lpos, nullptr, status, region,
-                              w.region_bytes, s, nullptr, 0, false, false, 0.0f, kPhasePlan | kPhaseScan, &m1);
-        if (rc != LMI_OK) return rc;
-        const WsLayout lb = ws_layout(&bd, nq, R, 15, LMI_Q_F16);
-        hipLaunchKernelGGL(kth_bound_kernel, dim3((unsigned)P), dim3(64), 0, s,
-                           (const uint64_t*)(region + lb.partial), lb.split_s * bd.max_chunks, lb.split_s,
-                           (const int32_t*)(region + lb.pair_q), (const int32_t*)(region + lb.pair_bucket), sub_first,
-                           (const uint32_t*)(region + lb.split_mask), P, 15, idx->bucket_off, w.cap, bound, fix);
-        LMI_LAUNCH_CHECK("kth_bound_kernel");
-        hipLaunchKernelGGL(x_margin_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (int64_t)P, two_eps, bound);
-        LMI_LAUNCH_CHECK("x_margin_kernel");
-    } else {
-        // 1. the fp16 scan on the rounded vectors: every pair's approximate k-th
-        rc = bucket_topk_impl(idx, qr, nq, idx->d_pad, classes, R, k, LMI_Q_F16, ld, lpos, nullptr, status,
-                              region, w.region_bytes, s);
-        if (rc != LMI_OK) return rc;
-        hipLaunchKernelGGL(x_bound_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (int64_t)P, k, ld, two_eps,
-                           bound);
-        LMI_LAUNCH_CHECK("x_bound_kernel");
-    }
-    // 2. every row under the bound (the collect scan, as the wide path's)
-    rc = bucket_topk_impl(idx, qr, nq, idx->d_pad, classes, R, 10, LMI_Q_F16, ld, lpos, nullptr, status, region,
-                          w.region_bytes, s, nullptr, 0, false, false, 0.0f, kPhasePlan | kPhaseScan, &m2);
-    if (rc != LMI_OK) return rc;
-    }
-    // 3. the candidates' exact distances, sorted; overflowed pairs whole
-    const WsLayout l = ws_layout(x_sample(k) ? &cd : idx, nq, R, 10, LMI_Q_F16);
-    XArgs a{};
-    a.rows32 = idx->corpus32;
-    a.rows32n = idx->corpus32n;
-    a.rows64 = out_f64 ? idx->corpus64 : nullptr;
-    a.d = idx->d;
-    a.d_pad = idx->d_pad;
-    a.gpos = idx->gpos;
-    a.bucket_off = idx->bucket_off;
-    a.n_rows = idx->n_rows;
-    a.q = q;
-    a.ldq = ldq;
-    a.q64 = out_f64 ? q64 : nullptr;
-    a.ldq64 = ldq64;
-    if (!a.q64 && !q) {
-        set_error("split mode: float32 output needs the float32 queries");
-        return LMI_E_INVALID;
-    }
-    a.classes = classes;
-    a.nq = nq;
-    a.R = R;
-    a.k = k;
-    a.pair_q = (const int32_t*)(region + l.pair_q);
-    a.pair_bucket = (const int32_t*)(region + l.pair_bucket);
-    a.cand = cand;
-    a.ccount = ccount;
-    a.cap = w.cap;
-    a.out_d = out_d;
-    a.out_f64 = out_f64;
-    a.out_pos = out_pos;
-    a.failed = (int32_t*)(ws + w.failed);
-    a.n_failed = (int32_t*)(ws + w.nfailed);
-    a.wgl = sampled ? (int32_t*)(ws + w.wgl) : nullptr;  // (two_eps > 0: the wave kernel runs)
-    a.n_wgl = (int32_t*)(ws + w.nfailed) + 16;
-    a.status = status;
-    a.two_eps = sampled ? two_eps : 0.0;
-    a.fix = sampled && !x_sample(k) ? fix : nullptr;
-    // (ABI 10: the float32 output in the reference's own float32 order)
-    a.qn32 = (!out_f64 && q) ? (const float*)(ws + w.qn32) : nullptr;
-    a.grp = (const int32_t*)(ws + w.grp);
-    a.nrows_c = idx->bucket_rows;
-    a.C = idx->n_buckets;
-    a.tailq = (const uint8_t*)(ws + w.tailq);
-    a.goff = (const int64_t*)(ws + w.goff);
-    a.plan_counts = (const int32_t*)(region + l.counts);
-    a.plan_cm = x_sample(k) ? 2 : 1;
-    if (x_sample(k)) {
-        a.soff = off2b;
-        a.skth = ld;
-        a.sfailed = (int32_t*)(ws + w.sfl);
-        a.n_sfailed = (int32_t*)(ws + w.nfailed) + 8;
-        a.spd = (double*)(ws + w.spd);
-        a.spg = (int32_t*)(ws + w.spg);
-    }
-    // (pairs whose class is out of range keep the prefill of step 1's prep:
-    // the outputs are prefilled here, by pair id, in step 3's own buffers)
-    hipLaunchKernelGGL(x_prefill_kernel, dim3((unsigned)(((int64_t)P * k + 255) / 256)), dim3(256), 0, s,
-                       (int64_t)P * k, out_d, out_f64, out_pos);
-    LMI_LAUNCH_CHECK("x_prefill_kernel");
-    return launch_x_refine(a, P, s);
-}
-}  // namespace lmi
-
-#ifdef LMI_DIAG
-// Diagnostic (the `make ablation` library only): lower every pair's global
-// bound before the SCAN phase, e.g. to the final k-th distance of the
-// all-rank lists (tools/bound_study.py: how much of a stripe's scan the
-// per-rank bound costs).  Call after the PLAN phase of lmi_bucket_topk with
-// the same arguments; seed_ord[pair id] is a distance ordinal (f2ord), the
-// bound keeps every row at or under it (ties survive).
-namespace {
-__global__ __launch_bounds__(256) void debug_seed_bounds_kernel(const int32_t* __restrict__ pair_q, int32_t P,
-                                                                const uint32_t* __restrict__ seed_ord,
-                                                                unsigned long long* __restrict__ thr_g) {
-    const int pp = blockIdx.x * 256 + threadIdx.x;
-    if (pp >= P) return;
-    const int p = pair_q[pp];
-    if (p < 0 || p >= P) return;
-    const unsigned long long v = ((unsigned long long)seed_ord[p] << 32) | 0xffffffffull;
-    if (v < thr_g[pp]) thr_g[pp] = v;
-}
-}  // namespace
-
-extern "C" int lmi_debug_seed_bounds(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
-                                     int32_t qmode, const uint32_t* seed_ord, void* workspace,
-                                     void* stream) {
-    using namespace lmi;
-    qmode &= ~LMI_Q_SEED_ROUND0;
-    take_phases(qmode);
-    const WsLayout w = ws_layout(idx, nq, R, k, qmode);
-    if (!w.use_v3) {
-        set_error("seeded bounds need scan v3");
-        return LMI_E_UNSUPPORTED;
-    }
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    const int P = nq * R;
-    hipLaunchKernelGGL(debug_seed_bounds_kernel, dim3((P + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), (const int32_t*)(ws + w.pair_q), P, seed_ord,
-                       (unsigned long long*)(ws + w.thr_g));
-    LMI_LAUNCH_CHECK("debug_seed_bounds_kernel");
-    return LMI_OK;
-}
-#endif
-
-namespace lmi {
-// k > 16: ceil(k / kp) scan passes of kp-entry lists (kp = 15 on scan v3, else
-// 16), each keeping the next kp entries of the (distance, position) order
-// after the previous pass's last key.  Lists of ldo = passes * kp entries.
-int passes_of(const lmi_index_desc* idx, int qmode, int k, int* kp_out) {
-    const int kp = pick_kl(idx, qmode, 15) == 15 ? 15 : 16;
-    if (kp_out) *kp_out = kp;
-    return (k + kp - 1) / kp;
-}
-
-size_t passes_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k, int qmode) {
-    int kp;
-    passes_of(idx, qmode, k, &kp);
-    const size_t P = (size_t)nq * R;
-    return align_up(P * 8, 256) + scan_workspace_bytes(idx, nq, R, kp, qmode, true);
-}
-
-int bucket_topk_passes(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq,
-                       const int32_t* classes, int32_t R, int32_t k, int32_t qmode, float* out_d,
-                       int32_t* out_pos, int32_t* out_row, int32_t ldo, int32_t* status,
-                       void* workspace, size_t ws_bytes, hipStream_t s) {
-    int kp;
-    const int np = passes_of(idx, qmode, k, &kp);
-    if (ldo < np * kp) {
-        set_error("pass lists of %d entries < %d passes x %d", ldo, np, kp);
-        return LMI_E_INVALID;
-    }
-    const size_t P = (size_t)nq * R;
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    auto* lo = reinterpret_cast<unsigned long long*>(ws);
-    const size_t lo_bytes = align_up(P * 8, 256);
-    if (ws_bytes < lo_bytes) {
-        set_error("workspace %zu B too small", ws_bytes);
-        return LMI_E_WORKSPACE;
-    }
-    LMI_TRY(fill_u32(lo, 0u, P * 2, s));
-    for (int j = 0; j < np; ++j) {
-        const int rc = bucket_topk_impl(idx, q, nq, ldq, classes, R, kp, qmode, out_d + (size_t)j * kp,
-                                        out_pos + (size_t)j * kp, out_row ? out_row + (size_t)j * kp : nullptr,
-                                        status, ws + lo_bytes, ws_bytes - lo_bytes, s, lo, ldo, j == 0);
-        if (rc != LMI_OK) return rc;
-        if (j + 1 < np) {
-            hipLaunchKernelGGL(next_lo_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, out_d,
-                               out_pos, (int32_t)P, ldo, (j + 1) * kp - 1, lo);
-            LMI_LAUNCH_CHECK("next_lo_kernel");
-        }
-    }
-    return LMI_OK;
-}
-
-namespace {
-struct WideWs {
-    bool on;       // the bound + collect path (else bucket_topk_passes alone)
-    int kw, cap;   // list entries produced (passes * kp); candidate slots per pair
-    int lists;     // bound-scan lists per bucket (at most; bound_lists_kernel)
-    int nbins;     // the bound scan's pruning bins per pair (Scan2Args::bins)
-    size_t bound, fix, cls, ccount, cand, fd, fpos, frow, sub_first, sub_rows, sub_take, bins, region,
-        region_bytes, total;
-};
-
-// The bound scan's index: the same rows and buckets, each bucket cut into at
-// most `lists` lists (bound_lists_kernel; their rows per bucket in sub_rows),
-// no chunk centroids (the nearest-chunk-first plan's units are the index's
-// chunks).  Host-side values only: the workspace size must not read the device.
-lmi_index_desc bound_desc(const lmi_index_desc* idx, int lists, const int32_t* sub_first) {
-    lmi_index_desc b = *idx;
-    b.max_chunks = lists;
-    b.n_chunks = idx->n_buckets * lists;
-    b.chunk_first = sub_first;
-    b.chunk_centroid = nullptr;
-    return b;
-}
-
-WideWs wide_ws(const lmi_index_desc* idx, int nq, int R, int k, int qmode, int ldo) {
-    WideWs w{};
-    int kp;
-    const int np = passes_of(idx, qmode, k, &kp);
-    w.kw = np * kp;
-    w.on = v3_capable(idx, qmode) && kp == 15 && !env_config().wide_passes;
-    const size_t P = (size_t)nq * R;
-    if (!w.on) {
-        w.region_bytes = w.total = passes_ws_bytes(idx, nq, R, k, qmode);
-        return w;
-    }
-    // Bound scan: 2 kw / 15 lists per bucket, so a pair's lists hold 2 kw
-    // entries, each the top-15 of the first quarter of its list's rows: their
-    // kw-th smallest is about the pair's 4 kw-th distance, and the collect scan
-    // finds about 4 kw rows within it; 8 kw (+ 64) slots before the fix-up
-    // passes take over.  Buckets of fewer lists' entries than kw but no more
-    // rows than the slots are collected whole.
-    w.lists = 2 * np;
-    w.nbins = np;  // (np * 15 = kw)
-    int cap = 256;
-    while (cap < 8 * w.kw + 64) cap <<= 1;
-    w.cap = std::min(cap, 8192);
-    // (candidate slots past 8 GiB -- huge batches at large k -- : the passes,
-    // whose lists are 8x smaller)
-    if (P * (size_t)w.cap * 8 > (size_t(8) << 30)) {
-        w.on = false;
-        w.region_bytes = w.total = passes_ws_bytes(idx, nq, R, k, qmode);
-        return w;
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    w.bound = take(P * 4);
-    w.fix = take(P * 4);
-    w.cls = take(P * 4);
-    w.ccount = take(P * 4);
-    w.cand = take(P * (size_t)w.cap * 8);
-    w.fd = take(P * (size_t)ldo * 4);
-    w.fpos = take(P * (size_t)ldo * 4);
-    w.frow = take(P * (size_t)ldo * 4);
-    w.sub_first = take(((size_t)idx->n_buckets + 1) * 4);
-    w.sub_rows = take((size_t)idx->n_buckets * 4);
-    w.sub_take = take((size_t)idx->n_buckets * 4);
-    w.bins = take(P * (size_t)w.nbins * 4);
-    const lmi_index_desc bd = bound_desc(idx, w.lists, nullptr);
-    w.region_bytes = std::max({scan_workspace_bytes(&bd, nq, R, 15, qmode),
-                               scan_workspace_bytes(idx, nq, R, 10, qmode),
-                               passes_ws_bytes(idx, nq, R, k, qmode)});
-    w.region = take(w.region_bytes);
-    w.total = off;
-    return w;
-}
-}  // namespace
-
-size_t wide_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k, int qmode, int ldo) {
-    return wide_ws(idx, nq, R, k, qmode, ldo).total;
-}
-
-int bucket_topk_wide(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq,
-                     const int32_t* classes, int32_t R, int32_t k, int32_t qmode, float* out_d,
-                     int32_t* out_pos, int32_t* out_row, int32_t ldo, int32_t* status,
-                     void* workspace, size_t ws_bytes, hipStream_t s) {
-    const WideWs w = wide_ws(idx, nq, R, k, qmode, ldo);
-    if (!w.on || idx->n_rows == 0)
-        return bucket_topk_passes(idx, q, nq, ldq, classes, R, k, qmode, out_d, out_pos, out_row, ldo,
-                                  status, workspace, ws_bytes, s);
-    if (ldo < w.kw) {
-        set_error("lists of %d entries < %d", ldo, w.kw);
-        return LMI_E_INVALID;
-    }
-    if (ws_bytes < w.total) {
-        set_error("workspace %zu B < required %zu B", ws_bytes, w.total);
-        return LMI_E_WORKSPACE;
-    }
-    if (nq == 0) return LMI_OK;
-    const int P = nq * R;
-    auto* ws = reinterpret_cast<unsigned char*>(workspace);
-    auto* bound = (uint32_t*)(ws + w.bound);
-    auto* fix = (int32_t*)(ws + w.fix);
-    auto* ccount = (uint32_t*)(ws + w.ccount);
-    auto* cand = (uint64_t*)(ws + w.cand);
-    auto* fd = (float*)(ws + w.fd);
-    auto* fpos = (int32_t*)(ws + w.fpos);
-    auto* frow = out_row ? (int32_t*)(ws + w.frow) : nullptr;
-    unsigned char* region = ws + w.region;
-    const int64_t PL = (int64_t)P * ldo;
-    hipLaunchKernelGGL(wide_init_kernel, dim3((unsigned)((PL + 255) / 256)), dim3(256), 0, s, (int64_t)P,
-                       ldo, out_d, out_pos, out_row, bound, fix);
-    LMI_LAUNCH_CHECK("wide_init_kernel");
-    const int plan_scan = kPhasePlan | kPhaseScan;
-    // 1. every (pair, bound-pass chunk part)'s own top-15 -> each pair's bound
-    auto* sub_first = (int32_t*)(ws + w.sub_first);
-    auto* sub_rows = (int32_t*)(ws + w.sub_rows);
-    auto* sub_take = (int32_t*)(ws + w.sub_take);
-    hipLaunchKernelGGL(bound_lists_kernel, dim3(1), dim3(256), 0, s, idx->bucket_off, idx->n_buckets,
-                       w.lists, sub_first, sub_rows, sub_take);
-    LMI_LAUNCH_CHECK("bound_lists_kernel");
-    const lmi_index_desc bd = bound_desc(idx, w.lists, sub_first);
-    auto* bins = (uint32_t*)(ws + w.bins);
-    LMI_TRY(fill_u32(bins, 0xffffffffu, (size_t)P * w.nbins, s));
-    const WideScan m1{1, nullptr, nullptr, nullptr, 0, bins, w.nbins, sub_rows, sub_take};
-    int rc = bucket_topk_impl(&bd, q, nq, ldq, classes, R, 15, qmode, fd, fpos, nullptr, status, region,
-                              w.region_bytes, s, nullptr, 0, false, false, 0.0f, plan_scan, &m1);
-    if (rc != LMI_OK) return rc;
-    {
-        const WsLayout l = ws_layout(&bd, nq, R, 15, qmode);
-        hipLaunchKernelGGL(kth_bound_kernel, dim3((unsigned)P), dim3(64), 0, s,
-                           (const uint64_t*)(region + l.partial), l.split_s * bd.max_chunks, l.split_s,
-                           (const int32_t*)(region + l.pair_q), (const int32_t*)(region + l.pair_bucket),
-                           sub_first, (const uint32_t*)(region + l.split_mask), P, w.kw, idx->bucket_off,
-                           w.cap, bound, fix);
-        LMI_LAUNCH_CHECK("kth_bound_kernel");
-    }
-    // 2. every row within the bound -> sorted, the first kw
-    const WideScan m2{2, bound, cand, ccount, w.cap, nullptr, 0, nullptr, nullptr};
-    rc = bucket_topk_impl(idx, q, nq, ldq, classes, R, 10, qmode, fd, fpos, nullptr, status, region,
-                          w.region_bytes, s, nullptr, 0, false, false, 0.0f, plan_scan, &m2);
-    if (rc != LMI_OK) return rc;
-    {
-        const WsLayout l = ws_layout(idx, nq, R, 10, qmode);
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute((const void*)collect_select_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8);
-        });
-        LMI_HIP_TRY(attr_err);
-        hipLaunchKernelGGL(collect_select_kernel, dim3((unsigned)P), dim3(256), (size_t)w.cap * 8, s, cand,
-                           ccount, w.cap, (const int32_t*)(region + l.pair_q),
-                           (const int32_t*)(region + l.pair_bucket), idx->gpos, P, w.kw, ldo, bound, fix,
-                           out_d, out_pos, out_row);
-        LMI_LAUNCH_CHECK("collect_select_kernel");
-    }
-    // 3. the pairs without a bound or with too many candidates: the passes,
-    //    over their buckets only (every other pair's class is -1)
-    if (env_config().wide_no_fixup) return LMI_OK;
-    int32_t* cls = (int32_t*)(ws + w.cls);
-    hipLaunchKernelGGL(fix_classes_kernel, dim3((P + 255) / 256), dim3(256), 0, s, classes, fix, P, cls);
-    LMI_LAUNCH_CHECK("fix_classes_kernel");
-    rc = bucket_topk_passes(idx, q, nq, ldq, cls, R, k, qmode, fd, fpos, frow, ldo, status, region,
-                            w.region_bytes, s);
-    if (rc != LMI_OK) return rc;
-    hipLaunchKernelGGL(fix_combine_kernel, dim3((unsigned)((PL + 255) / 256)), dim3(256), 0, s, fix,
-                       (int64_t)P, ldo, fd, fpos, frow, out_d, out_pos, out_row);
-    LMI_LAUNCH_CHECK("fix_combine_kernel");
-    return LMI_OK;
-}
-}  // namespace lmi
-
-
 extern "C" int32_t lmi_scan_set_workgroups(int32_t wgs) {
     const int prev = lmi::t_scan_wgs;
     lmi::t_scan_wgs = wgs > 0 ? wgs : 0;
     return prev;
 }
-
-extern "C" double lmi_split_eps(int32_t d_pad) { return d_pad > 0 ? lmi::split_eps(d_pad) : 0.0; }
 
 extern "C" int lmi_timing_enable(int32_t on) {
     lmi::Timing& t = lmi::timing();

@@ -1,7 +1,10 @@
 // Internal declarations shared by the K2 scan translation units
-// (lmi_scan.hip: prep / plan / scan v3 / chunk merge / host entry points;
-// lmi_scan_v12.hip: the round-1 and round-2 scan kernels, kept as fallbacks
-// for shapes scan v3 does not take and as A/B baselines).  Not an ABI.
+// (lmi_scan.hip: prep / plan / scan v3 / chunk merge / the scan's plan and
+// its one host entry, bucket_topk_impl; lmi_scan_wide.hip: k > 16;
+// lmi_scan_split.hip: the split mode's driver; lmi_scan_v12.hip: the round-1
+// and round-2 scan kernels, kept as fallbacks for shapes scan v3 does not take
+// and as A/B baselines) and with lmi_refine.hip, their one outside caller.
+// Not an ABI.
 #pragma once
 #include "lmi_common.hpp"
 
@@ -198,5 +201,228 @@ template <int KL, bool F16MATH, typename TC, bool LO = false>
 int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s);
 template <int KL>
 int launch_scan2(const Scan2Args& b, hipStream_t s);
+
+// ---- the scan's plan (lmi_scan.hip) -----------------------------------------
+// Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the
+// kernel family, the list length, the tile width, the tail split's parts and
+// where each array lies in the caller's workspace.  bucket_topk_impl reads it;
+// so do the workspace sizes and the drivers that look into a scan's region
+// afterwards (the grouped pairs, the partial lists).  lo: a lower-bound pass.
+// General: scan_kernel; Ring4: scan2_kernel (4 waves); Ring8: scan3_kernel
+enum class ScanKernel { General, Ring4, Ring8 };
+struct ScanPlan {
+    ScanKernel family;
+    // list length of the scan: 10 (k <= 10), 15 (k <= 15 on the 8-wave ring:
+    // the float64 mode's 10 + 5 guard entries), else 16
+    int32_t kl, qb;  // (qb: queries per tile)
+    // fp16 corpus and fp16-exact queries; the nearest-chunk-first plan (8-wave
+    // ring, chunk centroids)
+    bool f16math, nearest_first;
+    int32_t split_s;      // row parts of a tail-split chunk (1: the tail split is off)
+    int32_t list_stride;  // partial-list slots per pair: split_s * max(max_chunks, 1)
+    int32_t max_tiles;
+    // offsets into the workspace (pair_pos, seed_pos: LMI_Q_SEED_ROUND0, the
+    // grouped position of every pair id and of every grouped pair's (q, 0))
+    size_t qbuf, invq, counts, pair_q, pair_bucket, tiles, ntiles, work, partial, ext_off,
+        split_mask, thr_g, pref, pref_tmp, pref_tmp2, n_seed, pair_pos, seed_pos, total;
+};
+ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false);
+// the 8-wave ring serves this index and query class (the float64 mode's band lists)
+bool band_capable(const lmi_index_desc* idx, int qmode);
+size_t scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
+                            int32_t qmode, bool lo = false);
+
+// phases of bucket_topk_impl (LMI_Q_PHASE_* of the ABI, shifted to bits 0..2)
+constexpr int kPhasePlan = 1, kPhaseScan = 2, kPhaseMerge = 4, kPhaseAll = 7;
+// LMI_Q_PHASE_* bits of a qmode -> kPhase* (none set = all); strips them from qmode
+inline int take_phases(int32_t& qmode) {
+    const int p = (qmode >> 9) & 7;
+    qmode &= ~(7 << 9);
+    return p ? p : kPhaseAll;
+}
+// The scans of the wide path (k > 16, bucket_topk_wide): mode 1 writes every
+// (pair, chunk part) list as that part's own top-15 (no global bound); mode 2
+// collects every row within the pair's bound bound_ord[pair id] (a distance
+// ordinal; 0 = none) into cand[grouped pair * cap + i] (ccount: slots taken).
+struct WideScan {
+    int mode;
+    const uint32_t* bound_ord;
+    uint64_t* cand;
+    uint32_t* ccount;
+    int32_t cap;
+    uint32_t* bins;  // mode 1: [P][nbins], all ones at the start (Scan2Args::bins)
+    int32_t nbins;
+    const int32_t* sub_rows;  // mode 1: Scan2Args::sub_rows / sub_take
+    const int32_t* sub_take;
+    // mode 2: a pair whose (odd) bucket b has rows skipped in front of it
+    // (bucket b - 1 of the descriptor not empty: the split mode's sample,
+    // x_collect_desc) starts with its app_k (distance, row) entries app_d /
+    // app_row [pair id][app_k] as candidates (-1 rows skipped); null: none
+    const float* app_d;
+    const int32_t* app_row;
+    int32_t app_k;
+};
+// One call of K2 up to the merged per-pair lists (bucket_topk_impl, lmi_scan.hip):
+// lmi_bucket_topk's arguments, a third output (out_row: the shard-local row of
+// every entry, -1 = empty; nullable), and the options below.
+struct ScanCall {
+    const lmi_index_desc* idx;
+    const float* q;
+    int32_t nq, ldq;
+    const int32_t* classes;
+    int32_t R, k, qmode;
+    float* out_d;
+    int32_t *out_pos, *out_row, *status;
+    void* workspace;
+    size_t ws_bytes;
+    hipStream_t stream;
+    // device [nq*R] or null: keep only objects after the (distance, global
+    // position) key of their pair (the passes of k > 16)
+    const unsigned long long* lo_g = nullptr;
+    int32_t ldo = 0;      // entries per pair in the outputs (0: k)
+    bool prefill = true;  // write (+inf, -1) over all R*ldo entries first (the first pass)
+    // LMI_Q_SEED_ROUND0: pairs r >= 1 start from the bound of pair (q, 0),
+    // + seed_margin in distance
+    bool seed_r0 = false;
+    float seed_margin = 0.0f;
+    int phases = kPhaseAll;
+    const WideScan* wide = nullptr;
+    // [nq*R] float or null (k <= 15 on the 8-wave ring, kl = 15): the float64
+    // mode's band lists -- the scan's filter widened by seed_margin (2 eps),
+    // every pair's first 15 entries, and out_bound[pair] a distance such that
+    // each row of the shard the list does not hold failed the widened filter
+    // or has d32 >= it (chunk_merge_band_kernel)
+    float* out_bound = nullptr;
+    // with out_bound, or null: each pair's first kth_k list distances also
+    // written to kth_out[pair * kth_k] (the float64 global band's kth_send, ABI 10)
+    float* kth_out = nullptr;
+    int32_t kth_k = 0;
+    // scan_plan() of this call where the caller holds it (it reads the scan's
+    // region afterwards); null: built here
+    const ScanPlan* plan = nullptr;
+};
+int bucket_topk_impl(const ScanCall& c);
+
+// ---- k > LMI_MAX_K (lmi_scan_wide.hip) ---------------------------------------
+// passes_of() passes of kp-entry lists; bucket_topk_passes fills [nq*R][ldo]
+// lists (ldo >= passes * kp) with (d32, global position[, local row]).
+int passes_of(const lmi_index_desc* idx, int qmode, int k, int* kp_out);
+size_t passes_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k, int qmode);
+int bucket_topk_passes(const ScanCall& c);
+// The same lists as bucket_topk_passes from two scans (the 8-wave ring):
+// chunk lists -> per-pair bound (the kw-th smallest of the pair's chunk-list
+// distances, kw = passes * kp) -> collect the rows within it -> sort; pairs
+// without a bound (too few chunk-list entries) or whose candidates overflow
+// go through bucket_topk_passes restricted to them.  Off the 8-wave ring (or
+// under LMI_WIDE_PASSES) it is bucket_topk_passes.
+size_t wide_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k, int qmode, int ldo);
+int bucket_topk_wide(const ScanCall& c);
+// lmi_bucket_topk at k > LMI_MAX_K: bucket_topk_wide into lists at the head of
+// the workspace, their first k to the caller's [nq*R][k] outputs
+int bucket_topk_wide_k(const ScanCall& c);
+// The sampled bound of the wide path and of the split mode: every bucket cut
+// into at most `lists` lists (bound_lists_kernel -> sub_first / sub_rows /
+// sub_take), each list's first part scanned in MODE 1 with nbins pruning bins
+// per pair, and bound[pair id] = the kw-th smallest distance ordinal of the
+// pair's lists (kth_bound_kernel; no bound: all ones where the bucket fits cap
+// slots, else fix[pair id] = 1).  scan: the call of the MODE 1 scan but for
+// idx, k, prefill, phases and wide; wide_init_kernel pads its outputs
+// [nq*R][pad_ldo] (pad_ldo 0: none) and clears bound and fix.
+struct BoundScan {
+    int lists, nbins, kw, cap;
+    int32_t *sub_first, *sub_rows, *sub_take;
+    uint32_t *bins, *bound;
+    int32_t* fix;
+    float* pad_d;
+    int32_t *pad_pos, *pad_row;
+    int32_t pad_ldo;
+};
+int sampled_bound(const ScanCall& scan, const BoundScan& b);
+// the bound scan's index: idx with every bucket cut into at most `lists` lists
+lmi_index_desc bound_desc(const lmi_index_desc* idx, int lists, const int32_t* sub_first);
+
+// ---- the split mode (lmi_scan_split.hip; ABI 9, idx->corpus32) ---------------
+// Its exact step (lmi_refine.hip): per grouped pair of the collect scan, the
+// exact distances of its candidates, sorted, the first k; overflowed pairs
+// scanned whole.
+struct XArgs {
+    const float* rows32;   // [n_rows][d_pad] the caller's float32 rows
+    const double* rows64;  // [n_rows][d_pad] float64 rows (idx->corpus64) or null
+    int32_t d, d_pad;
+    const int32_t* gpos;
+    const int64_t* bucket_off;
+    int64_t n_rows;
+    const float* q;        // [nq][ldq] float32 queries
+    int32_t ldq;
+    const double* q64;     // float64 queries or null
+    int32_t ldq64;
+    const int32_t* classes;
+    int32_t nq, R, k;
+    const int32_t* pair_q;       // grouped pair -> pair id (the collect scan's plan)
+    const int32_t* pair_bucket;  // grouped pair -> bucket (-1: none)
+    const uint64_t* cand;        // [grouped pair][cap] (ord(d~) << 32 | row)
+    const uint32_t* ccount;
+    int32_t cap;
+    void* out_d;                 // [nq*R][k] float (out_f64 = 0) or double
+    int32_t out_f64;
+    int32_t* out_pos;
+    int32_t* failed;
+    int32_t* n_failed;
+    int32_t* status;
+    // > 0: the candidates are every row under a sampled bound + two_eps; only
+    // those within the k-th smallest d~ + two_eps are re-scored
+    double two_eps;
+    const int32_t* fix;  // [nq*R] pairs without a sampled bound (whole shard), or null
+    // ABI 10, the float32 output only: the reference's float32 operation order
+    // (oracle blas32_*; lmi_index_desc.corpus32): qn32 [nq][d_pad] the queries
+    // normalised as sklearn does in float32 (null: the exact value rounded),
+    // grp [R][C] queries of each (round, bucket) group, nrows_c [C] rows of
+    // each bucket in the whole index (null: this shard's)
+    const float* qn32;
+    const int32_t* grp;
+    const int64_t* nrows_c;
+    int32_t C;
+    // (the small kernel's corner block: tailq[pair] = the query is among the
+    // last M mod 4 of its group; goff [C+1] the buckets' global offsets)
+    const uint8_t* tailq;
+    const int64_t* goff;
+    const int32_t* plan_counts;  // [C] pairs per bucket (the collect scan's plan)
+    // ABI 11: rows32 normalised as sklearn does in float32 (idx->corpus32n) or
+    // null (then normalised per candidate)
+    const float* rows32n;
+    // the grouped pairs x_select_wave_kernel leaves to x_select_kernel (more
+    // candidates, overflowed, unbounded), appended by the wave kernel, and
+    // their count (null: x_select_kernel walks every grouped pair)
+    int32_t* wgl;
+    int32_t* n_wgl;
+    // the collect scan skipped each split bucket's sample rows (x_collect_desc):
+    // soff [2C+1] (bucket c's sample rows [soff[2c], soff[2c+1]), empty where the
+    // bucket was collected whole) and skth [nq*R][k] the sample's own lists (the
+    // pair's k-th at k - 1); a pair whose band reaches its sample's k-th goes to
+    // sfailed (grouped pair ids, count n_sfailed) and x_fallback_kernel scores
+    // its sample rows and its candidates exactly.  null: none skipped.  plan_cm:
+    // plan_counts has plan_cm entries per bucket, the pairs of bucket c at
+    // plan_cm c + plan_cm - 1
+    const int64_t* soff;
+    const float* skth;
+    int32_t* sfailed;
+    int32_t* n_sfailed;
+    double* spd;     // the sliced sfailed pairs' slice lists (x_fallback_slice_kernel)
+    int32_t* spg;
+    int32_t plan_cm;
+};
+// the sliced sample fallback (x_fallback_slice_kernel): the first
+// kXSlicedPairs sfailed pairs, kXSlices slices each (XArgs::spd / spg hold
+// kXSlicedPairs x kXSlices x k entries)
+constexpr int kXSlices = 32;
+constexpr int kXSlicedPairs = 256;
+int launch_x_refine(const XArgs& a, int64_t P, hipStream_t s);
+double split_eps(int d_pad);
+size_t x_ws_bytes(const lmi_index_desc* idx, int nq, int R, int k);
+size_t x_nfailed_offset(const lmi_index_desc* idx, int nq, int R, int k);
+int bucket_topk_x(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq, const double* q64,
+                  int32_t ldq64, const int32_t* classes, int32_t R, int32_t k, void* out_d, int out_f64,
+                  int32_t* out_pos, int32_t* status, void* workspace, size_t ws_bytes, hipStream_t s,
+                  int phases = kPhaseAll);
 
 }  // namespace lmi

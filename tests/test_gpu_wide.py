@@ -1,4 +1,4 @@
-"""k > 16 by bound + collect (csrc/lmi_scan.hip, bucket_topk_wide): a chunk-list
+"""k > 16 by bound + collect (csrc/lmi_scan_wide.hip, bucket_topk_wide): a chunk-list
 scan (every bucket cut into 2 kw / 15 lists, each the top-15 of a sample of its
 rows) gives each pair a bound -- the kw-th smallest of its lists' distances --,
 a collect scan gathers every row within it, a sort keeps the first kw; buckets

@@ -245,7 +245,8 @@ def test_search_path_initialises_workspace_with_kernels():
     ran between replays of two graphs, so the search path's sources initialise
     device memory with fill kernels (lmi::fill_u32), never hipMemsetAsync/hipMemset."""
     csrc = os.path.join(ROOT, "sisap23-laion-challenge-learned-index_amd", "csrc")
-    for name in ("lmi_scan.hip", "lmi_scan_v12.hip", "lmi_refine.hip", "lmi_merge.hip",
+    for name in ("lmi_scan.hip", "lmi_scan_wide.hip", "lmi_scan_split.hip", "lmi_scan_v12.hip",
+                 "lmi_refine.hip", "lmi_merge.hip",
                  "lmi_replay_gpu.hip", "lmi_router.hip", "lmi_abi.cpp"):
         src = open(os.path.join(csrc, name)).read()
         assert not re.search(r"\bhipMemset\w*\s*\(", src), name
