@@ -544,6 +544,46 @@ int lmi_mlp_train_steps(const lmi_mlp_train_desc* desc, const float* x, int64_t 
                         double beta1, double beta2, double eps, float* loss_out, void* workspace,
                         size_t ws_bytes, void* stream);
 
+/* ---- index update (K7): add and remove rows without a rebuild -------------- */
+/* An update of a one-GPU fp16 index writes a new bucket-sorted corpus beside
+ * the old one: in every bucket the surviving rows keep their order and the
+ * bucket's new rows follow in batch order -- the layout a construction from
+ * scratch over the updated row sequence gives (the reference's groupby visit
+ * order over the concatenated frame, LearnedIndex.py:143-145).  The host
+ * prepares the offsets (li.index.BucketLayout.updated); these two calls move
+ * the rows, asynchronously on `stream`, into caller-owned buffers.  Both OR
+ * bits into the device word `status` (zeroed by the caller) and never write
+ * outside dst_corpus [n_new][d_pad] / dst_inv_norm [n_new]: a destination row
+ * outside [0, n_new) is skipped and LMI_STATUS_INTERNAL raised.  Additions:
+ * LMI_ABI_VERSION does not change. */
+#define LMI_STATUS_ROWS_NOT_F16 4 /* lmi_index_ingest_rows: a float32 value is not fp16-exact */
+/* Old row i of bucket c (old_off[c] <= i < old_off[c+1]) goes to
+ *   new_off[c] + (i - old_off[c]) - #{dropped rows of bucket c before i},
+ * its 1/||y|| with it; a dropped row goes nowhere.
+ *   src_corpus / dst_corpus  device fp16 [n][d_pad], 16-byte aligned, distinct
+ *   old_off, new_off         device int64 [n_buckets + 1]; new_off[c] is where
+ *                            bucket c starts in the new corpus
+ *   dropped                  device int64 [n_dropped], ascending, distinct old
+ *                            rows (NULL when n_dropped == 0)
+ *   drop_before              device int64 [n_buckets + 1]: #{dropped < old_off[c]}
+ *                            (NULL when n_dropped == 0)
+ * One read and one write of the surviving rows, 16 bytes per lane. */
+int lmi_index_move_rows(const void* src_corpus, const float* src_inv_norm, int64_t n_old,
+                        int32_t d_pad, const int64_t* old_off, const int64_t* new_off,
+                        int32_t n_buckets, const int64_t* dropped, int64_t n_dropped,
+                        const int64_t* drop_before, void* dst_corpus, float* dst_inv_norm,
+                        int64_t n_new, int32_t* status, void* stream);
+/* Batch row j (device, `dtype` LMI_F16 or LMI_F32, m rows of d values, row
+ * stride ld elements) is stored at row new_dst[j] (device int64 [m]) as fp16
+ * with zeros in columns d..d_pad, and dst_inv_norm[new_dst[j]] = 1/||y|| of
+ * the STORED values: the norm in float64, norms below 10 eps(float32) taken
+ * as 1, one rounding to float32 (li.index._inv_norm).  A float32 value that
+ * does not round-trip through fp16 raises LMI_STATUS_ROWS_NOT_F16 (the
+ * rounded value is stored; the caller discards the buffers). */
+int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m, int64_t ld, int32_t d,
+                          int32_t d_pad, const int64_t* new_dst, void* dst_corpus,
+                          float* dst_inv_norm, int64_t n_new, int32_t* status, void* stream);
+
 /* ---- kernel timing (measurement only) -------------------------------------- */
 /* While enabled, lmi_bucket_topk records a HIP event pair on its stream around
  * its scan kernel (the roofline kernel).  lmi_timing_read waits for the pairs

@@ -375,6 +375,86 @@ class LearnedIndex(Logger):
             return lab
         return col
 
+    # ---- updates (an addition; the reference's index is frozen once built) ----
+    def _updatable_index(self, data_navigation, data_search, pred_categories):
+        """The HBM index of the given objects, for insert / delete (one GPU)."""
+        pg = self._proc_group()
+        if pg is not None and pg[2] > 1:
+            raise ValueError("index update: a striped index (world > 1) cannot be updated in place "
+                             "of a rebuild: stripe boundaries move with the bucket sizes and rows "
+                             "would migrate between ranks")
+        return self._device_index(data_navigation, data_search, pred_categories)
+
+    def _adopt(self, index, data_navigation, data_search, labels):
+        """Leave this object as `attach` would for these objects, over `index`
+        (an updated DeviceIndex): the next search / search_single call that
+        passes them reuses it, without a construction from their rows."""
+        self._index = index
+        self._searcher = None
+        self._cat_written = None
+        self._cache_key = ("updated", id(index))
+        self._trusted = (self._identity(data_navigation, data_search, labels), self._cache_key,
+                         (data_search, labels, data_navigation.index))
+        self._attached_labels = labels
+
+    def insert(self, data_navigation, data_search, pred_categories, new_navigation, new_search):
+        """Add objects to the index without a rebuild: the router labels the
+        new navigation rows (`predict`, as `build` labels the data), the frames
+        and labels are concatenated on the host and the HBM index takes the
+        new rows through DeviceIndex.add (rows move inside HBM; the corpus
+        does not cross PCIe again).  Returns
+
+            (data_navigation2, data_search2, pred_categories2)
+
+        to pass to later search / search_single calls, which reuse the updated
+        index as after `attach` (same contract: do not change them in place).
+        Answers are bitwise those of an index built from the concatenated
+        frames.  New ids (new_navigation.index) that repeat or collide with
+        existing ones raise ValueError."""
+        import pandas as pd
+        assert self.model is not None, 'Model is not trained, call `build` first.'
+        new_ids = np.asarray(new_navigation.index)
+        if np.unique(new_ids).size != new_ids.size:
+            raise ValueError("insert: duplicate ids among the new objects")
+        if np.isin(new_ids, np.asarray(data_navigation.index)).any():
+            raise ValueError("insert: ids of new objects are already in the index")
+        index = self._updatable_index(data_navigation, data_search, pred_categories)
+        nav_old = data_navigation.drop(columns="category", errors="ignore")
+        nav_new = new_navigation.drop(columns="category", errors="ignore")
+        new_labels = self.model.predict(data_X_to_torch(nav_new))
+        ds = _search_frame(new_search)
+        dts = _dtypes(ds)
+        dt = np.float16 if dts == {np.dtype(np.float16)} else \
+            np.float64 if np.dtype(np.float64) in dts else np.float32
+        if hasattr(ds, "index") and not ds.index.equals(new_navigation.index):
+            rows = ds.loc[new_navigation.index].to_numpy(dtype=dt)
+        else:
+            rows = np.asarray(ds, dtype=dt)
+        new_index = index.add(rows, new_labels, ids=new_ids)
+        labels2 = np.concatenate([np.asarray(pred_categories).astype(np.int64), new_labels])
+        nav2 = pd.concat([nav_old, nav_new])
+        nav2["category"] = labels2                     # what search() writes (:67)
+        search2 = pd.concat([data_search, new_search])
+        self._adopt(new_index, nav2, search2, labels2)
+        return nav2, search2, labels2
+
+    def delete(self, data_navigation, data_search, pred_categories, ids):
+        """Remove the objects with the given ids without a rebuild
+        (DeviceIndex.remove); returns the frames and labels without them, as
+        `insert` does.  An unknown id raises KeyError."""
+        index = self._updatable_index(data_navigation, data_search, pred_categories)
+        ids = np.asarray(ids).ravel()
+        new_index = index.remove(ids)
+        keep = ~np.isin(np.asarray(data_navigation.index), ids)
+        nav2 = data_navigation[keep].copy()    # (search() writes its 'category' column)
+        if hasattr(data_search, "index"):
+            search2 = data_search[~np.isin(np.asarray(data_search.index), ids)]
+        else:
+            search2 = np.asarray(data_search)[keep]
+        labels2 = np.asarray(pred_categories).astype(np.int64)[keep]
+        self._adopt(new_index, nav2, search2, labels2)
+        return nav2, search2, labels2
+
     # ---- build (outside the hot path) -------------------------------------
     def build(self, data, n_categories=100, epochs=100, lr=0.1, model_type='MLP',
               train_mode='reference'):

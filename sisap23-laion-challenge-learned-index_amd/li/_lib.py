@@ -27,6 +27,7 @@ LMI_E_WORKSPACE = 1003
 LMI_E_HIP = 1004
 LMI_STATUS_QUERY_NOT_F16 = 1
 LMI_STATUS_INTERNAL = 2
+LMI_STATUS_ROWS_NOT_F16 = 4
 
 LMI_F32 = 0
 LMI_F16 = 1
@@ -84,6 +85,8 @@ EXPORTS = (
     "lmi_kmeans_update",
     "lmi_mlp_train_workspace_bytes",
     "lmi_mlp_train_steps",
+    "lmi_index_move_rows",
+    "lmi_index_ingest_rows",
     "lmi_timing_enable",
     "lmi_timing_read",
     "lmi_last_error",
@@ -203,6 +206,9 @@ _SIGNATURES = {
     "lmi_mlp_train_steps": (C.c_int, [C.POINTER(MlpTrainDesc), _P, _I64, _I32, _P, _P, _I64, _I32, _I64,
                                       _I64, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                       _P, C.c_size_t, _P]),
+    "lmi_index_move_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P,
+                                      _P]),
+    "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "lmi_timing_enable": (C.c_int, [_I32]),
     "lmi_timing_read": (C.c_int32, [_P, _I32]),
     "lmi_last_error": (C.c_char_p, []),

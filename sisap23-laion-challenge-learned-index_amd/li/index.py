@@ -167,6 +167,86 @@ class BucketLayout:
     def bucket_size(self) -> np.ndarray:
         return np.diff(self.bucket_off)
 
+    def updated(self, drop_positions, new_labels):
+        """The layout after an update of the row sequence: the rows at the
+        global positions `drop_positions` are deleted from it and one row per
+        entry of `new_labels` is appended, in that order.  Returns
+
+            (layout, new_dst, surv_off, drop_before)
+
+        layout      equals from_labels over the updated label sequence (row
+                    indices renumbered: survivors keep their relative order,
+                    the new rows follow)
+        new_dst     int64 [m]: the global position of every new row -- behind
+                    its bucket's survivors, stable in batch order
+        surv_off    int64 [C+1]: prefix sums of the survivors per bucket; with
+                    the new offsets it places any per-position table of
+                    the survivors (place_survivors)
+        drop_before int64 [C+1]: how many dropped positions lie before each
+                    old bucket offset (lmi_index_move_rows' table)
+
+        Pure numpy, O(n + m) index arithmetic (slice copies per bucket) and
+        one stable sort of the m new labels; no sort over n."""
+        C_, off = self.n_buckets, self.bucket_off
+        n = int(off[-1])
+        drop = np.unique(np.asarray(drop_positions, dtype=np.int64).ravel())
+        if drop.size != np.asarray(drop_positions).size:
+            raise ValueError("drop_positions must be distinct")
+        if drop.size and (drop[0] < 0 or drop[-1] >= n):
+            raise ValueError(f"drop_positions must lie in [0, {n})")
+        lab = np.asarray(new_labels).astype(np.int64, copy=False).ravel()
+        if lab.size and (lab.min() < 0 or lab.max() >= C_):
+            raise ValueError(f"labels must lie in [0, {C_})")
+        m = int(lab.size)
+        drop_before = np.searchsorted(drop, off, side="left").astype(np.int64)
+        surv = np.diff(off) - np.diff(drop_before)
+        added = np.bincount(lab, minlength=C_).astype(np.int64)
+        new_off = np.zeros(C_ + 1, np.int64)
+        np.cumsum(surv + added, out=new_off[1:])
+        # survivors, in ascending old position (bucket by bucket): bucket c's
+        # start at new_off[c]
+        n_surv = n - int(drop.size)
+        surv_off = np.zeros(C_ + 1, np.int64)
+        np.cumsum(surv, out=surv_off[1:])
+        # new rows: stable rank inside the bucket, after its survivors
+        by_label = np.argsort(lab, kind="stable")
+        add_off = np.zeros(C_ + 1, np.int64)
+        np.cumsum(added, out=add_off[1:])
+        new_dst = np.empty(m, np.int64)
+        new_dst[by_label] = np.arange(m, dtype=np.int64) + np.repeat(
+            new_off[:-1] + surv - add_off[:-1], added)
+        # row indices of the updated sequence: the kept rows renumbered in
+        # their order, then the batch
+        kept = self.order
+        if drop.size:
+            keep_row = np.ones(n, bool)
+            keep_row[self.order[drop]] = False
+            renum = np.cumsum(keep_row) - 1
+            kept = renum[np.delete(self.order, drop)]
+        order = np.empty(n_surv + m, np.int64)
+        self.place_survivors(kept, surv_off, new_off, order)
+        order[new_dst] = n_surv + np.arange(m, dtype=np.int64)
+        return BucketLayout(C_, order, new_off), new_dst, surv_off, drop_before
+
+    @staticmethod
+    def place_survivors(kept, surv_off, new_off, out) -> None:
+        """out[new_off[c] + j] = kept[surv_off[c] + j], j < surv_off[c+1] -
+        surv_off[c], for every bucket c: a per-position table of the survivors
+        (`kept`, in ascending old position) laid out at the front of every
+        bucket's new range.  One slice copy per bucket (memcpy speed; an index
+        array over n is several times slower), an index array when there are
+        more buckets than that pays for."""
+        C_ = int(surv_off.size) - 1
+        if C_ <= 1 << 14:
+            for c in range(C_):
+                a, b = int(surv_off[c]), int(surv_off[c + 1])
+                if b > a:
+                    t = int(new_off[c])
+                    out[t:t + (b - a)] = kept[a:b]
+            return
+        shift = np.repeat(new_off[:-1] - surv_off[:-1], np.diff(surv_off))
+        out[np.arange(kept.size, dtype=np.int64) + shift] = kept
+
     def shard(self, rank: int, world: int):
         """(global positions of the shard's rows, local bucket offsets [C+1])."""
         if world == 1:
@@ -242,11 +322,25 @@ class DeviceIndex:
             self._fill(data, gpos, storage)
         self.gpos = torch.from_numpy(gpos.astype(np.int32)).to(self.device)
         self.n_rows = int(gpos.size)
-        # (default: by the index's size and world, default_chunk_rows)
-        self.chunk_rows = int(chunk_rows) if chunk_rows else default_chunk_rows(world, n)
-        cf = np.zeros(n_buckets + 1, np.int32)
+        cf = self._plan_tables(loc_off, chunk_rows)
+        self.chunk_centroid = None
+        if subcluster and self.n_chunks > 0:
+            self._subcluster_layout(loc_off, cf)
+        self._desc = IndexDescHolder(self)
+        self._ws = {}
+
+    def _plan_tables(self, loc_off, chunk_rows):
+        """chunk_rows and the scan's tables of a shard with the local bucket
+        offsets `loc_off` (bucket_off_local, bucket_rows, chunk_first and
+        their counts); returns the host chunk table."""
+        # (default: by the index's size and world, default_chunk_rows);
+        # _chunk_rows_given: an update keeps an explicit value and takes the
+        # default of its new size otherwise (DeviceIndex.add / remove)
+        self._chunk_rows_given = bool(chunk_rows)
+        self.chunk_rows = int(chunk_rows) if chunk_rows else default_chunk_rows(self.world, self.n_total)
+        cf = np.zeros(self.n_buckets + 1, np.int32)
         lib = _lib.load()
-        mx = lib.lmi_plan_chunks(loc_off.ctypes.data, n_buckets, self.chunk_rows, cf.ctypes.data)
+        mx = lib.lmi_plan_chunks(loc_off.ctypes.data, self.n_buckets, self.chunk_rows, cf.ctypes.data)
         if mx < 0:
             check("lmi_plan_chunks", -mx)
         self.max_chunks = int(mx)
@@ -256,11 +350,144 @@ class DeviceIndex:
         # the shape of the reference's per-bucket product
         self.bucket_rows = torch.from_numpy(np.ascontiguousarray(self.bucket_size, dtype=np.int64)).to(self.device)
         self.chunk_first = torch.from_numpy(cf).to(self.device)
-        self.chunk_centroid = None
-        if subcluster and self.n_chunks > 0:
-            self._subcluster_layout(loc_off, cf)
-        self._desc = IndexDescHolder(self)
-        self._ws = {}
+        return cf
+
+    # ---- updates (K7: csrc/lmi_update.hip) ----------------------
+    @classmethod
+    def empty(cls, d: int, n_buckets: int, *, device=None, chunk_rows: Optional[int] = None) -> "DeviceIndex":
+        """A one-GPU fp16 index of `n_buckets` empty buckets for rows of `d`
+        values, to be filled by `add`: what a construction over zero rows
+        gives."""
+        if int(d) < 1:
+            raise ValueError("d must be positive")
+        return cls(np.zeros((0, int(d)), np.float16), np.zeros((0,), np.int64), n_buckets,
+                   device=device, storage="f16", chunk_rows=chunk_rows)
+
+    def _check_updatable(self):
+        """What add / remove support, refused before any device work."""
+        if self.world > 1:
+            raise ValueError("index update: a striped index (world > 1) cannot be updated in place of "
+                             "a rebuild: stripe boundaries move with the bucket sizes and rows would "
+                             "migrate between ranks")
+        if self.storage != "f16":
+            raise ValueError(f"index update: storage {self.storage!r} is not supported (only 'f16')")
+        if self.corpus64 is not None:
+            raise ValueError("index update: an index with float64 rows (corpus64) is not supported")
+        if self.chunk_centroid is not None:
+            raise ValueError("index update: an index with a sub-cluster layout (chunk_centroid) is "
+                             "not supported")
+
+    def add(self, rows, labels, ids=None) -> "DeviceIndex":
+        """A NEW index with the batch appended to the row sequence: every row
+        goes to the end of the bucket `labels` names for it (host or device
+        integers), in batch order -- bitwise the index a construction from
+        scratch over the concatenated rows, labels and ids gives.  This index
+        is not touched.  `rows`: host or device, [m, d] fp16, or fp32 whose
+        values are fp16-exact (ValueError otherwise).  `ids` default to the
+        ids after the largest one present; ids that repeat or are present
+        already raise ValueError."""
+        self._check_updatable()
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        lab = lab.astype(np.int64, copy=False).ravel()
+        m = int(lab.size)
+        shape = tuple(rows.shape) if hasattr(rows, "shape") else np.asarray(rows).shape
+        if len(shape) != 2 or shape[0] != m or (m and shape[1] != self.d):
+            raise ValueError(f"rows must be [{m}, {self.d}] with one row per label")
+        if ids is None:
+            first = int(self.pos_to_id.max()) + 1 if self.pos_to_id.size else 1
+            ids = np.arange(first, first + m, dtype=np.int64)
+        ids = np.asarray(ids).astype(np.int64, copy=False).ravel()
+        if ids.shape != (m,):
+            raise ValueError("ids must have one entry per new row")
+        if np.unique(ids).size != m:
+            raise ValueError("duplicate ids among the new rows")
+        if m and np.isin(self.pos_to_id, ids).any():
+            raise ValueError("ids of new rows are already in the index")
+        return self._updated(np.zeros(0, np.int64), rows, lab, ids)
+
+    def remove(self, ids) -> "DeviceIndex":
+        """A NEW index without the rows of `ids` (this index is not touched):
+        bitwise the index a construction from scratch over the remaining rows
+        gives.  An id that is not in the index raises KeyError."""
+        self._check_updatable()
+        ids = np.asarray(ids).astype(np.int64, copy=False).ravel()
+        uniq = np.unique(ids)
+        if uniq.size != ids.size:
+            raise ValueError("duplicate ids to remove")
+        drop = np.flatnonzero(np.isin(self.pos_to_id, uniq))
+        if drop.size != uniq.size:
+            missing = np.setdiff1d(uniq, self.pos_to_id[drop])
+            raise KeyError(f"ids not in the index: {missing[:8].tolist()}"
+                           + (" ..." if missing.size > 8 else ""))
+        return self._updated(drop, None, np.zeros(0, np.int64), np.zeros(0, np.int64))
+
+    def _batch_rows(self, rows) -> torch.Tensor:
+        """The batch on the device as lmi_index_ingest_rows reads it: fp16 or
+        fp32 with contiguous rows (a device tensor of that form as it is)."""
+        if not isinstance(rows, torch.Tensor):
+            a = np.asarray(rows)
+            a = a if a.dtype in (np.float16, np.float32, np.float64) else a.astype(np.float32)
+            rows = torch.from_numpy(np.ascontiguousarray(a))
+        if rows.dtype == torch.float64:
+            f = rows.float()
+            if not torch.equal(f.double(), rows):
+                raise ValueError("index update: float64 rows must be fp16-representable")
+            rows = f
+        elif rows.dtype not in (torch.float16, torch.float32):
+            rows = rows.float()
+        rows = rows.to(self.device)
+        return rows if rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1] else rows.contiguous()
+
+    @torch.no_grad()
+    def _updated(self, drop, rows, lab, ids) -> "DeviceIndex":
+        """The index after dropping the global positions `drop` (ascending)
+        and appending the batch: host tables by index arithmetic
+        (BucketLayout.updated), rows by the K7 kernels into new buffers."""
+        lib = _lib.load()
+        layout, new_dst, surv_off, drop_before = self.layout.updated(drop, lab)
+        m, r = int(lab.size), int(drop.size)
+        n_old, n_new = self.n_rows, self.n_rows - r + m
+        new = object.__new__(DeviceIndex)
+        new.device, new.layout, new.n_buckets = self.device, layout, self.n_buckets
+        new.n_total = new.n_rows = n_new
+        new.rank, new.world = 0, 1
+        new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
+        p2id = np.empty(n_new, np.int64)
+        BucketLayout.place_survivors(np.delete(self.pos_to_id, drop) if r else self.pos_to_id, surv_off,
+                                     layout.bucket_off, p2id)
+        p2id[new_dst] = ids
+        new.pos_to_id = p2id
+        new.bucket_size = layout.bucket_size.copy()
+        new._plan_tables(layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
+        new.gpos = torch.arange(n_new, dtype=torch.int32, device=self.device)
+        new.chunk_centroid = None
+        dev = self.device
+        new.corpus = torch.empty((n_new, self.d_pad), dtype=torch.float16, device=dev)
+        new.inv_norm = torch.empty((n_new,), dtype=torch.float32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        s = _lib.stream_handle(dev)
+        if n_old - r > 0:
+            d_drop = torch.from_numpy(drop.astype(np.int64)).to(dev) if r else None
+            d_before = torch.from_numpy(drop_before).to(dev) if r else None
+            check("lmi_index_move_rows", lib.lmi_index_move_rows(
+                ptr(self.corpus), ptr(self.inv_norm), n_old, self.d_pad, ptr(self.bucket_off_local),
+                ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
+                ptr(new.corpus), ptr(new.inv_norm), n_new, ptr(status), s))
+        if m:
+            x = self._batch_rows(rows)
+            d_dst = torch.from_numpy(new_dst).to(dev)
+            check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
+                ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
+                self.d, self.d_pad, ptr(d_dst), ptr(new.corpus), ptr(new.inv_norm), n_new,
+                ptr(status), s))
+        st = int(status.item())  # (waits for both kernels: the inputs above stay alive until here)
+        if st & _lib.LMI_STATUS_ROWS_NOT_F16:
+            raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
+        if st:
+            raise RuntimeError(f"index update: internal status {st}")
+        new._desc = IndexDescHolder(new)
+        new._ws = {}
+        return new
 
     @torch.no_grad()
     def _fill(self, data, gpos, storage):
@@ -903,6 +1130,12 @@ class Searcher:
         self.exchange = bool(exchange)
         self._pinned = {}
         self._qcheck = None
+
+    def with_index(self, index: DeviceIndex) -> "Searcher":
+        """A Searcher over `index` (e.g. the result of DeviceIndex.add /
+        remove) with this one's router and group; its device tables are its
+        own, so this Searcher keeps answering from its own index."""
+        return Searcher(index, self.router, self.group, exchange=self.exchange)
 
     def _host(self, name, shape, dtype):
         buf = self._pinned.get(name)
