@@ -584,6 +584,49 @@ int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m, int64_t ld
                           int32_t d_pad, const int64_t* new_dst, void* dst_corpus,
                           float* dst_inv_norm, int64_t n_new, int32_t* status, void* stream);
 
+/* ---- index re-bucket (K8): new bucket labels without a rebuild -------------- */
+/* A relabel of a one-GPU fp16 index gives every row of its row sequence a new
+ * bucket; the new index is a permutation of the old one, made inside HBM
+ * (li.index.DeviceIndex.relabel).  Both calls run asynchronously on `stream`,
+ * write caller-owned buffers only and OR bits into the device word `status`
+ * (zeroed by the caller).  Additions: LMI_ABI_VERSION does not change. */
+#define LMI_STATUS_BAD_LABEL 8 /* lmi_bucket_sort_labels: a label outside [0, n_buckets) */
+#define LMI_REBUCKET_MAX_BUCKETS 1024 /* the sort keeps one LDS cursor per bucket and wave */
+#define LMI_REBUCKET_MAX_WAVES 4096   /* the sort's waves: longer intervals beyond */
+#define LMI_GATHER_MAX_GRID 2048      /* lmi_index_gather_rows: workgroups (grid-strided beyond) */
+#define LMI_GATHER_TILE_ROWS 32       /* destination rows of a workgroup per pass */
+/* The stable bucket sort of n labels (device, int32 or int64: label_bytes 4 or
+ * 8; labels[s] = bucket of sequence row s):
+ *   bucket_off  device int64 [n_buckets + 1]: prefix sums of the bucket sizes
+ *   order       device int64 [n]: the sequence row of every sorted position,
+ *               rows of one bucket in sequence order
+ * -- numpy's argsort(labels, kind="stable") and cumsum(bincount(labels)), bit
+ * for bit.  A counting sort in four launches: every wave owns one interval of
+ * the sequence (at most LMI_REBUCKET_MAX_WAVES waves), so ranks follow from
+ * (wave, group of 64, lane) and no atomic hands one out.  A label outside
+ * [0, n_buckets) raises LMI_STATUS_BAD_LABEL and nothing is written for its
+ * row (order then has unwritten entries: the caller discards it).
+ * LMI_E_INVALID: label_bytes, n < 0, n_buckets < 1, a null pointer;
+ * LMI_E_UNSUPPORTED: n_buckets > LMI_REBUCKET_MAX_BUCKETS; LMI_E_WORKSPACE: a
+ * workspace smaller than lmi_bucket_sort_labels_ws_bytes(n, n_buckets) (0 for
+ * n = 0 or arguments the sort refuses) or not 8-byte aligned -- all checked
+ * before any device call.  The workspace needs no initialisation. */
+size_t lmi_bucket_sort_labels_ws_bytes(int64_t n, int32_t n_buckets);
+int lmi_bucket_sort_labels(const void* labels, int32_t label_bytes, int64_t n, int32_t n_buckets,
+                           int64_t* bucket_off, int64_t* order, int32_t* status, void* workspace,
+                           size_t ws_bytes, void* stream);
+/* dst_corpus[p] = src_corpus[src_pos[p]] and dst_inv_norm[p] =
+ * src_inv_norm[src_pos[p]] for every p < n_dst:
+ *   src_corpus / dst_corpus  device fp16 [n][d_pad], 16-byte aligned, distinct
+ *   src_pos                  device int64 [n_dst], every entry in [0, n_src)
+ * Destination-major: a wave writes consecutive destination rows as one
+ * contiguous stream, 16 bytes per lane, every offset 64-bit.  A src_pos
+ * outside [0, n_src) is checked before the read: the row is skipped and
+ * LMI_STATUS_INTERNAL raised. */
+int lmi_index_gather_rows(const void* src_corpus, const float* src_inv_norm, int64_t n_src,
+                          int32_t d_pad, const int64_t* src_pos, void* dst_corpus,
+                          float* dst_inv_norm, int64_t n_dst, int32_t* status, void* stream);
+
 /* ---- kernel timing (measurement only) -------------------------------------- */
 /* While enabled, lmi_bucket_topk records a HIP event pair on its stream around
  * its scan kernel (the roofline kernel).  lmi_timing_read waits for the pairs

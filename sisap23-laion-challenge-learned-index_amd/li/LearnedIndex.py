@@ -455,6 +455,33 @@ class LearnedIndex(Logger):
         self._adopt(new_index, nav2, search2, labels2)
         return nav2, search2, labels2
 
+    def rebucket(self, data_navigation, data_search, pred_categories, new_categories=None):
+        """Give the indexed objects new bucket labels without a rebuild
+        (DeviceIndex.relabel: the rows are permuted inside HBM; the corpus does
+        not cross PCIe again).  `new_categories` default to the current
+        model's labels of the navigation rows (`predict`, as `build` labels
+        the data): after inserts, re-cluster and retrain with `build` on the
+        grown frames, then `rebucket(nav, ds, old_pred, pred)`.  The bucket
+        count follows the new labels and the model.  Returns
+
+            (data_navigation2, data_search, new_categories2)
+
+        to pass to later search / search_single calls, as `insert` does.
+        Answers are bitwise those of an index built from the same frames with
+        the new labels."""
+        index = self._updatable_index(data_navigation, data_search, pred_categories)
+        nav2 = data_navigation.drop(columns="category", errors="ignore")
+        if new_categories is None:
+            assert self.model is not None, 'Model is not trained, call `build` first.'
+            new_categories = self.model.predict(data_X_to_torch(nav2))
+        labels2 = np.array(new_categories).astype(np.int64).ravel()
+        if labels2.shape != (nav2.shape[0],):
+            raise ValueError("rebucket: new_categories must have one entry per object")
+        new_index = index.relabel(labels2, n_buckets=self._n_buckets(labels2))
+        nav2["category"] = labels2                     # what search() writes (:67)
+        self._adopt(new_index, nav2, data_search, labels2)
+        return nav2, data_search, labels2
+
     # ---- build (outside the hot path) -------------------------------------
     def build(self, data, n_categories=100, epochs=100, lr=0.1, model_type='MLP',
               train_mode='reference'):

@@ -28,6 +28,7 @@ LMI_E_HIP = 1004
 LMI_STATUS_QUERY_NOT_F16 = 1
 LMI_STATUS_INTERNAL = 2
 LMI_STATUS_ROWS_NOT_F16 = 4
+LMI_STATUS_BAD_LABEL = 8
 
 LMI_F32 = 0
 LMI_F16 = 1
@@ -53,6 +54,12 @@ LMI_KMEANS_MAX_D = 1024
 LMI_TRAIN_MAX_DIM = 1024
 LMI_ROUTER_MAX_DIM = 1024
 LMI_REFINE_EPS = 2.0 ** -16
+# K8 (csrc/lmi_rebucket.hip): the bucket sort's cap on buckets (LDS cursors) and
+# on waves, and the gather's capped grid (workgroups x destination rows a pass)
+LMI_REBUCKET_MAX_BUCKETS = 1024
+LMI_REBUCKET_MAX_WAVES = 4096
+LMI_GATHER_MAX_GRID = 2048
+LMI_GATHER_TILE_ROWS = 32
 
 # every symbol include/lmi_hip.h declares (tests check the export table)
 EXPORTS = (
@@ -87,6 +94,9 @@ EXPORTS = (
     "lmi_mlp_train_steps",
     "lmi_index_move_rows",
     "lmi_index_ingest_rows",
+    "lmi_bucket_sort_labels_ws_bytes",
+    "lmi_bucket_sort_labels",
+    "lmi_index_gather_rows",
     "lmi_timing_enable",
     "lmi_timing_read",
     "lmi_last_error",
@@ -209,6 +219,9 @@ _SIGNATURES = {
     "lmi_index_move_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P,
                                       _P]),
     "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),
+    "lmi_bucket_sort_labels": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_index_gather_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _P]),
     "lmi_timing_enable": (C.c_int, [_I32]),
     "lmi_timing_read": (C.c_int32, [_P, _I32]),
     "lmi_last_error": (C.c_char_p, []),

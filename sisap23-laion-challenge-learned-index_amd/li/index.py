@@ -421,6 +421,110 @@ class DeviceIndex:
                            + (" ..." if missing.size > 8 else ""))
         return self._updated(drop, None, np.zeros(0, np.int64), np.zeros(0, np.int64))
 
+    # ---- re-bucket (K8: csrc/lmi_rebucket.hip) ------------------
+    @staticmethod
+    def _sorted_by_bucket(lab: torch.Tensor, n_buckets: int):
+        """(order, bucket_off) of the device labels `lab` (int32 / int64), both
+        int64 on the device: BucketLayout.from_labels' tables.  Up to
+        LMI_REBUCKET_MAX_BUCKETS buckets by lmi_bucket_sort_labels; above, by
+        torch.sort(stable=True) on the device."""
+        dev, n = lab.device, int(lab.numel())
+        if n_buckets > _lib.LMI_REBUCKET_MAX_BUCKETS:
+            if n and (int(lab.min()) < 0 or int(lab.max()) >= n_buckets):
+                raise ValueError(f"labels must lie in [0, {n_buckets})")
+            order = torch.sort(lab, stable=True).indices
+            off = torch.zeros(n_buckets + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(torch.bincount(lab, minlength=n_buckets), 0, out=off[1:])
+            return order, off
+        lib = _lib.load()
+        order = torch.empty(n, dtype=torch.int64, device=dev)
+        off = torch.empty(n_buckets + 1, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        need = lib.lmi_bucket_sort_labels_ws_bytes(n, n_buckets)
+        ws = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
+        check("lmi_bucket_sort_labels", lib.lmi_bucket_sort_labels(
+            ptr(lab), lab.element_size(), n, n_buckets, ptr(off), ptr(order), ptr(status), ptr(ws),
+            ws.numel() * 8, _lib.stream_handle(dev)))
+        st = int(status.item())  # (before `order` indexes anything: a bad label leaves holes in it)
+        if st & _lib.LMI_STATUS_BAD_LABEL:
+            raise ValueError(f"labels must lie in [0, {n_buckets})")
+        if st:
+            raise RuntimeError(f"index relabel: internal status {st}")
+        return order, off
+
+    @torch.no_grad()
+    def relabel(self, labels, n_buckets: Optional[int] = None, *, timings=None) -> "DeviceIndex":
+        """A NEW index over the same row sequence with the bucket labels
+        `labels` (labels[s]: the bucket of sequence row s -- the constructor's
+        rows with survivors renumbered and batches appended, as layout.order
+        numbers them; host or device integers) and `n_buckets` buckets (default:
+        as many as now) -- bitwise the index a construction from scratch over
+        the rows in sequence order, these labels and the ids in sequence order
+        gives.  The rows move inside HBM (a stable bucket sort of the labels
+        and a row gather on the device); the host uploads the old order /
+        pos_to_id tables and downloads the new ones.  This index is not
+        touched.  `timings` (measurement only): a dict that receives the
+        seconds spent in 'sort', 'tables', 'gather' and 'host'."""
+        self._check_updatable()
+        C_ = self.n_buckets if n_buckets is None else int(n_buckets)
+        if C_ < 1:
+            raise ValueError("n_buckets must be positive")
+        dev, n = self.device, self.n_rows
+        if isinstance(labels, torch.Tensor):
+            lab = labels
+        else:
+            lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
+        if int(lab.numel()) != n:
+            raise ValueError(f"labels must have one entry per row of the index ({n})")
+        if lab.dtype not in (torch.int32, torch.int64):
+            lab = lab.to(torch.int64)
+        lab = lab.reshape(-1).to(dev).contiguous()
+        lib = _lib.load()
+        lap = [time.perf_counter()]
+
+        def mark(name):
+            if timings is not None:
+                torch.cuda.synchronize(dev)
+                lap.append(time.perf_counter())
+                timings[name] = timings.get(name, 0.0) + lap[-1] - lap[-2]
+
+        order, off = self._sorted_by_bucket(lab, C_)
+        mark("sort")
+        # src_pos[p]: where the old index holds the row of new position p (the
+        # inverse of the old order, read at the new one); pos_to_id moves as the rows do
+        old_order = torch.from_numpy(self.layout.order).to(dev)
+        inv = torch.empty(n, dtype=torch.int64, device=dev)
+        inv[old_order] = torch.arange(n, dtype=torch.int64, device=dev)
+        src_pos = inv[order]
+        del inv, old_order
+        p2id = torch.from_numpy(self.pos_to_id).to(dev)[src_pos]
+        mark("tables")
+        new = object.__new__(DeviceIndex)
+        new.device, new.n_buckets = dev, C_
+        new.n_total = new.n_rows = n
+        new.rank, new.world = 0, 1
+        new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
+        new.corpus = torch.empty((n, self.d_pad), dtype=torch.float16, device=dev)
+        new.inv_norm = torch.empty((n,), dtype=torch.float32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        check("lmi_index_gather_rows", lib.lmi_index_gather_rows(
+            ptr(self.corpus), ptr(self.inv_norm), n, self.d_pad, ptr(src_pos), ptr(new.corpus),
+            ptr(new.inv_norm), n, ptr(status), _lib.stream_handle(dev)))
+        st = int(status.item())  # (waits for the kernel: src_pos stays alive until here)
+        if st:
+            raise RuntimeError(f"index relabel: internal status {st}")
+        mark("gather")
+        new.layout = BucketLayout(C_, order.cpu().numpy(), off.cpu().numpy())
+        new.pos_to_id = p2id.cpu().numpy()
+        new.bucket_size = new.layout.bucket_size.copy()
+        new._plan_tables(new.layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
+        new.gpos = torch.arange(n, dtype=torch.int32, device=dev)
+        new.chunk_centroid = None
+        new._desc = IndexDescHolder(new)
+        new._ws = {}
+        mark("host")
+        return new
+
     def _batch_rows(self, rows) -> torch.Tensor:
         """The batch on the device as lmi_index_ingest_rows reads it: fp16 or
         fp32 with contiguous rows (a device tensor of that form as it is)."""
