@@ -1228,10 +1228,9 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     a.gpos = idx->gpos;
     a.lo_g = lo_g;
 
-    if (c.phases != kPhaseAll && !ring) {
-        set_error("phase flags need the fp16 scan (scan v2/v3: fp16 corpus and fp16-exact queries)");
-        return LMI_E_UNSUPPORTED;
-    }
+    // (the phases split the general kernel's call as they split the rings':
+    // everything a later phase reads -- the rounded queries, the tile plan,
+    // the work counter, the partial lists -- lives in the workspace)
     if (ring && do_scan) {
         Scan2Args b{};
         b.corpus = reinterpret_cast<const _Float16*>(idx->corpus);
@@ -1267,7 +1266,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
             b.sub_take = wide->sub_take;
         }
         LMI_TRY(launch.ring(b, s));
-    } else if (!ring) {
+    } else if (!ring && do_scan) {
         LMI_TRY(launch.general(a, idx->d_pad, s));
     }
     if (!do_merge) return LMI_OK;

@@ -178,9 +178,13 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
                 static_assert(sizeof(TC) == 2, "fp16 math needs an fp16 corpus");
                 const half8* ysrc = reinterpret_cast<const half8*>(yrow) + 4 * h;
                 half8 acur[4], anext[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) acur[s] = ysrc[s];
                 const int nkb = d_pad / 64;
+                // (d_pad == 32 has no full block: lane half 1's first 64 B
+                // would lie past its row, past the corpus for the last row)
+                if (nkb > 0) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) acur[s] = ysrc[s];
+                }
                 for (int kb = 0; kb < nkb; ++kb) {
                     if (kb + 1 < nkb) {
 #pragma unroll

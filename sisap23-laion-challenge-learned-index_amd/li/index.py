@@ -1216,10 +1216,13 @@ class Searcher:
         """`exchange`: run the list exchange (route_sharded, K2 into the packed
         send buffer, the all-gather, lmi_merge_topk_packed) over the process
         group.  None (default): when a group is initialised and the index is
-        a stripe of a G > 1 index, the group has G > 1 ranks, or
-        LMI_FORCE_EXCHANGE=1 (li.dist.force_exchange: a one-rank RCCL group
-        then takes the G > 1 branch of every step form, so the exchange runs
-        on one GPU exactly as on eight)."""
+        a stripe of a G > 1 index, or LMI_FORCE_EXCHANGE=1
+        (li.dist.force_exchange: a one-rank RCCL group then takes the G > 1
+        branch of every step form, so the exchange runs on one GPU exactly as
+        on eight).  A whole index (index.world == 1) under a group of several
+        ranks answers on its own: every rank holds every row, K3 does not
+        deduplicate, and gathering G copies of the same lists would repeat
+        each object G times -- asking for that exchange is a ValueError."""
         import torch.distributed as tdist
         from .dist import force_exchange
         self.index = index
@@ -1227,10 +1230,13 @@ class Searcher:
         self.group = group
         grouped = tdist.is_available() and tdist.is_initialized()
         if exchange is None:
-            exchange = grouped and (index.world > 1 or tdist.get_world_size(group) > 1
-                                    or force_exchange())
+            exchange = grouped and (index.world > 1 or force_exchange())
         if exchange and not grouped:
             raise ValueError("the list exchange needs an initialised process group")
+        if exchange and index.world == 1 and tdist.get_world_size(group) > 1:
+            raise ValueError("the list exchange over a group of several ranks needs a striped "
+                             "index (world > 1): every rank of a whole index returns the same "
+                             "lists, and the merge would repeat each object once per rank")
         self.exchange = bool(exchange)
         self._pinned = {}
         self._qcheck = None

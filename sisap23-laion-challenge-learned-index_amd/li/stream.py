@@ -139,8 +139,9 @@ class StreamedSearch:
     enqueues each scan at the start of its own launch.  `reserve_cus` (None:
     stream_reserve's default): CUs the scan's persistent grid leaves to the
     finish chain, which then runs beside the next scan.  fp16 index and
-    fp16-exact query batches (the phased scan
-    is the fp16 scan; other batches go through Searcher.search), or the split
+    fp16-exact query batches of an even width (the phased scan runs in fp16
+    arithmetic: the rings at d_pad 768, the general kernel's fp16-math variant
+    at every other width; other batches go through Searcher.search), or the split
     mode (storage f32x, k_round <= 10, float32 batches: its SCAN phase is the
     sample scan, the bound and the collect scan, its MERGE phase the exact
     re-score; ABI 11)."""

@@ -3,7 +3,12 @@
 gather_merge_packed -> lmi_merge_topk_packed, device replay) with
 torch.distributed over gloo, two ranks sharing the box's one GPU (RCCL refuses
 two ranks on one device; gloo stages the collectives through host memory).
-Rank 0 writes the answers to the .npz named on the command line."""
+Rank 0 writes the answers to the .npz named on the command line.
+
+A second argument "replicated" runs the other documented mode instead: every
+rank builds the WHOLE index (world = 1) inside the same process group and
+answers on its own (no list exchange: the ranks' lists are the same lists);
+every rank writes its answers to <path>.rank<r>.npz."""
 import os
 import sys
 
@@ -14,6 +19,36 @@ sys.path[:0] = [os.path.join(ROOT, "sisap23-laion-challenge-learned-index_amd"),
 
 
 N_BATCHES = 7
+
+
+# (router labels: no bucket a query probes is smaller than k, so the reference
+# semantics' short-bucket padding, which repeats ids, does not occur)
+REPLICATED = dict(n=3000, nq=96, C=16, seed=67, label_mode="router")
+
+
+def replicated(out_path):
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    import workloads
+    from li.dist import init_from_env
+    from li.index import DeviceIndex, DeviceRouter, Searcher
+    rank, world, _ = init_from_env(backend="gloo")
+    torch.cuda.set_device(0)
+    w = workloads.clustered(**REPLICATED)
+    ix = DeviceIndex(w["x"], w["labels"], w["C"], chunk_rows=256, device="cuda:0")
+    s = Searcher(ix, DeviceRouter(w["layers"], device="cuda:0"))
+    qn = torch.from_numpy(w["qn"]).cuda()
+    q = torch.from_numpy(w["q"]).cuda()
+    res = {"exchange": np.array([int(s.exchange)]), "world": np.array([world])}
+    for dist_ in ("f32", "f64"):
+        for R in (1, 4):
+            res[f"{dist_}_R{R}_d"], res[f"{dist_}_R{R}_a"] = s.search(qn, q, R, k=10, dist=dist_)
+    res["exact_d"], res["exact_a"] = s.search(qn, q, 4, k=10, semantics="exact")
+    np.savez(f"{out_path}.rank{rank}.npz", **res)
+    dist.barrier()
+    dist.destroy_process_group()
 
 
 def main(out_path):
@@ -83,4 +118,7 @@ def main(out_path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if sys.argv[2:] == ["replicated"]:
+        replicated(sys.argv[1])
+    else:
+        main(sys.argv[1])

@@ -65,7 +65,7 @@ def _worker(rank, world, port, result_path):
     sys.path[:0] = [os.path.join(root, "sisap23-laion-challenge-learned-index_amd"),
                     os.path.join(root, "oracle"), here]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+                      WORLD_SIZE=str(world), LOCAL_RANK="0")
     import lmi_oracle as O
     import workloads
     from li.dist import (gather_merge, gather_merge_packed, init_from_env, packed_lists,
@@ -123,6 +123,52 @@ def _worker(rank, world, port, result_path):
             f.write("ok" if ok else "mismatch")
     dist.barrier()
     dist.destroy_process_group()
+
+
+def _exchange_worker(rank, world, port, result_dir):
+    """When Searcher turns the list exchange on: only for a
+    striped index, or under LMI_FORCE_EXCHANGE=1 -- never for a whole index
+    that merely runs inside a group of several ranks, whose ranks all return
+    the same lists (K3 does not deduplicate)."""
+    import sys
+    import types
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    sys.path[:0] = [os.path.join(root, "sisap23-laion-challenge-learned-index_amd"),
+                    os.path.join(root, "oracle"), here]
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
+                      WORLD_SIZE=str(world), LOCAL_RANK="0")
+    os.environ.pop("LMI_FORCE_EXCHANGE", None)
+    from li.dist import init_from_env
+    from li.index import Searcher
+    init_from_env(backend="gloo")
+    whole = types.SimpleNamespace(world=1, rank=0)
+    stripe = types.SimpleNamespace(world=world, rank=rank)
+    got = {"whole": Searcher(whole, None).exchange,
+           "stripe": Searcher(stripe, None).exchange,
+           "whole_off": Searcher(whole, None, exchange=False).exchange}
+    try:
+        Searcher(whole, None, exchange=True)
+        got["whole_forced_raises"] = False
+    except ValueError as e:
+        got["whole_forced_raises"] = "striped" in str(e)
+    # (new_group is collective: every rank creates every one-rank group)
+    solo = [dist.new_group([r]) for r in range(world)][rank]
+    got["solo_plain"] = Searcher(whole, None, group=solo).exchange
+    os.environ["LMI_FORCE_EXCHANGE"] = "1"
+    got["solo_forced"] = Searcher(whole, None, group=solo).exchange
+    want = {"whole": False, "stripe": True, "whole_off": False, "whole_forced_raises": True,
+            "solo_plain": False, "solo_forced": True}
+    with open(os.path.join(result_dir, f"rank{rank}.txt"), "w") as f:
+        f.write("ok" if got == want else f"mismatch: {got}")
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_exchange_is_for_striped_indexes_only(tmp_path):
+    mp.spawn(_exchange_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    for r in range(2):
+        assert (tmp_path / f"rank{r}.txt").read_text() == "ok"
 
 
 @pytest.mark.parametrize("world", [2, 3])

@@ -4,7 +4,9 @@ bitwise equal answers (reference semantics R = 1 and 4, exact semantics) and
 bitwise equal merged per-(query, probe) lists, in both arithmetics.  This is
 the striped index + route_sharded + packed K2 buffers + all-gather +
 lmi_merge_topk_packed + device replay, as Searcher.search runs them at G > 1
-(the 8-GPU bench uses RCCL for the same collectives)."""
+(the 8-GPU bench uses RCCL for the same collectives).  And the replicated
+mode: two processes in one group that each hold the whole index answer
+exactly as one process does -- no object twice."""
 import os
 import socket
 import subprocess
@@ -85,3 +87,45 @@ def test_two_process_product_path_equals_one_process(world, tmp_path):
         d, a = s.search(T(a_), T(b_), 4, k=10)
         np.testing.assert_array_equal(got[f"stream_odd_{i}_d"], d)
         np.testing.assert_array_equal(got[f"stream_odd_{i}_a"], a)
+
+
+@pytest.mark.timeout(300)
+def test_replicated_index_under_a_group_answers_as_one_process(tmp_path):
+    """Each rank of a two-rank group builds the whole index (world = 1): no
+    list exchange (K3 would repeat every object once per rank), and both
+    ranks give the one-process answers bit for bit."""
+    out = tmp_path / "replicated"
+    port = _port()
+    procs = []
+    for r in range(2):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE="2",
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LMI_DIST_TIMEOUT_S="120")
+        env.pop("LMI_FORCE_EXCHANGE", None)
+        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "dist_gpu_worker.py"),
+                                       str(out), "replicated"], env=env))
+    rcs = [p.wait(timeout=240) for p in procs]
+    assert rcs == [0, 0], rcs
+    w = workloads.clustered(**dist_gpu_worker.REPLICATED)
+    s = Searcher(DeviceIndex(w["x"], w["labels"], w["C"], chunk_rows=256, device="cuda"),
+                 DeviceRouter(w["layers"], device="cuda"))
+    qn = torch.from_numpy(w["qn"]).cuda()
+    q = torch.from_numpy(w["q"]).cuda()
+    ref = {}
+    for dist_ in ("f32", "f64"):
+        for R in (1, 4):
+            ref[f"{dist_}_R{R}"] = s.search(qn, q, R, k=10, dist=dist_)
+    ref["exact"] = s.search(qn, q, 4, k=10, semantics="exact")
+    for name, (d, a) in ref.items():
+        # (this workload has no duplicated rows: only the fill id 0 may repeat)
+        for row in np.asarray(a):
+            real = row[row != 0]
+            assert np.unique(real).size == real.size, name
+    for r in range(2):
+        got = np.load(f"{out}.rank{r}.npz")
+        assert int(got["world"][0]) == 2 and int(got["exchange"][0]) == 0
+        for name, (d, a) in ref.items():
+            np.testing.assert_array_equal(got[f"{name}_d"], d, err_msg=f"rank {r} {name}")
+            np.testing.assert_array_equal(got[f"{name}_a"], a, err_msg=f"rank {r} {name}")
+            for row in got[f"{name}_a"]:
+                real = row[row != 0]
+                assert np.unique(real).size == real.size, f"rank {r} {name}: an id repeats"
