@@ -109,9 +109,12 @@ def test_device_replay_on_real_lists_reaches_every_branch(seed):
 def test_device_replay_large_groups(use_threshold, nq, C):
     """Groups whose relevant positions exceed the kernel's LDS staging
     (kUCap = 8192 entries) take the global-scratch path; small ones in the
-    same launch stay in LDS.  Selection runs from registers up to 16384
-    entries (thresholded rounds of nq=2500, C=4: 9.4K-14.4K), from the
-    global share beyond (nq=6000, C=5: 19K-25K; nq=12000, C=3: up to 74K)."""
+    same launch stay in LDS (thresholded rounds of nq=2500, C=4: 9.4K-14.4K
+    entries; nq=6000, C=5: 19K-25K; nq=12000, C=3: up to 74K).  The buckets
+    hold 40 to 400 rows, so every group's positions lie inside the selection
+    bitmap's span and all of them select by the bitmap; selection from
+    registers and from the global share (spans of 196608 positions and more)
+    is test_gpu_replay_params.py::test_selection_tiers_beyond_the_bitmap."""
     classes, d, pos, size, ids = _random_lists(21, nq=nq, R=3, C=C, kl=10, tiny=(C - 1,))
     ref_d, ref_a = replay(classes, d, pos, k_round=10, k_final=10, bucket_size=size,
                           pos_to_id=ids, use_threshold=use_threshold)
