@@ -79,6 +79,14 @@ extern "C" {
 /* ABI 10 (lmi_bucket_topk_f64g only): the float64 refinement as a phase of
  * its own, after the ranks' k-th distances were exchanged. */
 #define LMI_Q_PHASE_REFINE 0x1000
+/* The scan in two launches over one tile queue (lmi_scan_set_join_workgroups,
+ * j > 0): extra workgroups of the SCAN phase's kernel, launched on their own
+ * -- on any stream, before, beside or after the SCAN phase's launch, after the
+ * PLAN phase and before the MERGE phase.  The scan's workgroups never wait for
+ * one another and share only the queue counters and the pairs' bounds, so the
+ * late workers take whatever tiles are left and the merged lists are those of
+ * one launch.  Not part of "no phase flag = all three"; a no-op with j = 0. */
+#define LMI_Q_PHASE_SCAN_JOIN 0x2000
 
 #define LMI_MAX_LAYERS 8
 #define LMI_MAX_K 16          /* largest k of one scan pass (and of K3 / the float32 ABI 1 lists) */
@@ -678,6 +686,25 @@ int lmi_config_reload(void);
  * keeps the grid it was captured with); results never depend on it.  Returns
  * the previous setting. */
 int32_t lmi_scan_set_workgroups(int32_t wgs);
+/* The late-joining scan (see LMI_Q_PHASE_SCAN_JOIN): the number j of the
+ * scan's workgroups that the SCAN phase leaves to the SCAN_JOIN phase.  With
+ * j > 0 the SCAN phase of lmi_bucket_topk[_f64*] launches its kernel with j
+ * workgroups fewer than the grid above (at least one stays), and the
+ * SCAN_JOIN phase launches the same kernel with j workgroups on the workspace
+ * as the plan left it.  The plan never depends on j.  0 (the default): the
+ * SCAN phase launches the whole grid and the SCAN_JOIN phase does nothing.
+ * Only the scans of the 8-wave ring with 10- or 15-entry lists or band lists
+ * take j > 0 (lmi_scan_joinable / lmi_scan_f64_joinable); every other scan
+ * (the split mode, k > LMI_MAX_K, the general kernel and the 4-wave ring)
+ * refuses a SCAN or SCAN_JOIN phase while j > 0 with LMI_E_INVALID and
+ * launches nothing.  Thread-local, read at launch like the grid; results
+ * never depend on it.  Returns the previous setting. */
+int32_t lmi_scan_set_join_workgroups(int32_t j);
+/* 1 when lmi_bucket_topk (lmi_scan_joinable) or lmi_bucket_topk_f64* (the
+ * _f64 form) of these arguments runs a scan that takes j > 0, else 0. */
+int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, int32_t qmode);
+int lmi_scan_f64_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
+                          int32_t qmode);
 
 #ifdef __cplusplus
 }

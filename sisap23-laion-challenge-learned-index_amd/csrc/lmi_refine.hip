@@ -1825,7 +1825,7 @@ int bucket_topk_f64_impl(const lmi_index_desc* idx, const float* q, int32_t nq, 
         // none = all four (one rank: kth_all == kth_send)
         const bool ref = (qmode & LMI_Q_PHASE_REFINE) != 0;
         qmode &= ~LMI_Q_PHASE_REFINE;
-        const bool any = ((qmode >> 9) & 7) != 0;
+        const bool any = (qmode & ((7 << 9) | LMI_Q_PHASE_SCAN_JOIN)) != 0;
         phases = take_phases(qmode);
         if (!any && ref) phases = 0;
         do_refine = ref || !any;
@@ -1849,6 +1849,9 @@ int bucket_topk_f64_impl(const lmi_index_desc* idx, const float* q, int32_t nq, 
     LMI_CHECK_ARG(q64 == nullptr || ldq64 >= idx->d, "ldq64 < d");
     if (idx->corpus32) {  // (phases: k <= 10, ABI 11; not the global band's REFINE)
         LMI_CHECK_ARG(!global, "the global band needs an index without corpus32");
+        bool done;
+        LMI_TRY(join_gate(phases, false, &done));  // (the split mode's scans take no join workgroups)
+        if (done) return LMI_OK;
         return bucket_topk_x(idx, q, nq, ldq, q64, ldq64, classes, R, k, out_d, 1, out_pos, status,
                              workspace, ws_bytes, reinterpret_cast<hipStream_t>(stream), phases);
     }
@@ -1856,6 +1859,14 @@ int bucket_topk_f64_impl(const lmi_index_desc* idx, const float* q, int32_t nq, 
     if (ws_bytes < w.total) {
         set_error("workspace %zu B < required %zu B", ws_bytes, w.total);
         return LMI_E_WORKSPACE;
+    }
+    // (join workgroups, lmi_scan_set_join_workgroups: the one scan of the
+    // 8-wave ring takes them -- bucket_topk_impl gates it again --, the passes
+    // of k + 5 > LMI_MAX_K and the other kernels refuse before any launch)
+    if (phases != 0) {
+        bool done;
+        LMI_TRY(join_gate(phases, !w.passes && band_capable(idx, qmode), &done));
+        if (done && !do_refine) return LMI_OK;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     auto* ws = reinterpret_cast<unsigned char*>(workspace);
@@ -1962,6 +1973,15 @@ extern "C" int lmi_bucket_topk_f64q(const lmi_index_desc* idx, const float* q, i
 
 extern "C" int lmi_f64_global_band(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
                                    int32_t qmode) {
+    using namespace lmi;
+    qmode &= ~(LMI_Q_SEED_ROUND0 | LMI_Q_PHASE_REFINE);
+    take_phases(qmode);
+    if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K_F64) return 0;
+    return (!refine_ws(idx, nq, R, k, qmode).passes && band_capable(idx, qmode)) ? 1 : 0;
+}
+
+extern "C" int lmi_scan_f64_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
+                                     int32_t qmode) {
     using namespace lmi;
     qmode &= ~(LMI_Q_SEED_ROUND0 | LMI_Q_PHASE_REFINE);
     take_phases(qmode);

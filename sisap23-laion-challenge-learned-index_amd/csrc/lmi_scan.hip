@@ -899,7 +899,30 @@ bool band_capable(const lmi_index_desc* idx, int qmode) {
 
 namespace {
 thread_local int t_scan_wgs = 0;  // lmi_scan_set_workgroups (0: env / every CU)
+thread_local int t_join_wgs = 0;  // lmi_scan_set_join_workgroups (0: one launch)
+thread_local int t_grid = 0;      // ScanGrid: the grid of the launch under way (0: num_cus())
 }  // namespace
+
+int join_wgs() { return t_join_wgs; }
+
+int join_gate(int& phases, bool joinable, bool* done) {
+    *done = false;
+    if (t_join_wgs == 0) {
+        phases &= ~kPhaseJoin;
+        *done = phases == 0;
+        return LMI_OK;
+    }
+    if ((phases & (kPhaseScan | kPhaseJoin)) && !joinable) {
+        set_error("this scan does not take join workgroups (j = %d): the 8-wave ring's 10- and 15-entry "
+                  "lists and band lists do", t_join_wgs);
+        return LMI_E_INVALID;
+    }
+    return LMI_OK;
+}
+
+int scan_grid() { return t_grid > 0 ? t_grid : num_cus(); }
+ScanGrid::ScanGrid(int wgs) { t_grid = wgs; }
+ScanGrid::~ScanGrid() { t_grid = 0; }
 
 int num_cus() {
     static int n = 0;
@@ -1046,7 +1069,14 @@ extern "C" int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool seed = (qmode & LMI_Q_SEED_ROUND0) != 0;
     qmode &= ~LMI_Q_SEED_ROUND0;
-    const int phases = take_phases(qmode);
+    int phases = take_phases(qmode);
+    // (the split mode and k > LMI_MAX_K refuse join workgroups before they
+    // launch anything; bucket_topk_impl gates its own call)
+    if (idx && (idx->corpus32 || k > LMI_MAX_K)) {
+        bool done;
+        LMI_TRY(join_gate(phases, false, &done));
+        if (done) return LMI_OK;
+    }
     if (idx && idx->corpus32)  // (phases: k <= 10, ABI 11)
         return bucket_topk_x(idx, q, nq, ldq, nullptr, 0, classes, R, k, out_d, 0, out_pos, status, workspace,
                              ws_bytes, s, phases);
@@ -1067,7 +1097,6 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     float *out_d = c.out_d, *out_bound = c.out_bound, *kth_out = c.kth_out;
     int32_t *out_pos = c.out_pos, *out_row = c.out_row, *status = c.status;
     hipStream_t s = c.stream;
-    const bool do_plan = c.phases & kPhasePlan, do_scan = c.phases & kPhaseScan, do_merge = c.phases & kPhaseMerge;
     LMI_CHECK_ARG(idx != nullptr, "null index");
     LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32, "bad corpus dtype");
     LMI_CHECK_ARG(idx->d >= 1 && idx->d_pad >= idx->d && idx->d_pad % 32 == 0, "bad d/d_pad");
@@ -1094,6 +1123,22 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         set_error("no scan kernel takes this call's wide mode, lower bounds or band lists with %d-entry lists", w.kl);
         return LMI_E_UNSUPPORTED;
     }
+    // The scan in two launches (lmi_scan_set_join_workgroups, j > 0): the SCAN
+    // phase launches the grid less j workgroups, the SCAN_JOIN phase the same
+    // kernel with j on the workspace as it stands -- extra workers of the same
+    // tile queues.  The product lists of the 8-wave ring take it (plain 10- and
+    // 15-entry lists, the band lists); the plan below never sees j
+    int phases = c.phases;
+    {
+        bool done;
+        LMI_TRY(join_gate(phases, v3 && wide == nullptr && lo_g == nullptr, &done));
+        if (done) return LMI_OK;
+    }
+    const bool do_plan = phases & kPhasePlan, do_scan = phases & kPhaseScan, do_merge = phases & kPhaseMerge;
+    // (at least one workgroup stays in the main launch; phases & kPhaseJoin is
+    // set only with j > 0)
+    const int join_n = std::min(join_wgs(), num_cus() - 1);
+    const bool do_join = (phases & kPhaseJoin) && join_n > 0;
     auto* ws = reinterpret_cast<unsigned char*>(c.workspace);
     const int P = nq * R;
 
@@ -1231,7 +1276,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     // (the phases split the general kernel's call as they split the rings':
     // everything a later phase reads -- the rounded queries, the tile plan,
     // the work counter, the partial lists -- lives in the workspace)
-    if (ring && do_scan) {
+    if (ring && (do_scan || do_join)) {
         Scan2Args b{};
         b.corpus = reinterpret_cast<const _Float16*>(idx->corpus);
         b.inv_norm = idx->inv_norm;
@@ -1265,7 +1310,16 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
             b.sub_rows = wide->sub_rows;
             b.sub_take = wide->sub_take;
         }
-        LMI_TRY(launch.ring(b, s));
+        if (do_scan && join_n > 0) {
+            const ScanGrid grid(num_cus() - join_n);
+            LMI_TRY(launch.ring(b, s));
+        } else if (do_scan) {
+            LMI_TRY(launch.ring(b, s));
+        }
+        if (do_join) {
+            const ScanGrid grid(join_n);
+            LMI_TRY(launch.ring(b, s));
+        }
     } else if (!ring && do_scan) {
         LMI_TRY(launch.general(a, idx->d_pad, s));
     }
@@ -1300,6 +1354,20 @@ extern "C" int32_t lmi_scan_set_workgroups(int32_t wgs) {
     const int prev = lmi::t_scan_wgs;
     lmi::t_scan_wgs = wgs > 0 ? wgs : 0;
     return prev;
+}
+
+extern "C" int32_t lmi_scan_set_join_workgroups(int32_t j) {
+    const int prev = lmi::t_join_wgs;
+    lmi::t_join_wgs = j > 0 ? j : 0;
+    return prev;
+}
+
+extern "C" int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, int32_t qmode) {
+    using namespace lmi;
+    qmode &= ~LMI_Q_SEED_ROUND0;
+    take_phases(qmode);
+    if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
+    return scan_plan(idx, nq, R, k, qmode).family == ScanKernel::Ring8 ? 1 : 0;
 }
 
 extern "C" int lmi_timing_enable(int32_t on) {

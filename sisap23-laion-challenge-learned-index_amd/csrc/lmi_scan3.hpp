@@ -929,8 +929,9 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     }
 }
 
-// one launch of the persistent grid (one workgroup per CU, dynamic LDS);
-// HIP events around it while lmi_timing_enable is on
+// one launch of the persistent grid (one workgroup per CU, dynamic LDS; inside
+// a ScanGrid scope that scope's grid: the main and the join launch of a scan
+// in two launches); HIP events around it while lmi_timing_enable is on
 template <int KL, int ABL, bool LO = false, int MODE = 0>
 int launch_scan3_v(const Scan2Args& b, hipStream_t s) {
     constexpr size_t lds = v3::lds_bytes<KL>();
@@ -947,7 +948,7 @@ int launch_scan3_v(const Scan2Args& b, hipStream_t s) {
         const int rc = timing_record(s, true, ev);
         if (rc != LMI_OK) return rc;
     }
-    hipLaunchKernelGGL((scan3_kernel<KL, ABL, LO, MODE>), dim3(num_cus()), dim3(v3::NW * 64), lds, s, b);
+    hipLaunchKernelGGL((scan3_kernel<KL, ABL, LO, MODE>), dim3(scan_grid()), dim3(v3::NW * 64), lds, s, b);
     LMI_LAUNCH_CHECK("scan3_kernel");
     if (timed) return timing_record(s, false, ev);
     return LMI_OK;

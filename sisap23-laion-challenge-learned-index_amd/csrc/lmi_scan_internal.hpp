@@ -232,14 +232,31 @@ bool band_capable(const lmi_index_desc* idx, int qmode);
 size_t scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
                             int32_t qmode, bool lo = false);
 
-// phases of bucket_topk_impl (LMI_Q_PHASE_* of the ABI, shifted to bits 0..2)
-constexpr int kPhasePlan = 1, kPhaseScan = 2, kPhaseMerge = 4, kPhaseAll = 7;
+// phases of bucket_topk_impl (LMI_Q_PHASE_* of the ABI, shifted to bits 0..2;
+// kPhaseJoin: LMI_Q_PHASE_SCAN_JOIN, not one of "all")
+constexpr int kPhasePlan = 1, kPhaseScan = 2, kPhaseMerge = 4, kPhaseAll = 7, kPhaseJoin = 8;
 // LMI_Q_PHASE_* bits of a qmode -> kPhase* (none set = all); strips them from qmode
 inline int take_phases(int32_t& qmode) {
-    const int p = (qmode >> 9) & 7;
-    qmode &= ~(7 << 9);
+    const int p = ((qmode >> 9) & 7) | ((qmode & LMI_Q_PHASE_SCAN_JOIN) ? kPhaseJoin : 0);
+    qmode &= ~((7 << 9) | LMI_Q_PHASE_SCAN_JOIN);
     return p ? p : kPhaseAll;
 }
+// The late-joining scan (lmi_scan_set_join_workgroups): j of this thread, and
+// the gate every entry point passes its phases through before it launches
+// anything: with j = 0 the join phase is dropped (*done: nothing is left to
+// do); with j > 0 a call with a SCAN or SCAN_JOIN phase whose scan does not
+// take the join (`joinable` false) is refused with LMI_E_INVALID
+int join_wgs();
+int join_gate(int& phases, bool joinable, bool* done);
+// the grid of the scan launch under way: scan_grid() is num_cus() but inside a
+// ScanGrid scope (the main and the join launch of bucket_topk_impl)
+int scan_grid();
+struct ScanGrid {
+    explicit ScanGrid(int wgs);
+    ~ScanGrid();
+    ScanGrid(const ScanGrid&) = delete;
+    ScanGrid& operator=(const ScanGrid&) = delete;
+};
 // The scans of the wide path (k > 16, bucket_topk_wide): mode 1 writes every
 // (pair, chunk part) list as that part's own top-15 (no global bound); mode 2
 // collects every row within the pair's bound bound_ord[pair id] (a distance

@@ -42,6 +42,7 @@ LMI_Q_PHASE_PLAN = 0x200
 LMI_Q_PHASE_SCAN = 0x400
 LMI_Q_PHASE_MERGE = 0x800
 LMI_Q_PHASE_REFINE = 0x1000
+LMI_Q_PHASE_SCAN_JOIN = 0x2000
 LMI_REPLAY_PHASE_GROUPS = 1
 LMI_REPLAY_PHASE_ROUNDS = 2
 LMI_MAX_LAYERS = 8
@@ -103,6 +104,9 @@ EXPORTS = (
     "lmi_abi_version",
     "lmi_config_reload",
     "lmi_scan_set_workgroups",
+    "lmi_scan_set_join_workgroups",
+    "lmi_scan_joinable",
+    "lmi_scan_f64_joinable",
     "lmi_host_hash64",
     "lmi_host_stage_f16",
     "lmi_host_copy",
@@ -228,6 +232,9 @@ _SIGNATURES = {
     "lmi_abi_version": (C.c_int32, []),
     "lmi_config_reload": (C.c_int, []),
     "lmi_scan_set_workgroups": (C.c_int32, [_I32]),
+    "lmi_scan_set_join_workgroups": (C.c_int32, [_I32]),
+    "lmi_scan_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
+    "lmi_scan_f64_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_host_hash64": (C.c_uint64, [_P, C.c_uint64, _I32]),
     "lmi_host_stage_f16": (C.c_int32, [_P, C.c_uint64, _P, _I32]),
     "lmi_host_copy": (C.c_int, [_P, _P, C.c_uint64, _I32]),

@@ -21,7 +21,11 @@ batch it finished; every batch passes every stage (the same kernels as
 Searcher.search), so each answer equals Searcher.search of its batch bit for
 bit.  The persistent scan holds every CU while it runs, so the R, P and F
 chains start in its tail; the next launch's scan, enqueued ahead, waits on
-the device for this launch's F, so the scans run back to back.
+the device for this launch's F, so the scans run back to back.  With
+`join_cus` = j the scan is two launches of one kernel over one set of tile
+queues: S, the grid less j workgroups, starts right behind the previous scan
+without that wait, F runs on the j CUs left free, and SJ, j more workgroups,
+follows F on the finish stream.
 
 G > 1 ranks (the corpus striped, li.dist): each rank stages and uploads only
 its block of the batch (1/G of the rows: the host-memory traffic of a new
@@ -123,6 +127,26 @@ def stream_reserve() -> int:
     return int(env) if env is not None else 0
 
 
+# The default `join_cus` of a StreamedSearch, as a fraction of the device's CUs
+# (0: off): measured at 10M, W = 1, float32 (profiles/scan_join_ab.txt,
+# DESIGN.md §5 "The finish beside a late-joining scan"): CUs/8 took 1.0-1.3%
+# off the step (every replicate under the parent's fastest); CUs/4 and 3 CUs/8
+# were within the parent's spread, CUs/16 and 3 CUs/32 10% slower (the finish
+# then gets no CU beside the scan, as with reserve_cus).  The float64 stream
+# and the striped (G > 1) stream are not measured yet: off by default there.
+JOIN_CUS_FRACTION = 0.125
+# ... and only where the scan is long beside the finish it overlaps: pairs x
+# mean bucket rows of at least this (10M, R = 4, 10k queries: 3.3e9, a 6.9 ms
+# scan, -1%; 300K, R = 7: 1.7e8, a 0.6 ms scan in a host-bound 0.8 ms launch,
+# where the second graph launch per step made the launch 1.04-1.19 ms)
+JOIN_MIN_WORK = 1.5e9
+
+
+def stream_join(ncu: int) -> int:
+    """The default `join_cus` of a StreamedSearch on a device of `ncu` CUs."""
+    return int(ncu * JOIN_CUS_FRACTION)
+
+
 class QueryNotF16(RuntimeError):
     """A streamed batch held clip768 values that fp16 cannot represent: the
     phased scan (fp16 MFMA) cannot answer it; Searcher.search can (exact fp32
@@ -138,7 +162,17 @@ class StreamedSearch:
     earlier) and, unless `reserve_cus` > 0, for this launch's F; False
     enqueues each scan at the start of its own launch.  `reserve_cus` (None:
     stream_reserve's default): CUs the scan's persistent grid leaves to the
-    finish chain, which then runs beside the next scan.  fp16 index and
+    finish chain, which then runs beside the next scan.  `join_cus` (None:
+    stream_join's default for the float32 stream of one rank where the scan
+    takes it, the 8-wave ring's lists, else 0;
+    exclusive with `reserve_cus`): the scan in two launches over one tile
+    queue -- the S graph launches the scan's grid less `join_cus` workgroups
+    right behind the previous scan, without waiting for this launch's F, which
+    runs on the CUs left free; the SJ graph, `join_cus` more workgroups of the
+    same kernel on the same queues (LMI_Q_PHASE_SCAN_JOIN), follows F on the
+    finish stream.  `time_scans` brackets the S graph: its workgroups run
+    until the shared queues are empty, so its end is the scan's end to within
+    one tile.  fp16 index and
     fp16-exact query batches of an even width (the phased scan runs in fp16
     arithmetic: the rings at d_pad 768, the general kernel's fp16-math variant
     at every other width; other batches go through Searcher.search), or the split
@@ -151,7 +185,8 @@ class StreamedSearch:
     def __init__(self, searcher, q_nav, q_search, R: int, k: int = 10, *,
                  k_round: int = 10, use_threshold: bool = True, dist: str = "f32",
                  capture: bool = True, lookahead: bool = True, kth_peers=None,
-                 reserve_cus: Optional[int] = None, stop_mass=None, min_probes: int = 1):
+                 reserve_cus: Optional[int] = None, stop_mass=None, min_probes: int = 1,
+                 join_cus: Optional[int] = None):
         from .index import check_stop
         check_stop(stop_mass, min_probes)
         # the router's stop rule (DeviceRouter.topr), inside the route stage
@@ -311,15 +346,21 @@ class StreamedSearch:
                           pos_to_id=p2id, use_threshold=use_threshold, out=(ad, aa, ast[1:2]),
                           phases=_lib.LMI_REPLAY_PHASE_GROUPS, ws=self.rws[j], k_list=kl)
 
-        def scan(j):
-            if not self.scan_wgs:
-                phase(j, _lib.LMI_Q_PHASE_SCAN)
+        def scan(j, ph=_lib.LMI_Q_PHASE_SCAN):
+            if not self.scan_wgs and not self.join_wgs:
+                phase(j, ph)
                 return
-            prev = lib.lmi_scan_set_workgroups(self.scan_wgs)
+            # (the two are exclusive: the grid for reserve_cus, j for join_cus)
+            setter = lib.lmi_scan_set_workgroups if self.scan_wgs else lib.lmi_scan_set_join_workgroups
+            prev = setter(self.scan_wgs or self.join_wgs)
             try:
-                phase(j, _lib.LMI_Q_PHASE_SCAN)
+                phase(j, ph)
             finally:
-                lib.lmi_scan_set_workgroups(prev)
+                setter(prev)
+
+        def join(j):
+            # (the late join: join_wgs more workgroups of slot j's scan)
+            scan(j, _lib.LMI_Q_PHASE_SCAN_JOIN)
 
         def finish1(j):
             if gband:
@@ -360,7 +401,7 @@ class StreamedSearch:
         # (F1: the merge phase [float64: + the kth exchange and the REFINE
         # phase]; FX: the all-gather of slot j's lists with the next batch's
         # block, which waits for that block's route; F2: K3 + replay + D2H)
-        self._f = dict(U=upload, R=route, X=xgather, P=plan, S=scan, F=finish, F1=finish1,
+        self._f = dict(U=upload, R=route, X=xgather, P=plan, S=scan, SJ=join, F=finish, F1=finish1,
                        FX=xgather, F2=finish2)
         # four streams: the finish, the plan, the upload + route (the H2D on
         # the copy engine, then the router), and the scan on the caller's
@@ -370,7 +411,7 @@ class StreamedSearch:
         self._cs = self._rs
         ev = lambda: [torch.cuda.Event() for _ in range(NS)]
         self._up, self._rdone, self._pdone, self._sdone = ev(), ev(), ev(), ev()
-        self._gdone, self._fdone = ev(), ev()
+        self._gdone, self._fdone, self._jdone = ev(), ev(), ev()
         self.graphs = None
         self._closed = False
         self._t = None  # launch counter once primed
@@ -391,6 +432,27 @@ class StreamedSearch:
             raise ValueError(f"reserve_cus={r} outside [0, {ncu})")
         self.scan_wgs = ncu - r if r > 0 else 0
         self.overlap = r > 0
+        # join_cus > 0: the scan in two launches (lmi_scan_set_join_workgroups,
+        # LMI_Q_PHASE_SCAN_JOIN): the S graph holds the grid less join_cus
+        # workgroups and does not wait for the launch's finish either; the SJ
+        # graph, the other join_cus workgroups, is launched on the finish
+        # stream behind F (DESIGN.md §5 "The finish beside a late-joining scan")
+        joinable = not split and bool((lib.lmi_scan_f64_joinable if f64 else lib.lmi_scan_joinable)(
+            C.byref(ix.desc_for(kl)), nq, R, kl, _lib.LMI_Q_F16))
+        if join_cus is None:
+            work = nq * R * int(ix.desc.n_rows) / max(int(ix.desc.n_buckets), 1)
+            jw = stream_join(ncu) if joinable and r == 0 and not f64 and not X and work >= JOIN_MIN_WORK else 0
+        else:
+            jw = int(join_cus)
+            if not 0 <= jw < ncu:
+                raise ValueError(f"join_cus={jw} outside [0, {ncu})")
+            if jw > 0 and r > 0:
+                raise ValueError("join_cus and reserve_cus are exclusive")
+            if jw > 0 and not joinable:
+                raise ValueError("join_cus needs the 8-wave ring's scan (an fp16 index of width 768, "
+                                 "k_round <= 15, not the split mode)")
+        self.join_cus = self.join_wgs = jw
+        self._joins = []  # slots whose main scan is enqueued and whose join is not yet
         self._s_ahead = False  # the next launch's scan is already enqueued
         for j in range(NS):
             if not self.stage(nav, qs, slot=j):
@@ -419,7 +481,8 @@ class StreamedSearch:
         if capture:
             # one graph per (stage, slot); F is F1 + FX + F2 at G > 1 (the garbage
             # collector off meanwhile: li._host "graph lifetime")
-            names = ("R", "P", "S") + (("F1", "FX", "F2") if X else ("F",))
+            names = ("R", "P", "S") + (("SJ",) if self.join_wgs else ()) + \
+                (("F1", "FX", "F2") if X else ("F",))
             self.graphs = {}
             with no_gc_capture():
                 for name in names:
@@ -438,7 +501,8 @@ class StreamedSearch:
         step() returns)."""
         if getattr(self, "_closed", True) or capture_underway():
             return
-        for evs in (self._up, self._rdone, self._pdone, self._sdone, self._gdone, self._fdone):
+        for evs in (self._up, self._rdone, self._pdone, self._sdone, self._gdone, self._fdone,
+                    self._jdone):
             for e in evs:
                 e.synchronize()
         for st in (self._fs, self._ps, self._rs):
@@ -516,6 +580,8 @@ class StreamedSearch:
         for name in order:
             if name == "X":
                 self._f["X"]((j + 1) % self.NS)  # the exchange buffer holding slot j's block
+            elif name == "S":
+                self._scan_eager(j)
             else:
                 self._f[name](j)
             if name == upto:
@@ -531,6 +597,14 @@ class StreamedSearch:
         torch.cuda.current_stream(dev).synchronize()
         self._t = 0
         self._s_ahead = False
+        self._joins = []
+
+    def _scan_eager(self, j):
+        """Slot j's whole scan on the current stream (fill and drain): the
+        SCAN phase and, with `join_cus`, its join workgroups behind it."""
+        self._f["S"](j)
+        if self.join_wgs:
+            self._f["SJ"](j)
 
     def _run(self, name, j):
         if self.graphs is not None:
@@ -548,11 +622,25 @@ class StreamedSearch:
         else:
             self._run("S", j)
         self._sdone[j].record(main)
+        if self.join_wgs:
+            self._joins.append(j)
+
+    def _run_joins(self):
+        """The late joins of the scans enqueued so far, on the finish stream
+        (behind the finish just launched there; each after its slot's plan)."""
+        for j in self._joins:
+            self._fs.wait_event(self._pdone[j])
+            with torch.cuda.stream(self._fs):
+                self._run("SJ", j)
+            self._jdone[j].record(self._fs)
+        self._joins = []
 
     def scan_ms(self):
         """Durations (ms) of the scans step() launched while `time_scans` was
         set (HIP events on the scan's stream, outside the captured graphs),
-        in launch order; clears the record."""
+        in launch order; clears the record.  With `join_cus` the events stay
+        around the S graph alone: the main workgroups run until the shared
+        queues are empty, so its end is the scan's end to within one tile."""
         out = []
         for e0, e1 in self._scan_ev:
             e1.synchronize()
@@ -576,7 +664,10 @@ class StreamedSearch:
             plan:   wait route [G > 1: the all-gather] -> widen, K2 PLAN (slot t)
 
         With `lookahead` the next launch's scan (slot t+3, planned a launch
-        earlier) is enqueued too, behind this launch's finish on the device."""
+        earlier) is enqueued too, behind this launch's finish on the device;
+        with `join_cus` it does not wait for the finish, and its late join
+        (and the join of a scan enqueued at the start of this launch) goes
+        onto the finish stream behind F."""
         if self._closed:
             raise RuntimeError("StreamedSearch: step() after close()")
         if self._t is None:
@@ -605,6 +696,11 @@ class StreamedSearch:
                 self._run("P", jr)
             self._pdone[jr].record(self._ps)
         self._fs.wait_event(self._sdone[jf])
+        if self.join_wgs:
+            # (slot jf's join went onto this stream one or two launches ago:
+            # stream order already puts it before F; the event holds where the
+            # streams were exchanged meanwhile)
+            self._fs.wait_event(self._jdone[jf])
         if not X:
             with torch.cuda.stream(self._fs):
                 self._run("F", jf)
@@ -630,9 +726,11 @@ class StreamedSearch:
         if self.lookahead:
             jn = (t + 3) % NS
             main.wait_event(self._pdone[jn])
-            if not self.overlap:
+            if not self.overlap and not self.join_wgs:
                 main.wait_event(self._fdone[jf])
             self._run_scan(jn, main)
+        # (join_cus: the joins of the scans this launch enqueued, behind F)
+        self._run_joins()
         self._s_ahead = bool(self.lookahead)
         self._t += 1
         self.launches += 1
@@ -712,11 +810,11 @@ class StreamedSearch:
         sync()
         yield self._take(j1, held[j1])
         if not self._s_ahead:
-            self._f["S"](j2)
+            self._scan_eager(j2)
         self._f["F"](j2)
         sync()
         yield self._take(j2, held[j2])
-        self._f["S"](j3)
+        self._scan_eager(j3)
         self._f["F"](j3)
         sync()
         self.drain()

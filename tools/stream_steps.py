@@ -20,6 +20,8 @@ ap.add_argument("--modes", default="stream", help="comma list of stream (default
 ap.add_argument("--dist", default="f32", choices=["f32", "f64"])
 ap.add_argument("--chunks", default="", help="comma list of chunk rows to try (default: the bench's by W)")
 ap.add_argument("--all-ranks", action="store_true", help="time every rank's stripe of each W (not only rank 0)")
+ap.add_argument("--join-cus", type=int, default=None,
+                help="StreamedSearch(join_cus=...): workgroups of the late-joining scan (0: none; default: the stream's)")
 ap.add_argument("--local-band", action="store_true",
                 help="float64: every stripe refines the band of its own list (the round-5 form; "
                      "LMI_F64_LOCAL_BAND=1 must be set too) instead of the W-rank band")
@@ -73,7 +75,7 @@ for W, ck, rk in [(W, ck, rk) for W in map(int, a.worlds.split(","))
                 ka = peer_kth(W, ck)
                 kw["kth_peers"] = torch.cat([ka[:rk], ka[rk + 1:]])
             st = s.streamed(qn, q, 4, k=10, dist=a.dist, capture=not (a.eager or mode == "stream-eager"),
-                            lookahead=mode != "stream-nola", **kw)
+                            lookahead=mode != "stream-nola", join_cus=a.join_cus, **kw)
             fn = st.step
         else:
             st = s.graph(qn, q, 4, k=10, dist=a.dist, pipeline=mode == "graph-pipe")
@@ -85,6 +87,6 @@ for W, ck, rk in [(W, ck, rk) for W in map(int, a.worlds.split(","))
             fn()
         torch.cuda.synchronize()
         print(f"world {W} rank {rk} chunk {ck} {a.dist}: {mode} {(time.perf_counter() - t0) / a.steps * 1e3:.3f} ms/step "
-              f"(scan WGs {os.environ.get('LMI_SCAN_WGS', 'all CUs')})", flush=True)
+              f"(scan WGs {os.environ.get('LMI_SCAN_WGS', 'all CUs')}, join {getattr(st, 'join_cus', 0)})", flush=True)
         del st, fn
     del s, ix; torch.cuda.empty_cache()
