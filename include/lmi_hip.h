@@ -592,6 +592,47 @@ int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m, int64_t ld
                           int32_t d_pad, const int64_t* new_dst, void* dst_corpus,
                           float* dst_inv_norm, int64_t n_new, int32_t* status, void* stream);
 
+/* ---- index update in place (K9): add / remove inside one buffer ------------- */
+/* lmi_index_move_rows with source and destination in the SAME store of
+ * `capacity` rows (li.index.DeviceIndex.add / remove with inplace=True): an add
+ * (direction LMI_INPLACE_ADD: n_dropped == 0, n_new >= n_old) shifts every old
+ * row right, a remove (LMI_INPLACE_REMOVE: n_new == n_old - n_dropped) shifts
+ * every survivor left, both by an amount that does not decrease along the
+ * corpus.  The host cuts the rows that move into slabs
+ * (li.index.BucketLayout.inplace_slabs):
+ *   slabs   HOST int64 [n_slabs][3] = (a, b, staged): old rows [a, b) inside
+ *           [0, n_old), disjoint, in processing order -- an add from the end of
+ *           the corpus backwards (every b <= the a before it), a remove from
+ *           the front forwards (every a >= the b before it)
+ *   staged = 0  the slab's destinations are disjoint from [a, b): one launch
+ *               reads the store and writes the store
+ *   staged = 1  the slab (at most stage_rows rows) is first copied to
+ *               stage_corpus [stage_rows][d_pad] / stage_inv_norm [stage_rows],
+ *               then written from there in a second launch
+ * The whole chain is enqueued on `stream` by this one call; the order between
+ * slabs is stream order alone (no grid barrier, no flag, no cooperative
+ * launch), and inside one launch no workgroup writes a row another reads.
+ * flags: LMI_INPLACE_MEMCPY copies a staged slab with hipMemcpyAsync instead
+ * of the copy kernel (measurement).  The tables are lmi_index_move_rows'.
+ * LMI_E_INVALID before any device call: a null or misaligned pointer, n_old
+ * or n_new above capacity, counts that contradict the direction, a slab
+ * outside [0, n_old), overlapping or out of the direction's order, a staged
+ * slab longer than stage_rows.  In the kernel, before every write: the
+ * destination lies in [0, n_new), outside [a, b) for a direct slab, and on
+ * the direction's side of the source row; a row that fails is skipped and
+ * LMI_STATUS_INTERNAL raised (the store's content is then undefined).
+ * Additions: LMI_ABI_VERSION does not change. */
+#define LMI_INPLACE_ADD 1
+#define LMI_INPLACE_REMOVE (-1)
+#define LMI_INPLACE_MEMCPY 1
+int lmi_index_move_rows_inplace(void* corpus, float* inv_norm, int64_t n_old, int64_t n_new,
+                                int64_t capacity, int32_t d_pad, const int64_t* old_off,
+                                const int64_t* new_off, int32_t n_buckets, const int64_t* dropped,
+                                int64_t n_dropped, const int64_t* drop_before, int32_t direction,
+                                const int64_t* slabs, int64_t n_slabs, void* stage_corpus,
+                                float* stage_inv_norm, int64_t stage_rows, int32_t flags,
+                                int32_t* status, void* stream);
+
 /* ---- index re-bucket (K8): new bucket labels without a rebuild -------------- */
 /* A relabel of a one-GPU fp16 index gives every row of its row sequence a new
  * bucket; the new index is a permutation of the old one, made inside HBM

@@ -15,6 +15,12 @@
 //
 // Every destination row is checked against [0, n_new) before it is written;
 // a row that fails is skipped and LMI_STATUS_INTERNAL is raised.
+//
+// K9 (at the end of this file; DESIGN.md §3 "K9") is the same move with source
+// and destination in ONE store that has room for the new rows
+// (lmi_index_move_rows_inplace): slabs of rows in stream order, each moved
+// directly or through a staging buffer.  Offered for add and remove only; a
+// re-bucket (lmi_rebucket.hip) still writes a new corpus.
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
@@ -249,5 +255,202 @@ extern "C" int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m,
                            static_cast<uint4*>(dst_corpus), dst_inv_norm, n_new, status);
     }
     LMI_LAUNCH_CHECK("ingest_rows_kernel");
+    return LMI_OK;
+}
+
+// K9 — the same update inside ONE buffer (lmi_index_move_rows_inplace; DESIGN.md
+// §3 "K9").  An add shifts every old row right, a remove shifts every survivor
+// left, both by an amount that does not decrease along the corpus, so the host
+// cuts the shifted rows into slabs [a, b) (li.index.BucketLayout.inplace_slabs)
+// and the slabs run one after the other in stream order -- an add from the end
+// of the corpus backwards, a remove from the front forwards:
+//
+//   direct  the slab's destinations are disjoint from [a, b): one launch reads
+//           the store and writes the store
+//   staged  the slab is copied to the staging buffer first; a second launch
+//           writes it from there to its destinations
+//
+// Destinations of a slab lie in its own (already staged) source range or in
+// rows earlier slabs have vacated, never in rows a later slab still reads, and
+// inside one launch no workgroup writes a row another one reads.  There is no
+// barrier, flag or cooperative launch: the order between slabs is the stream's.
+namespace lmi {
+namespace {
+
+constexpr int kCopyThreads = 256;
+constexpr int kCopyMaxGrid = 4096;
+
+// move_rows_kernel restricted to the old rows [a, b), read from `src` whose row
+// 0 is old row src_row0 (the store: 0; the staging buffer: a).  src and dst may
+// be the same buffer (a direct slab), so neither is __restrict__.  Before every
+// write: the destination lies in [0, n_new), outside [a, b) for a direct slab,
+// and on the declared side of the source row (direction > 0: right, < 0: left).
+__global__ __launch_bounds__(kMoveThreads) void move_range_kernel(
+    const uint4* src, const float* src_inv, int64_t src_row0, int64_t a, int64_t b, int32_t pieces,
+    const int64_t* __restrict__ old_off, const int64_t* __restrict__ new_off, int32_t n_buckets,
+    const int64_t* __restrict__ dropped, int64_t n_dropped, const int64_t* __restrict__ drop_before,
+    uint4* dst, float* dst_inv, int64_t n_new, int32_t direction, int32_t direct,
+    int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t n_tiles = (b - a + kMoveTileRows - 1) / kMoveTileRows;
+    const int32_t total = kMoveWaveRows * pieces;  // 16-byte pieces of the wave's rows
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t base = a + tile * kMoveTileRows + (int64_t)wave * kMoveWaveRows;
+        int64_t to = -1;
+        if (lane < kMoveWaveRows && base + lane < b) {
+            const int64_t i = base + lane;
+            to = move_dst(i, old_off, new_off, n_buckets, dropped, n_dropped, drop_before);
+            if (to >= 0) {  // (a dropped row goes nowhere)
+                const bool bad = to >= n_new || (direct && to >= a && to < b) ||
+                                 (direction > 0 ? to < i : to > i);
+                if (bad) {  // (never, for tables and slabs that describe the update)
+                    atomicOr(status, LMI_STATUS_INTERNAL);
+                    to = -1;
+                }
+            }
+            if (to >= 0) dst_inv[to] = src_inv[i - src_row0];
+        }
+        const uint4* s = src + (base - src_row0) * pieces;
+        // four 16-byte loads in flight per lane before the first store
+        for (int32_t q0 = lane; q0 < total + lane; q0 += 4 * 64) {
+            // (named registers, not arrays: no staging through LDS or scratch)
+            auto at = [&](int32_t q) -> int64_t {  // piece q's place in dst, -1: none
+                const int32_t r = q < total ? q / pieces : 0;
+                const int64_t t = __shfl(to, r);   // (every lane takes part)
+                return (q < total && t >= 0) ? t * pieces + (q - r * pieces) : -1;
+            };
+            const int64_t a0 = at(q0), a1 = at(q0 + 64), a2 = at(q0 + 128), a3 = at(q0 + 192);
+            uint4 v0 = {}, v1 = {}, v2 = {}, v3 = {};
+            if (a0 >= 0) v0 = s[q0];
+            if (a1 >= 0) v1 = s[q0 + 64];
+            if (a2 >= 0) v2 = s[q0 + 128];
+            if (a3 >= 0) v3 = s[q0 + 192];
+            if (a0 >= 0) dst[a0] = v0;
+            if (a1 >= 0) dst[a1] = v1;
+            if (a2 >= 0) dst[a2] = v2;
+            if (a3 >= 0) dst[a3] = v3;
+        }
+    }
+}
+
+// rows [0, n_rows) of src (n_pieces 16-byte pieces) and their 1/||y|| to the
+// staging buffer: a contiguous copy, four loads in flight per thread
+__global__ __launch_bounds__(kCopyThreads) void copy_slab_kernel(
+    const uint4* __restrict__ src, const float* __restrict__ src_inv, int64_t n_pieces, int64_t n_rows,
+    uint4* __restrict__ dst, float* __restrict__ dst_inv) {
+    const int64_t step = (int64_t)gridDim.x * kCopyThreads * 4;
+    for (int64_t q = (int64_t)blockIdx.x * kCopyThreads * 4 + threadIdx.x; q < n_pieces; q += step) {
+        const bool p1 = q + kCopyThreads < n_pieces, p2 = q + 2 * kCopyThreads < n_pieces,
+                   p3 = q + 3 * kCopyThreads < n_pieces;
+        uint4 v0 = src[q], v1 = {}, v2 = {}, v3 = {};
+        if (p1) v1 = src[q + kCopyThreads];
+        if (p2) v2 = src[q + 2 * kCopyThreads];
+        if (p3) v3 = src[q + 3 * kCopyThreads];
+        dst[q] = v0;
+        if (p1) dst[q + kCopyThreads] = v1;
+        if (p2) dst[q + 2 * kCopyThreads] = v2;
+        if (p3) dst[q + 3 * kCopyThreads] = v3;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x; i < n_rows;
+         i += (int64_t)gridDim.x * kCopyThreads)
+        dst_inv[i] = src_inv[i];
+}
+
+}  // namespace
+}  // namespace lmi
+
+extern "C" int lmi_index_move_rows_inplace(void* corpus, float* inv_norm, int64_t n_old, int64_t n_new,
+                                           int64_t capacity, int32_t d_pad, const int64_t* old_off,
+                                           const int64_t* new_off, int32_t n_buckets,
+                                           const int64_t* dropped, int64_t n_dropped,
+                                           const int64_t* drop_before, int32_t direction,
+                                           const int64_t* slabs, int64_t n_slabs, void* stage_corpus,
+                                           float* stage_inv_norm, int64_t stage_rows, int32_t flags,
+                                           int32_t* status, void* stream) {
+    using namespace lmi;
+    LMI_CHECK_ARG(direction == LMI_INPLACE_ADD || direction == LMI_INPLACE_REMOVE,
+                  "move rows in place: direction=%d (LMI_INPLACE_ADD or LMI_INPLACE_REMOVE)", direction);
+    LMI_CHECK_ARG((flags & ~LMI_INPLACE_MEMCPY) == 0, "move rows in place: flags=%d", flags);
+    LMI_CHECK_ARG(n_old >= 0 && n_new >= 0 && n_dropped >= 0 && n_dropped <= n_old && n_slabs >= 0 &&
+                      stage_rows >= 0,
+                  "move rows in place: n_old=%lld n_new=%lld n_dropped=%lld n_slabs=%lld stage_rows=%lld",
+                  (long long)n_old, (long long)n_new, (long long)n_dropped, (long long)n_slabs,
+                  (long long)stage_rows);
+    LMI_CHECK_ARG(n_old <= capacity && n_new <= capacity,
+                  "move rows in place: n_old=%lld / n_new=%lld rows exceed the capacity of %lld rows",
+                  (long long)n_old, (long long)n_new, (long long)capacity);
+    if (direction == LMI_INPLACE_ADD)
+        LMI_CHECK_ARG(n_dropped == 0 && n_new >= n_old,
+                      "move rows in place: an add drops no row and does not shrink (n_dropped=%lld, "
+                      "n_old=%lld, n_new=%lld)", (long long)n_dropped, (long long)n_old, (long long)n_new);
+    else
+        LMI_CHECK_ARG(n_new == n_old - n_dropped,
+                      "move rows in place: a remove leaves n_old - n_dropped = %lld rows, n_new=%lld",
+                      (long long)(n_old - n_dropped), (long long)n_new);
+    LMI_CHECK_ARG(d_pad > 0 && d_pad % 32 == 0, "move rows in place: d_pad=%d (a positive multiple of 32)",
+                  d_pad);
+    LMI_CHECK_ARG(n_buckets >= 1, "move rows in place: n_buckets=%d", n_buckets);
+    if (n_slabs == 0) return LMI_OK;  // no row moves
+    LMI_CHECK_ARG(corpus && inv_norm && old_off && new_off && slabs && status,
+                  "move rows in place: null pointer");
+    LMI_CHECK_ARG(n_dropped == 0 || (dropped && drop_before),
+                  "move rows in place: null dropped / drop_before");
+    LMI_CHECK_ARG(aligned16(corpus), "move rows in place: corpus not 16-byte aligned");
+    // the plan: slabs inside [0, n_old), disjoint, in the direction's order
+    // (an add from the end backwards, a remove from the front forwards)
+    bool any_staged = false;
+    for (int64_t k = 0; k < n_slabs; ++k) {
+        const int64_t a = slabs[3 * k], b = slabs[3 * k + 1], staged = slabs[3 * k + 2];
+        LMI_CHECK_ARG(a >= 0 && a < b && b <= n_old && (staged == 0 || staged == 1),
+                      "move rows in place: slab %lld = [%lld, %lld) staged=%lld outside [0, %lld)",
+                      (long long)k, (long long)a, (long long)b, (long long)staged, (long long)n_old);
+        if (k > 0) {
+            const int64_t pa = slabs[3 * k - 3], pb = slabs[3 * k - 2];
+            LMI_CHECK_ARG(direction == LMI_INPLACE_ADD ? b <= pa : a >= pb,
+                          "move rows in place: slab %lld = [%lld, %lld) overlaps or is out of order "
+                          "after [%lld, %lld)", (long long)k, (long long)a, (long long)b, (long long)pa,
+                          (long long)pb);
+        }
+        LMI_CHECK_ARG(!staged || b - a <= stage_rows,
+                      "move rows in place: staged slab %lld holds %lld rows, the staging buffer %lld",
+                      (long long)k, (long long)(b - a), (long long)stage_rows);
+        any_staged |= staged != 0;
+    }
+    LMI_CHECK_ARG(!any_staged || (stage_corpus && stage_inv_norm && aligned16(stage_corpus) &&
+                                  stage_corpus != corpus && stage_inv_norm != inv_norm),
+                  "move rows in place: staging buffers null, misaligned or the store itself");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t pieces = d_pad / 8;
+    uint4* const store = static_cast<uint4*>(corpus);
+    uint4* const stage = static_cast<uint4*>(stage_corpus);
+    for (int64_t k = 0; k < n_slabs; ++k) {
+        const int64_t a = slabs[3 * k], b = slabs[3 * k + 1];
+        const bool staged = slabs[3 * k + 2] != 0;
+        if (staged) {
+            const int64_t n_pieces = (b - a) * pieces;
+            if (flags & LMI_INPLACE_MEMCPY) {
+                LMI_HIP_TRY(hipMemcpyAsync(stage, store + a * pieces, (size_t)n_pieces * sizeof(uint4),
+                                           hipMemcpyDeviceToDevice, s));
+                LMI_HIP_TRY(hipMemcpyAsync(stage_inv_norm, inv_norm + a, (size_t)(b - a) * sizeof(float),
+                                           hipMemcpyDeviceToDevice, s));
+            } else {
+                const int64_t per = (int64_t)kCopyThreads * 4;
+                const unsigned grid = (unsigned)std::min<int64_t>((n_pieces + per - 1) / per, kCopyMaxGrid);
+                hipLaunchKernelGGL(copy_slab_kernel, dim3(grid), dim3(kCopyThreads), 0, s,
+                                   store + a * pieces, inv_norm + a, n_pieces, b - a, stage,
+                                   stage_inv_norm);
+                LMI_LAUNCH_CHECK("copy_slab_kernel");
+            }
+        }
+        const int64_t tiles = (b - a + kMoveTileRows - 1) / kMoveTileRows;
+        const unsigned grid = (unsigned)std::min<int64_t>(tiles, kMoveMaxGrid);
+        hipLaunchKernelGGL(move_range_kernel, dim3(grid), dim3(kMoveThreads), 0, s,
+                           staged ? stage : store, staged ? stage_inv_norm : inv_norm,
+                           staged ? a : (int64_t)0, a, b, pieces, old_off, new_off, n_buckets, dropped,
+                           n_dropped, drop_before, store, inv_norm, n_new, direction, staged ? 0 : 1,
+                           status);
+        LMI_LAUNCH_CHECK("move_range_kernel");
+    }
     return LMI_OK;
 }

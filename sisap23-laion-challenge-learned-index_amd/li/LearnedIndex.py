@@ -200,17 +200,20 @@ class LearnedIndex(Logger):
         return (refs[0] is data_search and refs[1] is labels and refs[2] is data_navigation.index
                 and t[0] == self._identity(data_navigation, data_search, labels))
 
-    def attach(self, data_navigation, data_search, pred_categories):
+    def attach(self, data_navigation, data_search, pred_categories, capacity=None):
         """Build the HBM index of data_search (rows in data_navigation's id
         order, bucket labels `pred_categories`) now, outside any timed call,
         and trust these objects: later search / search_single calls that pass
         the same objects (same id, shape, dtype and value arrays) reuse it
         without hashing their bytes.  The caller must not change them in
         place afterwards (or must call attach again).  An addition; the
-        reference has no such step (it re-gathers every bucket per call)."""
+        reference has no such step (it re-gathers every bucket per call).
+        `capacity`: rows to allocate the HBM index for (DeviceIndex's
+        `capacity`), so that insert / delete with inplace=True can update it
+        inside its own store."""
         self._trusted = None
         self._cat_written = None
-        self._device_index(data_navigation, data_search, pred_categories)
+        self._device_index(data_navigation, data_search, pred_categories, capacity=capacity)
         # strong references to the trusted objects: while they are held, their
         # id()s and buffers cannot be reused by new objects (ADVICE r3)
         self._trusted = (self._identity(data_navigation, data_search, pred_categories),
@@ -223,17 +226,19 @@ class LearnedIndex(Logger):
         self._trusted = None
         self._cat_written = None
 
-    def _device_index(self, data_navigation, data_search, labels):
-        """DeviceIndex of data_search rows in data_navigation order."""
+    def _device_index(self, data_navigation, data_search, labels, capacity=None):
+        """DeviceIndex of data_search rows in data_navigation order (with a
+        store of at least `capacity` rows when given)."""
         from .index import DeviceIndex
-        if self._is_attached(data_navigation, data_search, labels):
+        fits = lambda ix: capacity is None or ix.capacity >= int(capacity)
+        if self._is_attached(data_navigation, data_search, labels) and fits(self._index):
             return self._index
         labels = np.asarray(labels).astype(np.int64)
         ds = _search_frame(data_search)
         ids = np.asarray(data_navigation.index)
         key = (content_key(ds), content_key(labels), content_key(ids),
                content_key(np.asarray(ds.index)) if hasattr(ds, "index") else None)
-        if self._index is not None and self._cache_key == key:
+        if self._index is not None and self._cache_key == key and fits(self._index):
             return self._index
         # fp16 data (the real clip768 'emb') stays fp16 on its way to HBM;
         # float64 data keeps its float64 values for the float64 mode
@@ -250,7 +255,7 @@ class LearnedIndex(Logger):
         self._searcher = None
         pg = self._proc_group()
         shard = {} if pg is None else dict(rank=pg[1], world=pg[2], chunk_rows=pg[3])
-        self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, **shard)
+        self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, **shard)
         self._cache_key = key
         return self._index
 
@@ -397,7 +402,8 @@ class LearnedIndex(Logger):
                          (data_search, labels, data_navigation.index))
         self._attached_labels = labels
 
-    def insert(self, data_navigation, data_search, pred_categories, new_navigation, new_search):
+    def insert(self, data_navigation, data_search, pred_categories, new_navigation, new_search,
+               inplace=False):
         """Add objects to the index without a rebuild: the router labels the
         new navigation rows (`predict`, as `build` labels the data), the frames
         and labels are concatenated on the host and the HBM index takes the
@@ -410,7 +416,10 @@ class LearnedIndex(Logger):
         index as after `attach` (same contract: do not change them in place).
         Answers are bitwise those of an index built from the concatenated
         frames.  New ids (new_navigation.index) that repeat or collide with
-        existing ones raise ValueError."""
+        existing ones raise ValueError.  `inplace` (default off): the rows
+        move inside the index's own store (DeviceIndex.add(inplace=True); the
+        index needs the room: attach(..., capacity=...)) -- same frames, same
+        answers, no second corpus in HBM."""
         import pandas as pd
         assert self.model is not None, 'Model is not trained, call `build` first.'
         new_ids = np.asarray(new_navigation.index)
@@ -430,7 +439,7 @@ class LearnedIndex(Logger):
             rows = ds.loc[new_navigation.index].to_numpy(dtype=dt)
         else:
             rows = np.asarray(ds, dtype=dt)
-        new_index = index.add(rows, new_labels, ids=new_ids)
+        new_index = index.add(rows, new_labels, ids=new_ids, inplace=inplace)
         labels2 = np.concatenate([np.asarray(pred_categories).astype(np.int64), new_labels])
         nav2 = pd.concat([nav_old, nav_new])
         nav2["category"] = labels2                     # what search() writes (:67)
@@ -438,13 +447,14 @@ class LearnedIndex(Logger):
         self._adopt(new_index, nav2, search2, labels2)
         return nav2, search2, labels2
 
-    def delete(self, data_navigation, data_search, pred_categories, ids):
+    def delete(self, data_navigation, data_search, pred_categories, ids, inplace=False):
         """Remove the objects with the given ids without a rebuild
         (DeviceIndex.remove); returns the frames and labels without them, as
-        `insert` does.  An unknown id raises KeyError."""
+        `insert` does.  An unknown id raises KeyError.  `inplace`: as
+        `insert` (DeviceIndex.remove(inplace=True))."""
         index = self._updatable_index(data_navigation, data_search, pred_categories)
         ids = np.asarray(ids).ravel()
-        new_index = index.remove(ids)
+        new_index = index.remove(ids, inplace=inplace)
         keep = ~np.isin(np.asarray(data_navigation.index), ids)
         nav2 = data_navigation[keep].copy()    # (search() writes its 'category' column)
         if hasattr(data_search, "index"):

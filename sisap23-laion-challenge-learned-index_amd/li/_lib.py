@@ -61,6 +61,11 @@ LMI_REBUCKET_MAX_BUCKETS = 1024
 LMI_REBUCKET_MAX_WAVES = 4096
 LMI_GATHER_MAX_GRID = 2048
 LMI_GATHER_TILE_ROWS = 32
+# K9 (lmi_index_move_rows_inplace): the direction of an in-place update and the
+# flag that copies staged slabs with hipMemcpyAsync (measurement)
+LMI_INPLACE_ADD = 1
+LMI_INPLACE_REMOVE = -1
+LMI_INPLACE_MEMCPY = 1
 
 # every symbol include/lmi_hip.h declares (tests check the export table)
 EXPORTS = (
@@ -95,6 +100,7 @@ EXPORTS = (
     "lmi_mlp_train_steps",
     "lmi_index_move_rows",
     "lmi_index_ingest_rows",
+    "lmi_index_move_rows_inplace",
     "lmi_bucket_sort_labels_ws_bytes",
     "lmi_bucket_sort_labels",
     "lmi_index_gather_rows",
@@ -223,6 +229,8 @@ _SIGNATURES = {
     "lmi_index_move_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P,
                                       _P]),
     "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "lmi_index_move_rows_inplace": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P,
+                                              _I32, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),
     "lmi_bucket_sort_labels": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
     "lmi_index_gather_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _P]),

@@ -65,6 +65,7 @@ class GraphedSearch:
         self.stop_mass, self.min_probes = stop_mass, min_probes
         s = searcher
         ix = s.index
+        ix._check_live()
         dev = ix.device
         lib = _lib.load()
         self.searcher, self.R, self.k, self.k_round = s, R, k, k_round
@@ -279,6 +280,7 @@ class GraphedSearch:
         launch replays).  False if it cannot be staged in the captured
         precision (clip768 values not fp16-representable under an fp16
         capture): run() then answers it on the eager path."""
+        self.searcher.index._check_live()
         nav = host_array(q_nav)
         qs = host_array(q_search)
         nq, d, dn, per, wq = self.nq, self.d, self.dn, self.per, self.wq
@@ -327,6 +329,7 @@ class GraphedSearch:
         """Replay the step (after staging a new batch, if given) -> (dists f64
         [nq, w], anns uint32 [nq, w])."""
         s = self.searcher
+        s.index._check_live()
         dev = s.index.device
         if self.graph is None and self._step is None:
             raise RuntimeError("GraphedSearch: run() after close()")
@@ -392,6 +395,7 @@ class GraphedSearch:
         ticket's answer is valid until the launch after next)."""
         if not self.pipeline:
             raise ValueError("launch() needs GraphedSearch(pipeline=True)")
+        self.searcher.index._check_live()
         slot = self._slot
         self._run_pipelined(self.searcher.index.device)
         return slot

@@ -21,6 +21,7 @@ every probed bucket whatever the bucket popularity.
 """
 from __future__ import annotations
 
+import bisect
 import ctypes as C
 import dataclasses
 import os
@@ -34,6 +35,11 @@ from . import _lib
 from ._lib import check, ptr
 
 DEFAULT_CHUNK_ROWS = 8192
+# In-place updates (K9): rows of a staged slab, the least rows of
+# a direct slab, and the cap on the staging buffer (the Infinity Cache's size)
+DEFAULT_SLAB_ROWS = 64 << 10
+DEFAULT_DIRECT_ROWS = 16 << 10
+STAGING_MAX_BYTES = 256 << 20
 SPLIT_D_PAD = 768  # the split mode's (storage "f32x") row width: the fp16 scan's
 
 
@@ -228,6 +234,84 @@ class BucketLayout:
         order[new_dst] = n_surv + np.arange(m, dtype=np.int64)
         return BucketLayout(C_, order, new_off), new_dst, surv_off, drop_before
 
+    def inplace_slabs(self, new_off, drop, slab_rows: int, direct_rows: int) -> np.ndarray:
+        """The plan of an update inside one buffer (lmi_index_move_rows_inplace):
+        int64 [k, 3] rows (a, b, staged) -- slabs [a, b) of this layout's
+        positions, in processing order.  `new_off`: the bucket offsets after
+        the update (updated()'s layout.bucket_off); `drop`: the ascending
+        dropped positions.  No drops: an add, every row moves right by its
+        bucket's new_off - bucket_off, which does not decrease along the
+        corpus; drops: a remove (no new rows), every survivor moves left by the
+        number of drops before it.
+
+        Rows that do not move are in no slab: an add's prefix up to and
+        including the first bucket that receives a row, a remove's prefix
+        before the first drop.  An add is cut from the end backwards, a remove
+        from the front forwards.  At the cursor the longest DIRECT slab is
+        taken -- its destinations lie outside [a, b): a + shift(a) >= b for an
+        add, dest(b - 1) < a for a remove -- when it has at least
+        `direct_rows` rows; otherwise a STAGED slab of at most `slab_rows`
+        rows.  Destinations of a slab then lie in its own range or in rows
+        earlier slabs have vacated, never in rows a later slab reads.
+        O(slabs * log) host arithmetic, no array over n."""
+        slab_rows, direct_rows = int(slab_rows), int(direct_rows)
+        if slab_rows < 1 or direct_rows < 1:
+            raise ValueError("slab_rows and direct_rows must be positive")
+        off = self.bucket_off
+        n = int(off[-1])
+        new_off = np.asarray(new_off, dtype=np.int64)
+        drop = np.asarray(drop, dtype=np.int64).ravel()
+        if new_off.shape != off.shape:
+            raise ValueError("new_off must have one entry per bucket offset")
+        out = []
+        if drop.size == 0:
+            shift = new_off[:-1] - off[:-1]
+            if (shift < 0).any() or (np.diff(shift) < 0).any():
+                raise ValueError("inplace_slabs: new_off is not this layout plus added rows")
+            moved = np.flatnonzero(shift > 0)
+            if n == 0 or moved.size == 0:
+                return np.zeros((0, 3), np.int64)
+            first = int(off[moved[0]])           # rows before it keep their place
+            # hi[c]: where the last row of bucket c lands (non-decreasing in c)
+            hi, lo, sh = (off[1:] - 1 + shift).tolist(), off[:-1].tolist(), shift.tolist()
+            e = n
+            while e > first:
+                c = bisect.bisect_left(hi, e)    # the first bucket with a row landing at or past e
+                a = max(lo[c], e - sh[c], first)
+                staged = e - a < direct_rows
+                if staged:
+                    a = max(first, e - slab_rows)
+                out.append((a, e, int(staged)))
+                e = a
+            return np.array(out, np.int64).reshape(-1, 3)
+        r = int(drop.size)
+        if (np.diff(drop) <= 0).any() or drop[0] < 0 or drop[-1] >= n:
+            raise ValueError(f"inplace_slabs: drop must be ascending, distinct and inside [0, {n})")
+        if int(new_off[-1]) != n - r:
+            raise ValueError("inplace_slabs: a remove in place takes no new rows")
+        n_surv = n - r
+        d = drop.tolist()
+        key = (drop - np.arange(r, dtype=np.int64)).tolist()   # survivors before each drop
+
+        def survivor(t):                         # position of the survivor of rank t
+            return t + bisect.bisect_right(key, t)
+
+        def next_survivor(s):                    # the first survivor at or after s (n: none)
+            t = s - bisect.bisect_left(d, s)
+            return survivor(t) if t < n_surv else n
+
+        s = next_survivor(d[0])
+        while s < n:
+            # (dest(i) = survivors before i: the last row with dest < s is the
+            # survivor of rank s - 1, at or after s as a drop lies before s)
+            b = survivor(s - 1) + 1 if s - 1 < n_surv else n
+            staged = b - s < direct_rows
+            if staged:
+                b = min(n, s + slab_rows)
+            out.append((s, b, int(staged)))
+            s = next_survivor(b)
+        return np.array(out, np.int64).reshape(-1, 3)
+
     @staticmethod
     def place_survivors(kept, surv_off, new_off, out) -> None:
         """out[new_off[c] + j] = kept[surv_off[c] + j], j < surv_off[c+1] -
@@ -295,10 +379,20 @@ class DeviceIndex:
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
     corpus32n = None  # corpus32 normalised as sklearn does in float32 (ABI 11)
     inv_norm32 = None  # 1/||y|| of corpus32 (the general scan's, k > 16 in f32x)
+    consumed = False   # True once an in-place update has taken this index's store (K9)
 
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
                  storage: str = "auto", chunk_rows: Optional[int] = None,
-                 rank: int = 0, world: int = 1, subcluster: bool = False):
+                 rank: int = 0, world: int = 1, subcluster: bool = False,
+                 capacity: Optional[int] = None):
+        """`capacity` (None: as many rows as the index holds, today's
+        allocation): the rows the corpus and 1/||y|| stores are allocated for,
+        so that add / remove with inplace=True can grow the index inside them
+        (K9).  `corpus` and `inv_norm` are the leading [n_rows] views of the
+        stores; rows past n_rows have unspecified content.  Only for the
+        kinds an update supports (one GPU, storage 'f16', no float64 rows, no
+        sub-cluster layout): ValueError otherwise, or when below the row
+        count."""
         _lib.load()
         self.device = torch.device(device if device is not None else "cuda")
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
@@ -316,6 +410,14 @@ class DeviceIndex:
         self.rank, self.world = rank, world
 
         gpos, loc_off = self.layout.shard(rank, world)
+        self._capacity = None
+        if capacity is not None:
+            if world > 1 or subcluster:
+                raise ValueError("capacity: only an index that add / remove support can reserve rows "
+                                 "(not a striped index, world > 1, nor a sub-cluster layout)")
+            if int(capacity) < n:
+                raise ValueError(f"capacity {int(capacity)} is below the {n} rows of the index")
+            self._capacity = int(capacity)
         if isinstance(data, RowSource):
             self._fill_from_source(data, gpos)
         else:
@@ -354,14 +456,88 @@ class DeviceIndex:
 
     # ---- updates (K7: csrc/lmi_update.hip) ----------------------
     @classmethod
-    def empty(cls, d: int, n_buckets: int, *, device=None, chunk_rows: Optional[int] = None) -> "DeviceIndex":
+    def empty(cls, d: int, n_buckets: int, *, device=None, chunk_rows: Optional[int] = None,
+              capacity: Optional[int] = None) -> "DeviceIndex":
         """A one-GPU fp16 index of `n_buckets` empty buckets for rows of `d`
         values, to be filled by `add`: what a construction over zero rows
-        gives."""
+        gives.  `capacity`: rows to reserve for add(..., inplace=True)."""
         if int(d) < 1:
             raise ValueError("d must be positive")
         return cls(np.zeros((0, int(d)), np.float16), np.zeros((0,), np.int64), n_buckets,
-                   device=device, storage="f16", chunk_rows=chunk_rows)
+                   device=device, storage="f16", chunk_rows=chunk_rows, capacity=capacity)
+
+    # ---- the row store (K9: reserved capacity; DESIGN.md §3) -------------------
+    def _alloc_store(self, n_rows: int, dtype=torch.float16, zero: bool = False, capacity=None):
+        """Allocate the corpus and 1/||y|| stores for max(capacity, n_rows)
+        rows (`capacity` default: the constructor's) and set `corpus` /
+        `inv_norm` to their leading [n_rows] views -- the stores themselves
+        when nothing is reserved."""
+        cap = self._capacity if capacity is None else capacity
+        cap = max(int(cap), n_rows) if cap is not None else n_rows
+        make = torch.zeros if zero else torch.empty
+        self._store = make((cap, self.d_pad), dtype=dtype, device=self.device)
+        self._store_inv = torch.empty((cap,), dtype=torch.float32, device=self.device)
+        self._capacity = cap
+        self.corpus, self.inv_norm = self._store[:n_rows], self._store_inv[:n_rows]
+
+    @property
+    def capacity(self) -> int:
+        """Rows the corpus store holds (n_rows when nothing is reserved)."""
+        return int(self._capacity)
+
+    def _check_live(self):
+        """Refuse a consumed index before anything is launched on it: its
+        store belongs to the index the in-place update returned, and its
+        offset tables are gone (a captured graph would replay over moved rows
+        through freed tables)."""
+        if self.consumed:
+            raise RuntimeError("this index was updated in place (add / remove with inplace=True) and "
+                               "is consumed: use the index that call returned "
+                               "(Searcher.with_index(new))")
+
+    def _consume(self):
+        """Drop the device arrays and mark the index consumed."""
+        self.consumed = True
+        for name in ("corpus", "inv_norm", "_store", "_store_inv", "gpos", "bucket_off_local",
+                     "bucket_rows", "chunk_first", "_desc", "_desc32"):
+            setattr(self, name, None)
+        self._ws = {}
+
+    def reserve(self, rows: int) -> "DeviceIndex":
+        """A NEW index with the same content on a store of `rows` rows (the
+        one copying step for an index built without a capacity; this index is
+        not touched).  ValueError when `rows` is below the row count."""
+        self._check_live()
+        self._check_updatable()
+        if int(rows) < self.n_rows:
+            raise ValueError(f"reserve: {int(rows)} rows are below the {self.n_rows} rows of the index")
+        new = self._successor(self.layout, self.pos_to_id, int(rows))
+        new.corpus.copy_(self.corpus)
+        new.inv_norm.copy_(self.inv_norm)
+        torch.cuda.current_stream(self.device).synchronize()
+        return new
+
+    def _successor(self, layout, pos_to_id, capacity: int) -> "DeviceIndex":
+        """A one-GPU fp16 index over `layout` / `pos_to_id` with this one's
+        shape and chunk rule: every table, and fresh stores of `capacity`
+        rows (or more, when the layout holds more) whose rows the caller
+        writes."""
+        n_new = int(layout.bucket_off[-1])
+        new = object.__new__(DeviceIndex)
+        new.device, new.layout, new.n_buckets = self.device, layout, layout.n_buckets
+        new.n_total = new.n_rows = n_new
+        new.rank, new.world = 0, 1
+        new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
+        new.pos_to_id = pos_to_id
+        new.bucket_size = layout.bucket_size.copy()
+        new._plan_tables(layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
+        new.gpos = torch.arange(n_new, dtype=torch.int32, device=self.device)
+        new.chunk_centroid = None
+        new._ws = {}
+        if capacity is not None:
+            new._alloc_store(n_new, capacity=capacity)
+            new._desc = IndexDescHolder(new)
+        return new
 
     def _check_updatable(self):
         """What add / remove support, refused before any device work."""
@@ -377,7 +553,8 @@ class DeviceIndex:
             raise ValueError("index update: an index with a sub-cluster layout (chunk_centroid) is "
                              "not supported")
 
-    def add(self, rows, labels, ids=None) -> "DeviceIndex":
+    def add(self, rows, labels, ids=None, *, inplace: bool = False, slab_rows: Optional[int] = None,
+            direct_rows: Optional[int] = None, timings: Optional[dict] = None) -> "DeviceIndex":
         """A NEW index with the batch appended to the row sequence: every row
         goes to the end of the bucket `labels` names for it (host or device
         integers), in batch order -- bitwise the index a construction from
@@ -385,7 +562,26 @@ class DeviceIndex:
         is not touched.  `rows`: host or device, [m, d] fp16, or fp32 whose
         values are fp16-exact (ValueError otherwise).  `ids` default to the
         ids after the largest one present; ids that repeat or are present
-        already raise ValueError."""
+        already raise ValueError.
+
+        inplace=True (K9): the rows move inside this index's own store, which
+        the returned index takes over (same corpus.data_ptr()); no second
+        corpus is allocated.  The result is the same index, bit for bit.  THIS
+        index is consumed: `consumed` becomes True, its device arrays are
+        dropped and everything that would launch on it raises RuntimeError --
+        go on with Searcher.with_index(new).  Needs n_rows + m <= capacity
+        (ValueError otherwise: build with `capacity`, or `reserve`).  Every
+        refusal comes before the first row moves and leaves this index in
+        use, unchanged.  The call waits for the whole device before it moves
+        a row (replays queued on other streams have finished) and again
+        before it returns.  `slab_rows`, `direct_rows`: the slab plan's tuning
+        (BucketLayout.inplace_slabs; defaults DEFAULT_SLAB_ROWS capped to a
+        STAGING_MAX_BYTES staging buffer, DEFAULT_DIRECT_ROWS).  `timings`
+        (measurement only): a dict that receives 'move_ms' (device events
+        around the row moves), 'moved_rows' and, in place, 'direct_slabs',
+        'staged_slabs', 'staged_rows' (of moved_rows) and 'staging_rows' (the
+        staging buffer's)."""
+        self._check_live()
         self._check_updatable()
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
         lab = lab.astype(np.int64, copy=False).ravel()
@@ -403,12 +599,17 @@ class DeviceIndex:
             raise ValueError("duplicate ids among the new rows")
         if m and np.isin(self.pos_to_id, ids).any():
             raise ValueError("ids of new rows are already in the index")
-        return self._updated(np.zeros(0, np.int64), rows, lab, ids)
+        return self._updated(np.zeros(0, np.int64), rows, lab, ids, inplace=inplace,
+                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
 
-    def remove(self, ids) -> "DeviceIndex":
+    def remove(self, ids, *, inplace: bool = False, slab_rows: Optional[int] = None,
+               direct_rows: Optional[int] = None, timings: Optional[dict] = None) -> "DeviceIndex":
         """A NEW index without the rows of `ids` (this index is not touched):
         bitwise the index a construction from scratch over the remaining rows
-        gives.  An id that is not in the index raises KeyError."""
+        gives.  An id that is not in the index raises KeyError.  inplace=True
+        and the other keywords: as `add` -- the survivors move left inside
+        this index's store and this index is consumed."""
+        self._check_live()
         self._check_updatable()
         ids = np.asarray(ids).astype(np.int64, copy=False).ravel()
         uniq = np.unique(ids)
@@ -419,7 +620,8 @@ class DeviceIndex:
             missing = np.setdiff1d(uniq, self.pos_to_id[drop])
             raise KeyError(f"ids not in the index: {missing[:8].tolist()}"
                            + (" ..." if missing.size > 8 else ""))
-        return self._updated(drop, None, np.zeros(0, np.int64), np.zeros(0, np.int64))
+        return self._updated(drop, None, np.zeros(0, np.int64), np.zeros(0, np.int64), inplace=inplace,
+                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
 
     # ---- re-bucket (K8: csrc/lmi_rebucket.hip) ------------------
     @staticmethod
@@ -465,6 +667,7 @@ class DeviceIndex:
         pos_to_id tables and downloads the new ones.  This index is not
         touched.  `timings` (measurement only): a dict that receives the
         seconds spent in 'sort', 'tables', 'gather' and 'host'."""
+        self._check_live()
         self._check_updatable()
         C_ = self.n_buckets if n_buckets is None else int(n_buckets)
         if C_ < 1:
@@ -504,8 +707,7 @@ class DeviceIndex:
         new.n_total = new.n_rows = n
         new.rank, new.world = 0, 1
         new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
-        new.corpus = torch.empty((n, self.d_pad), dtype=torch.float16, device=dev)
-        new.inv_norm = torch.empty((n,), dtype=torch.float32, device=dev)
+        new._alloc_store(n, capacity=self.capacity)   # (a reserved index stays reserved)
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
         check("lmi_index_gather_rows", lib.lmi_index_gather_rows(
             ptr(self.corpus), ptr(self.inv_norm), n, self.d_pad, ptr(src_pos), ptr(new.corpus),
@@ -543,54 +745,130 @@ class DeviceIndex:
         return rows if rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1] else rows.contiguous()
 
     @torch.no_grad()
-    def _updated(self, drop, rows, lab, ids) -> "DeviceIndex":
+    def _updated(self, drop, rows, lab, ids, *, inplace=False, slab_rows=None, direct_rows=None,
+                 timings=None) -> "DeviceIndex":
         """The index after dropping the global positions `drop` (ascending)
         and appending the batch: host tables by index arithmetic
-        (BucketLayout.updated), rows by the K7 kernels into new buffers."""
+        (BucketLayout.updated), rows by the K7 kernels into new stores -- or,
+        `inplace`, by the K9 chain inside this index's own."""
         lib = _lib.load()
-        layout, new_dst, surv_off, drop_before = self.layout.updated(drop, lab)
         m, r = int(lab.size), int(drop.size)
         n_old, n_new = self.n_rows, self.n_rows - r + m
-        new = object.__new__(DeviceIndex)
-        new.device, new.layout, new.n_buckets = self.device, layout, self.n_buckets
-        new.n_total = new.n_rows = n_new
-        new.rank, new.world = 0, 1
-        new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
+        if inplace and n_new > self.capacity:
+            raise ValueError(f"index update in place: {n_new} rows exceed the capacity of "
+                             f"{self.capacity} rows (build the index with `capacity`, or `reserve`)")
+        layout, new_dst, surv_off, drop_before = self.layout.updated(drop, lab)
+        dev = self.device
+        s = _lib.stream_handle(dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        tmp = None
+        if inplace and m:
+            # the batch first, into a temporary [m, d_pad] buffer: its status
+            # word is read before any row of the store moves
+            x = self._batch_rows(rows)
+            tmp = torch.empty((m, self.d_pad), dtype=torch.float16, device=dev)
+            tmp_inv = torch.empty((m,), dtype=torch.float32, device=dev)
+            seq = torch.arange(m, dtype=torch.int64, device=dev)
+            check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
+                ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
+                self.d, self.d_pad, ptr(seq), ptr(tmp), ptr(tmp_inv), m, ptr(status), s))
+            st = int(status.item())
+            if st & _lib.LMI_STATUS_ROWS_NOT_F16:
+                raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
+            if st:
+                raise RuntimeError(f"index update: internal status {st} (the index is unchanged)")
+            del x, tmp_inv, seq
         p2id = np.empty(n_new, np.int64)
         BucketLayout.place_survivors(np.delete(self.pos_to_id, drop) if r else self.pos_to_id, surv_off,
                                      layout.bucket_off, p2id)
         p2id[new_dst] = ids
-        new.pos_to_id = p2id
-        new.bucket_size = layout.bucket_size.copy()
-        new._plan_tables(layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
-        new.gpos = torch.arange(n_new, dtype=torch.int32, device=self.device)
-        new.chunk_centroid = None
-        dev = self.device
-        new.corpus = torch.empty((n_new, self.d_pad), dtype=torch.float16, device=dev)
-        new.inv_norm = torch.empty((n_new,), dtype=torch.float32, device=dev)
-        status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        s = _lib.stream_handle(dev)
-        if n_old - r > 0:
-            d_drop = torch.from_numpy(drop.astype(np.int64)).to(dev) if r else None
-            d_before = torch.from_numpy(drop_before).to(dev) if r else None
-            check("lmi_index_move_rows", lib.lmi_index_move_rows(
-                ptr(self.corpus), ptr(self.inv_norm), n_old, self.d_pad, ptr(self.bucket_off_local),
-                ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
-                ptr(new.corpus), ptr(new.inv_norm), n_new, ptr(status), s))
+        new = self._successor(layout, p2id, None if inplace else max(self.capacity, n_new))
+        ev = None
+        if timings is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        d_drop = torch.from_numpy(drop.astype(np.int64)).to(dev) if r else None
+        d_before = torch.from_numpy(drop_before).to(dev) if r else None
+        d_dst = torch.from_numpy(new_dst).to(dev) if m else None
+        if not inplace:
+            if ev:
+                ev[0].record()
+            if n_old - r > 0:
+                check("lmi_index_move_rows", lib.lmi_index_move_rows(
+                    ptr(self.corpus), ptr(self.inv_norm), n_old, self.d_pad, ptr(self.bucket_off_local),
+                    ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
+                    ptr(new.corpus), ptr(new.inv_norm), n_new, ptr(status), s))
+            if ev:
+                ev[1].record()
+            if m:
+                x = self._batch_rows(rows)
+                check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
+                    ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
+                    self.d, self.d_pad, ptr(d_dst), ptr(new.corpus), ptr(new.inv_norm), n_new,
+                    ptr(status), s))
+            st = int(status.item())  # (waits for both kernels: the inputs above stay alive until here)
+            if st & _lib.LMI_STATUS_ROWS_NOT_F16:
+                raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
+            if st:
+                raise RuntimeError(f"index update: internal status {st}")
+            if ev:
+                timings["move_ms"] = ev[0].elapsed_time(ev[1])
+                timings["moved_rows"] = n_old - r
+            return new
+        # ---- in place (K9): the slab plan, then the whole chain in one call ----
+        row_bytes = 2 * self.d_pad + 4
+        if slab_rows is None:
+            slab_rows = max(1, min(DEFAULT_SLAB_ROWS, STAGING_MAX_BYTES // row_bytes))
+        if direct_rows is None:
+            direct_rows = DEFAULT_DIRECT_ROWS
+        slabs = np.ascontiguousarray(self.layout.inplace_slabs(layout.bucket_off, drop, slab_rows,
+                                                               direct_rows))
+        staged = slabs[slabs[:, 2] == 1]
+        stage_rows = int((staged[:, 1] - staged[:, 0]).max()) if staged.size else 0
+        stage = stage_inv = None
+        if stage_rows:
+            stage = torch.empty((stage_rows, self.d_pad), dtype=torch.float16, device=dev)
+            stage_inv = torch.empty((stage_rows,), dtype=torch.float32, device=dev)
+        store, store_inv, cap = self._store, self._store_inv, self.capacity
+        old_off = self.bucket_off_local
+        # everything queued on the device (replays on other streams that read
+        # this index) finishes before the first row moves
+        torch.cuda.synchronize(dev)
+        if ev:
+            ev[0].record()
+        rc = lib.lmi_index_move_rows_inplace(
+            ptr(store), ptr(store_inv), n_old, n_new, cap, self.d_pad, ptr(old_off),
+            ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
+            _lib.LMI_INPLACE_REMOVE if r else _lib.LMI_INPLACE_ADD, slabs.ctypes.data,
+            int(slabs.shape[0]), ptr(stage), ptr(stage_inv), stage_rows,
+            _lib.LMI_INPLACE_MEMCPY if os.environ.get("LMI_INPLACE_MEMCPY") == "1" else 0,
+            ptr(status), s)
+        if rc == _lib.LMI_E_INVALID:
+            check("lmi_index_move_rows_inplace", rc)  # (refused on the host: nothing was launched)
+        # from here on rows may have moved: this object must not launch again
+        self._consume()
+        check("lmi_index_move_rows_inplace", rc)
+        if ev:
+            ev[1].record()
         if m:
-            x = self._batch_rows(rows)
-            d_dst = torch.from_numpy(new_dst).to(dev)
+            # the batch, from the temporary to its places behind the moved rows
             check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
-                ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
-                self.d, self.d_pad, ptr(d_dst), ptr(new.corpus), ptr(new.inv_norm), n_new,
-                ptr(status), s))
-        st = int(status.item())  # (waits for both kernels: the inputs above stay alive until here)
-        if st & _lib.LMI_STATUS_ROWS_NOT_F16:
-            raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
+                ptr(tmp), _lib.LMI_F16, m, self.d_pad, self.d, self.d_pad, ptr(d_dst), ptr(store),
+                ptr(store_inv), n_new, ptr(status), s))
+        st = int(status.item())  # (waits for the chain: the buffers above stay alive until here)
+        torch.cuda.synchronize(dev)
         if st:
-            raise RuntimeError(f"index update: internal status {st}")
+            raise RuntimeError(f"index update in place: internal status {st}; the index is consumed "
+                               "and the content of its store is undefined")
+        new._store, new._store_inv, new._capacity = store, store_inv, cap
+        new.corpus, new.inv_norm = store[:n_new], store_inv[:n_new]
         new._desc = IndexDescHolder(new)
-        new._ws = {}
+        if ev:
+            timings["move_ms"] = ev[0].elapsed_time(ev[1])
+            timings["direct_slabs"] = int((slabs[:, 2] == 0).sum())
+            timings["staged_slabs"] = int((slabs[:, 2] == 1).sum())
+            timings["moved_rows"] = int((slabs[:, 1] - slabs[:, 0]).sum())
+            timings["staged_rows"] = int((staged[:, 1] - staged[:, 0]).sum())
+            timings["staging_rows"] = stage_rows
         return new
 
     @torch.no_grad()
@@ -639,8 +917,11 @@ class DeviceIndex:
         self.storage = storage
         tdt = torch.float32 if storage == "f32" else torch.float16
         n_rows = int(gpos.size)
-        self.corpus = torch.zeros((n_rows, self.d_pad), dtype=tdt, device=self.device)
-        self.inv_norm = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
+        if self._capacity is not None and (storage != "f16" or src64 is not None):
+            raise ValueError("capacity: only an index that add / remove support can reserve rows "
+                             f"(storage 'f16' without float64 rows; this one is {storage!r}"
+                             + (" with corpus64)" if src64 is not None else ")"))
+        self._alloc_store(n_rows, tdt, zero=True)
         if storage == "f32x":
             self.corpus32 = torch.zeros((n_rows, self.d_pad), dtype=torch.float32, device=self.device)
             self.inv_norm32 = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
@@ -685,8 +966,7 @@ class DeviceIndex:
         self.d_pad = (self.d + 31) // 32 * 32
         self.storage = "f16"
         n_rows = int(gpos.size)
-        self.corpus = torch.zeros((n_rows, self.d_pad), dtype=torch.float16, device=self.device)
-        self.inv_norm = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
+        self._alloc_store(n_rows, torch.float16, zero=True)
         slot = torch.full((n,), -1, dtype=torch.int64, device=self.device)
         slot[torch.from_numpy(self.layout.order[gpos]).to(self.device)] = torch.arange(
             n_rows, dtype=torch.int64, device=self.device)
@@ -759,6 +1039,7 @@ class DeviceIndex:
 
     @property
     def desc(self) -> _lib.IndexDesc:
+        self._check_live()
         return self._desc.desc
 
     def desc_for(self, k: int) -> _lib.IndexDesc:
@@ -1244,7 +1525,9 @@ class Searcher:
     def with_index(self, index: DeviceIndex) -> "Searcher":
         """A Searcher over `index` (e.g. the result of DeviceIndex.add /
         remove) with this one's router and group; its device tables are its
-        own, so this Searcher keeps answering from its own index."""
+        own, so this Searcher keeps answering from its own index -- unless the
+        update was made in place: this Searcher's index is then consumed and
+        every search on it raises RuntimeError."""
         return Searcher(index, self.router, self.group, exchange=self.exchange)
 
     def _host(self, name, shape, dtype):
@@ -1336,6 +1619,7 @@ class Searcher:
         `stop_mass`, `min_probes`: the router's stop rule (DeviceRouter.topr);
         a dropped probe's list is (+inf, -1)."""
         check_stop(stop_mass, min_probes)
+        self.index._check_live()
         if classes is None:
             classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
@@ -1415,6 +1699,7 @@ class Searcher:
         ms; the stages are then separated by stream synchronisations."""
         import time
         check_stop(stop_mass, min_probes)
+        self.index._check_live()
         if replay_on not in ("device", "host"):
             raise ValueError("replay_on must be 'device' or 'host'")
         if semantics not in ("reference", "exact"):

@@ -194,6 +194,7 @@ class StreamedSearch:
         self.stop_mass, self.min_probes = stop_mass, min_probes
         s = searcher
         ix = s.index
+        ix._check_live()
         dev = ix.device
         lib = _lib.load()
         self.searcher, self.R, self.k, self.k_round = s, R, k, k_round
@@ -550,6 +551,7 @@ class StreamedSearch:
         value of the block is not fp16-representable: the block still goes
         in, flagged, and the launch that finishes the batch raises
         QueryNotF16 on every rank (stream() then answers it eagerly)."""
+        self.searcher.index._check_live()
         nav, qs = host_array(q_nav), host_array(q_search)
         nq, d, dn, per = self.nq, self.d, self.dn, self.per
         if nav.shape != (nq, dn) or qs.shape != (nq, d):
@@ -591,6 +593,7 @@ class StreamedSearch:
         """Fill the pipeline with the staged rows of slots 1, 2 and 3 (eagerly:
         slot 1 up to its scan, slots 2 and 3 up to their plans): the next
         launch answers slot 1."""
+        self.searcher.index._check_live()
         dev = self.searcher.index.device
         for j, upto in ((1, "S"), (2, "P"), (3, "P")):
             self._fill(j, upto)
@@ -670,6 +673,7 @@ class StreamedSearch:
         onto the finish stream behind F."""
         if self._closed:
             raise RuntimeError("StreamedSearch: step() after close()")
+        self.searcher.index._check_live()
         if self._t is None:
             self.prime()
         dev = self.searcher.index.device
