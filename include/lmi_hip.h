@@ -565,6 +565,10 @@ int lmi_mlp_train_steps(const lmi_mlp_train_desc* desc, const float* x, int64_t 
  * outside [0, n_new) is skipped and LMI_STATUS_INTERNAL raised.  Additions:
  * LMI_ABI_VERSION does not change. */
 #define LMI_STATUS_ROWS_NOT_F16 4 /* lmi_index_ingest_rows: a float32 value is not fp16-exact */
+#define LMI_STATUS_ROWS_LOW_NORM 16 /* lmi_index_ingest_rows: a stored row's norm lies in
+                                     * [10 eps(float64), 10 eps(float32)): a note, not an error --
+                                     * the float64 mode scores it with its true 1/||y||
+                                     * (li.index.DeviceIndex.inv_norm64) */
 /* Old row i of bucket c (old_off[c] <= i < old_off[c+1]) goes to
  *   new_off[c] + (i - old_off[c]) - #{dropped rows of bucket c before i},
  * its 1/||y|| with it; a dropped row goes nowhere.
@@ -587,7 +591,9 @@ int lmi_index_move_rows(const void* src_corpus, const float* src_inv_norm, int64
  * the STORED values: the norm in float64, norms below 10 eps(float32) taken
  * as 1, one rounding to float32 (li.index._inv_norm).  A float32 value that
  * does not round-trip through fp16 raises LMI_STATUS_ROWS_NOT_F16 (the
- * rounded value is stored; the caller discards the buffers). */
+ * rounded value is stored; the caller discards the buffers).  A stored row
+ * whose norm is below 10 eps(float32) but not below 10 eps(float64) raises
+ * LMI_STATUS_ROWS_LOW_NORM (the row and its 1/||y|| = 1 are stored as usual). */
 int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m, int64_t ld, int32_t d,
                           int32_t d_pad, const int64_t* new_dst, void* dst_corpus,
                           float* dst_inv_norm, int64_t n_new, int32_t* status, void* stream);

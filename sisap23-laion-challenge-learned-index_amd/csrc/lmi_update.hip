@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_rows_kernel(
     const int64_t wave0 = (int64_t)blockIdx.x * (kIngestThreads / 64) + (threadIdx.x >> 6);
     const int64_t n_waves = (int64_t)gridDim.x * (kIngestThreads / 64);
     const int32_t pieces = d_pad / 8;
-    bool inexact = false;
+    bool inexact = false, low_norm = false;
     for (int64_t j = wave0; j < m; j += n_waves) {
         const int64_t to = new_dst[j];
         if (to < 0 || to >= n_new) {
@@ -186,11 +186,17 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_rows_kernel(
         acc = wave_sum(acc);
         if (lane == 0) {
             double norm = sqrt(acc);
-            if (norm < 10.0 * 0x1p-23) norm = 1.0;
+            if (norm < 10.0 * 0x1p-23) {
+                // under the float32 rule but not under the float64 one: the
+                // float64 mode needs this row's true 1/||y|| (inv_norm64)
+                low_norm |= norm >= 10.0 * 0x1p-52;
+                norm = 1.0;
+            }
             dst_inv[to] = (float)(1.0 / norm);
         }
     }
     if (inexact) atomicOr(status, LMI_STATUS_ROWS_NOT_F16);
+    if (low_norm) atomicOr(status, LMI_STATUS_ROWS_LOW_NORM);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

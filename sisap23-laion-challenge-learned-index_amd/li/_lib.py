@@ -29,6 +29,7 @@ LMI_STATUS_QUERY_NOT_F16 = 1
 LMI_STATUS_INTERNAL = 2
 LMI_STATUS_ROWS_NOT_F16 = 4
 LMI_STATUS_BAD_LABEL = 8
+LMI_STATUS_ROWS_LOW_NORM = 16
 
 LMI_F32 = 0
 LMI_F16 = 1

@@ -98,6 +98,16 @@ def _inv_norm(rows: torch.Tensor) -> torch.Tensor:
     return (1.0 / norm).float()
 
 
+def _low_norm(rows: torch.Tensor):
+    """(mask, 1/||y|| float32) of the rows whose float64 norm lies in
+    [10 eps(float64), 10 eps(float32)): _inv_norm scores them with norm 1 (the
+    float32 rule), the reference's float64 branch with their true norm."""
+    f = rows.double()
+    norm = torch.sqrt((f * f).sum(dim=1))
+    low = (norm < 10 * float(np.finfo(np.float32).eps)) & (norm >= 10 * float(np.finfo(np.float64).eps))
+    return low, (1.0 / torch.where(low, norm, torch.ones_like(norm))).float()
+
+
 def refine_eps(d_pad: int, f16math: bool, rounded_inputs: bool = False) -> float:
     """The float64 mode's band ε (lmi_bucket_topk_f64): a bound on |d32 - d64|
     for every (query, row), d32 the scan's float32 distance and d64 the
@@ -112,7 +122,14 @@ def refine_eps(d_pad: int, f16math: bool, rounded_inputs: bool = False) -> float
       1/||q|| prep_kernel: per lane 4 * ceil(d_pad/256) fmaf terms, then a
             6-level butterfly: gamma(2 h_q)/2 for the sqrt of the sum, + 4u for
             sqrt and division (<= 2 ulp each);
-      1/||y|| float64 norm rounded once (_inv_norm): u;
+      1/||y|| float64 norm rounded once (_inv_norm): u -- of the row's true
+            norm: the float64 mode reads DeviceIndex.inv_norm64 where a stored
+            row's norm is under the float32 zero rule and not under the float64
+            one (with inv_norm's 1 such a row's d32 would be ~1 whatever its
+            direction, off by up to 2).  Nothing else changes for such rows:
+            fp16 products are exact in float32 down to subnormal x subnormal
+            (2^-48), and 1/norm <= 1 / (10 eps64) = 4.6e14 (1.7e7 for fp16
+            rows, whose smallest non-zero norm is 2^-24) is a normal float32;
       scale (1/||q||)(1/||y||) one multiply: 2u; the final fma: 2u absolute.
     rounded_inputs: float64 rows or queries scanned after rounding to float32
     (lmi_index_desc.corpus64, lmi_bucket_topk_f64q): the cosine of the rounded
@@ -379,6 +396,10 @@ class DeviceIndex:
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
     corpus32n = None  # corpus32 normalised as sklearn does in float32 (ABI 11)
     inv_norm32 = None  # 1/||y|| of corpus32 (the general scan's, k > 16 in f32x)
+    # inv_norm with the true 1/||y|| of the rows whose norm lies in [10 eps64,
+    # 10 eps32), for the float64 calls; None when no stored row does (_low_norm)
+    inv_norm64 = None
+    _desc64 = None
     consumed = False   # True once an in-place update has taken this index's store (K9)
 
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
@@ -499,7 +520,7 @@ class DeviceIndex:
         """Drop the device arrays and mark the index consumed."""
         self.consumed = True
         for name in ("corpus", "inv_norm", "_store", "_store_inv", "gpos", "bucket_off_local",
-                     "bucket_rows", "chunk_first", "_desc", "_desc32"):
+                     "bucket_rows", "chunk_first", "_desc", "_desc32", "inv_norm64", "_desc64"):
             setattr(self, name, None)
         self._ws = {}
 
@@ -514,6 +535,8 @@ class DeviceIndex:
         new = self._successor(self.layout, self.pos_to_id, int(rows))
         new.corpus.copy_(self.corpus)
         new.inv_norm.copy_(self.inv_norm)
+        if self.inv_norm64 is not None:
+            new.inv_norm64 = self.inv_norm64.clone()
         torch.cuda.current_stream(self.device).synchronize()
         return new
 
@@ -715,6 +738,8 @@ class DeviceIndex:
         st = int(status.item())  # (waits for the kernel: src_pos stays alive until here)
         if st:
             raise RuntimeError(f"index relabel: internal status {st}")
+        if self.inv_norm64 is not None:
+            new._set_inv_norm64()
         mark("gather")
         new.layout = BucketLayout(C_, order.cpu().numpy(), off.cpu().numpy())
         new.pos_to_id = p2id.cpu().numpy()
@@ -762,6 +787,10 @@ class DeviceIndex:
         s = _lib.stream_handle(dev)
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
         tmp = None
+        # the successor needs an inv_norm64 only when this index has one or the
+        # batch brings such a row (the ingest's LMI_STATUS_ROWS_LOW_NORM): an
+        # update of an index without them launches and reads nothing more
+        low64 = self.inv_norm64 is not None
         if inplace and m:
             # the batch first, into a temporary [m, d_pad] buffer: its status
             # word is read before any row of the store moves
@@ -775,7 +804,7 @@ class DeviceIndex:
             st = int(status.item())
             if st & _lib.LMI_STATUS_ROWS_NOT_F16:
                 raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
-            if st:
+            if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
                 raise RuntimeError(f"index update: internal status {st} (the index is unchanged)")
             del x, tmp_inv, seq
         p2id = np.empty(n_new, np.int64)
@@ -808,8 +837,10 @@ class DeviceIndex:
             st = int(status.item())  # (waits for both kernels: the inputs above stay alive until here)
             if st & _lib.LMI_STATUS_ROWS_NOT_F16:
                 raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
-            if st:
+            if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
                 raise RuntimeError(f"index update: internal status {st}")
+            if low64 or st & _lib.LMI_STATUS_ROWS_LOW_NORM:
+                new._set_inv_norm64()
             if ev:
                 timings["move_ms"] = ev[0].elapsed_time(ev[1])
                 timings["moved_rows"] = n_old - r
@@ -856,11 +887,13 @@ class DeviceIndex:
                 ptr(store_inv), n_new, ptr(status), s))
         st = int(status.item())  # (waits for the chain: the buffers above stay alive until here)
         torch.cuda.synchronize(dev)
-        if st:
+        if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
             raise RuntimeError(f"index update in place: internal status {st}; the index is consumed "
                                "and the content of its store is undefined")
         new._store, new._store_inv, new._capacity = store, store_inv, cap
         new.corpus, new.inv_norm = store[:n_new], store_inv[:n_new]
+        if low64 or st & _lib.LMI_STATUS_ROWS_LOW_NORM:
+            new._set_inv_norm64()
         new._desc = IndexDescHolder(new)
         if ev:
             timings["move_ms"] = ev[0].elapsed_time(ev[1])
@@ -945,6 +978,8 @@ class DeviceIndex:
             self.corpus[a:a + step, : self.d] = blk.to(tdt)
             self.inv_norm[a:a + step] = _inv_norm(blk.to(tdt))
             del blk, f
+        if storage != "f32x":
+            self._set_inv_norm64()
         if storage == "f32x" and self.d % 16 == 0 and os.environ.get("LMI_SPLIT_NORM32", "1") != "0":
             # every row divided by its float32 norm as the reference's
             # normalize(Y) computes it, once (lmi_index_desc.corpus32n): the
@@ -981,6 +1016,26 @@ class DeviceIndex:
             self.inv_norm[dst] = _inv_norm(x)
             del blk, x
         del slot
+        self._set_inv_norm64()
+
+    @torch.no_grad()
+    def _set_inv_norm64(self):
+        """inv_norm64 from the stored rows (storage 'f16' / 'f32'): None, or
+        a copy of inv_norm in which the rows _low_norm finds hold their true
+        1/||y||.  Such a row's inv_norm is exactly 1, so only the rows with
+        that value are read again.  A function of the stored values alone: an
+        update that calls this gets the table of the index built from
+        scratch."""
+        self.inv_norm64 = self._desc64 = None
+        cand = torch.nonzero(self.inv_norm == 1.0).flatten()
+        step = 1 << 16
+        for a in range(0, int(cand.numel()), step):
+            at = cand[a:a + step]
+            low, inv = _low_norm(self.corpus.index_select(0, at))
+            if bool(low.any()):
+                if self.inv_norm64 is None:
+                    self.inv_norm64 = self.inv_norm.clone()
+                self.inv_norm64[at[low]] = inv[low]
 
     @torch.no_grad()
     def _subcluster_layout(self, loc_off, cf, iters: int = 8, seed: int = 1):
@@ -1027,7 +1082,7 @@ class DeviceIndex:
                 self.gpos[a:b] = self.gpos[a:b][order]
                 # the row arrays that share corpus's local row index (the
                 # split mode's float32 rows, the float64 rows) move with it
-                for name in ("corpus32", "corpus32n", "inv_norm32", "corpus64"):
+                for name in ("corpus32", "corpus32n", "inv_norm32", "corpus64", "inv_norm64"):
                     t = getattr(self, name)
                     if t is not None:
                         t[a:b] = t[a:b][order]
@@ -1042,11 +1097,17 @@ class DeviceIndex:
         self._check_live()
         return self._desc.desc
 
-    def desc_for(self, k: int) -> _lib.IndexDesc:
+    def desc_for(self, k: int, f64: bool = False) -> _lib.IndexDesc:
         """The descriptor a call with k entries per list takes: the split mode
         (storage "f32x") holds k <= LMI_MAX_K; wider lists scan the float32
         rows with the general exact-fp32 kernel (a second descriptor over
-        corpus32)."""
+        corpus32).  `f64` (the lmi_bucket_topk_f64* calls): the descriptor
+        over inv_norm64 in place of inv_norm, where the index keeps one."""
+        if f64 and self.inv_norm64 is not None:
+            self._check_live()
+            if self._desc64 is None:
+                self._desc64 = IndexDescHolder(self, inv_norm=self.inv_norm64)
+            return self._desc64.desc
         if self.storage != "f32x" or k <= _lib.LMI_MAX_K:
             return self.desc
         if getattr(self, "_desc32", None) is None:
@@ -1064,14 +1125,14 @@ class DeviceIndex:
 
 
 class IndexDescHolder:
-    def __init__(self, ix: DeviceIndex, general32: bool = False):
+    def __init__(self, ix: DeviceIndex, general32: bool = False, inv_norm=None):
         d = _lib.IndexDesc()
         d.corpus = ptr(ix.corpus32 if general32 else ix.corpus)
         d.dtype = _lib.LMI_F32 if (general32 or ix.storage == "f32") else _lib.LMI_F16
         d.d = ix.d
         d.d_pad = ix.d_pad
         d.n_rows = ix.n_rows
-        d.inv_norm = ptr(ix.inv_norm32 if general32 else ix.inv_norm)
+        d.inv_norm = ptr(inv_norm if inv_norm is not None else ix.inv_norm32 if general32 else ix.inv_norm)
         d.gpos = ptr(ix.gpos)
         d.n_buckets = ix.n_buckets
         d.bucket_off = ptr(ix.bucket_off_local)
@@ -1309,7 +1370,7 @@ def bucket_topk_f64(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, 
         status = torch.zeros((1,), dtype=torch.int32, device=index.device)
     else:
         out_d, out_pos, status = out
-    desc = index.desc_for(k)
+    desc = index.desc_for(k, f64=True)
     need = lib.lmi_scan_f64_workspace_bytes(C.byref(desc), nq, R, k, qmode)
     if ws is None:
         ws = index._ws.get("f64")

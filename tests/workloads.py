@@ -92,6 +92,59 @@ def float64_inputs(w, seed, rel=2e-10):
     return x64, q64
 
 
+def pow2_scaled(a, rng, lo, hi):
+    """`a` with every row multiplied by 2^e, e drawn per row from [lo, hi]
+    with the generator `rng`: exact in the array's format as long as nothing
+    leaves its range, which is asserted.  Returns (scaled, e)."""
+    e = rng.integers(lo, hi + 1, a.shape[0])
+    out = np.ldexp(a, e[:, None]).astype(a.dtype)
+    assert np.array_equal(np.ldexp(out.astype(np.float64), -e[:, None]), a.astype(np.float64))
+    return out, e
+
+
+def subnormal_scaled(w, s):
+    """The workload's rows, and every other query, times 2^-s and rounded to
+    fp16 (float32 arrays of fp16 values): at s = 10 most components of a
+    unit row of 768 values are fp16 subnormals (below 2^-14), at s = 17 all."""
+    x = (w["x"] * np.float32(2.0 ** -s)).astype(np.float16).astype(np.float32)
+    q = w["q"].copy()
+    q[::2] = (q[::2] * np.float32(2.0 ** -s)).astype(np.float16).astype(np.float32)
+    return x, q
+
+
+def subnormal_share(a):
+    """Share of the non-zero values of `a` that are fp16 subnormals."""
+    v = np.abs(a[a != 0])
+    return float((v < 2.0 ** -14).mean())
+
+
+def planted_low_norm(w, classes, R, C, norm=1e-6, free=30):
+    """The workload with rows under float32's zero-norm rule and above
+    float64's planted where they decide the answer: for every even query i and
+    probe r whose bucket has at least `free` rows, row (7 i + r) % len(rows)
+    of bucket classes[i, r] becomes q16[i] * norm / ||q16[i]|| rounded to
+    fp16 -- the query's own direction (cosine distance ~0 in float64
+    arithmetic up to fp16 rounding of the tiny components) at a norm the
+    float32 rule replaces by 1 (distance ~1).  Returns (x, planted): the
+    corpus (float32 array of fp16 values) and the planted row of each
+    (i, r) or -1."""
+    x = w["x"].astype(np.float16)
+    q16 = w["q"].astype(np.float16)
+    labels = np.asarray(w["labels"])
+    planted = np.full((q16.shape[0], R), -1, np.int64)
+    for i in range(0, q16.shape[0], 2):
+        qi = q16[i].astype(np.float64)
+        for r in range(R):
+            rows = np.flatnonzero(labels == classes[i, r])
+            if rows.size < free:
+                continue
+            t = int(rows[(7 * i + r) % rows.size])
+            x[t] = (qi * norm / np.linalg.norm(qi)).astype(np.float16)
+            planted[planted == t] = -1      # (a row planted twice belongs to its last pair)
+            planted[i, r] = t
+    return x.astype(np.float32), planted
+
+
 def float32_inputs(w, seed, rel=2e-5, rel_q=None):
     """Float32 corpus and queries that are NOT fp16-exact, for the split mode
     (lmi_index_desc.corpus32): the workload's fp16-exact values times
