@@ -682,6 +682,51 @@ int lmi_index_gather_rows(const void* src_corpus, const float* src_inv_norm, int
                           int32_t d_pad, const int64_t* src_pos, void* dst_corpus,
                           float* dst_inv_norm, int64_t n_dst, int32_t* status, void* stream);
 
+/* ---- index re-bucket in place (K10): the gather as two passes of row swaps ---- */
+/* relabel's gather new[p] = old[src_pos[p]] inside ONE store
+ * (li.index.DeviceIndex.relabel(inplace=True)): every permutation is the
+ * product of two involutions, and an involution is a set of disjoint row swaps.
+ * Both calls run asynchronously on `stream`, write caller-owned buffers only
+ * and OR bits into the device word `status` (zeroed by the caller).
+ * Additions: LMI_ABI_VERSION does not change. */
+#define LMI_STATUS_BAD_PERM 32 /* lmi_perm_involutions: src_pos is no permutation of [0, n) */
+/* The plan of src_pos (device int64 [n]; sigma below):
+ *   partner1, partner2  device int64 [n], both involutions; swapping row j with
+ *                       row partner1[j] for every j, then with partner2[j],
+ *                       gives the gather by sigma
+ * The plan is fixed: the leader L of a cycle of sigma is its smallest
+ * position, e_0 = L, e_(t+1) = sigma(e_t), m the cycle's length;
+ * partner1[e_t] = e_((m - t) mod m) and partner2[e_t] = e_(m - 1 - t).  A fixed
+ * point of sigma is its own partner twice; a 2-cycle swaps in pass 2 only.
+ * Pointer doubling over sigma on ping-pong buffers, ceil(log2 n) rounds for
+ * the leaders and as many for the ranks, always all of them: nothing is read
+ * back by the host, and 2 ceil(log2 n) + 9 launches are enqueued.  src_pos is
+ * validated first (every entry in [0, n), every value hit once); when it is no
+ * permutation LMI_STATUS_BAD_PERM is raised, the partners are unspecified and
+ * no access leaves the buffers.  LMI_E_INVALID: n < 0, a null or misaligned
+ * pointer, two of src_pos / partner1 / partner2 the same buffer;
+ * LMI_E_WORKSPACE: a workspace smaller than lmi_perm_involutions_ws_bytes(n)
+ * (40 bytes a row and 8 per 2048 rows; 0 for n <= 0) or not 16-byte aligned --
+ * all checked before any device call.  The workspace needs no initialisation.
+ * n = 0: nothing is enqueued. */
+size_t lmi_perm_involutions_ws_bytes(int64_t n);
+int lmi_perm_involutions(const int64_t* src_pos, int64_t n, int64_t* partner1, int64_t* partner2,
+                         int32_t* status, void* workspace, size_t ws_bytes, void* stream);
+/* One pass: for every j < n with partner[j] > j, rows j and partner[j] of
+ * corpus (device fp16 [n][d_pad], 16-byte aligned, d_pad a multiple of 8) and
+ * the two inv_norm entries change places.  Every pair is checked before its
+ * first write: partner[j] lies in [0, n) and partner[partner[j]] == j; a pair
+ * that fails is skipped and LMI_STATUS_INTERNAL raised (the store's content is
+ * then undefined for the caller's purpose; every valid pair is swapped).  The
+ * pairs of one launch are disjoint, so no workgroup writes a row another
+ * reads; between two passes the order is stream order alone (no grid barrier,
+ * no flag, no cooperative launch).  The grid is capped at LMI_GATHER_MAX_GRID
+ * workgroups of LMI_GATHER_TILE_ROWS rows a pass and grid-strided beyond;
+ * every offset is 64-bit.  LMI_E_INVALID before any device call: n < 0, d_pad,
+ * a null or misaligned pointer.  n = 0: nothing is enqueued. */
+int lmi_index_swap_rows(void* corpus, float* inv_norm, int64_t n, int32_t d_pad,
+                        const int64_t* partner, int32_t* status, void* stream);
+
 /* ---- kernel timing (measurement only) -------------------------------------- */
 /* While enabled, lmi_bucket_topk records a HIP event pair on its stream around
  * its scan kernel (the roofline kernel).  lmi_timing_read waits for the pairs

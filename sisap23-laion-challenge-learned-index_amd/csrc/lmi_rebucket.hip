@@ -335,3 +335,411 @@ extern "C" int lmi_index_gather_rows(const void* src_corpus, const float* src_in
     LMI_LAUNCH_CHECK("gather_rows_kernel");
     return LMI_OK;
 }
+
+// ---- K10 -- re-bucket inside the index's own store (DESIGN.md §3 "K10") -----
+// (lmi_perm_involutions, lmi_index_swap_rows: DeviceIndex.relabel(inplace=True))
+//
+// The gather new[p] = old[sigma[p]] as two passes of disjoint row swaps: every
+// permutation is the product of two involutions.  On a cycle of sigma with the
+// ranks e_0 = L (the smallest position), e_(t+1) = sigma(e_t) and length m the
+// content of rank t + 1 has to reach rank t; pass 1 swaps rank t with rank -t,
+// pass 2 swaps rank u with rank m - 1 - u, and t + 1 -> -(t + 1) -> t.
+//
+//   plan    pointer doubling over sigma in ceil(log2 n) rounds a stage, on
+//           ping-pong buffers of (value, next) pairs (one 16-byte read per hop):
+//             stage 1  leader: v = min(v, v[next]); next = next[next]
+//             stage 2  distance to the leader on the lists cut at the leaders
+//                      (next[L] = L, v[L] = 0): v += v[next]; next = next[next]
+//                      -> m = v[sigma(L)] + 1, t = (m - v) mod m
+//             stage 3  exclusive prefix sums of m over the leaders in position
+//                      order: every cycle gets a range of the table E,
+//                      E[base + t] = e_t; the partners are read from E
+//           sigma is validated first (in range; inv[sigma[p]] = p written by
+//           all, read back by all: two equal entries lose one write).  Every
+//           hop goes through in_range(), so a sigma that is no permutation
+//           costs a status bit and never an access outside the buffers.
+//   swap    row j and row partner[j] for every j with partner[j] > j, mapped as
+//           the gather is: a wave owns 8 consecutive rows j, 16 bytes per lane,
+//           both pieces of four pairs in registers before the first store.
+namespace lmi {
+namespace {
+
+constexpr int kPermThreads = 256;
+constexpr int kPermMaxGrid = 2048;                   // elementwise kernels: grid-strided beyond
+constexpr int kPermScanItems = 8;                    // values a thread sums in the prefix scan
+constexpr int kPermScanTile = kPermThreads * kPermScanItems;
+constexpr int kPermScanThreads = 1024;               // the one workgroup over the tile sums
+
+struct alignas(16) PermPair {
+    int64_t v;    // stage 1: smallest position seen; stage 2: distance to the leader
+    int64_t nx;   // the position 2^round hops on
+};
+
+// sigma[p] when it names a position, p itself otherwise (a hop that stays)
+__device__ inline int64_t in_range(const int64_t* __restrict__ sigma, int64_t p, int64_t n) {
+    const int64_t v = sigma[p];
+    return (v >= 0 && v < n) ? v : p;
+}
+
+inline int perm_rounds(int64_t n) {
+    int r = 0;
+    while (((int64_t)1 << r) < n) ++r;
+    return r;
+}
+
+inline int64_t perm_tiles(int64_t n) { return (n + kPermScanTile - 1) / kPermScanTile; }
+
+inline unsigned perm_grid(int64_t n) {
+    return (unsigned)std::min<int64_t>((n + kPermThreads - 1) / kPermThreads, kPermMaxGrid);
+}
+
+#define LMI_PERM_FOR(p, n)                                                        \
+    for (int64_t p = (int64_t)blockIdx.x * kPermThreads + threadIdx.x; p < (n);   \
+         p += (int64_t)gridDim.x * kPermThreads)
+
+// stage 1's start and the first half of the validation
+__global__ __launch_bounds__(kPermThreads) void perm_init_kernel(const int64_t* __restrict__ sigma,
+                                                                 int64_t n, PermPair* __restrict__ out,
+                                                                 int64_t* __restrict__ inv,
+                                                                 int32_t* __restrict__ status) {
+    bool bad = false;
+    LMI_PERM_FOR(p, n) {
+        const int64_t v = sigma[p];
+        const bool ok = v >= 0 && v < n;
+        if (ok) inv[v] = p;
+        else bad = true;
+        out[p] = PermPair{p, ok ? v : p};
+    }
+    if (bad) atomicOr(status, LMI_STATUS_BAD_PERM);
+}
+
+// ... the second half: a value hit twice kept one of its two writers
+__global__ __launch_bounds__(kPermThreads) void perm_check_kernel(const int64_t* __restrict__ sigma,
+                                                                  int64_t n,
+                                                                  const int64_t* __restrict__ inv,
+                                                                  int32_t* __restrict__ status) {
+    bool bad = false;
+    LMI_PERM_FOR(p, n) {
+        const int64_t v = sigma[p];
+        if (v >= 0 && v < n && inv[v] != p) bad = true;
+    }
+    if (bad) atomicOr(status, LMI_STATUS_BAD_PERM);
+}
+
+// one doubling round, `in` -> `out` (never in place: a racing update reads a
+// neighbour of another round); two independent hops in flight per lane
+template <bool kMin>
+__global__ __launch_bounds__(kPermThreads) void perm_double_kernel(const PermPair* __restrict__ in,
+                                                                   PermPair* __restrict__ out,
+                                                                   int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kPermThreads;
+    for (int64_t p = (int64_t)blockIdx.x * kPermThreads + threadIdx.x; p < n; p += 2 * stride) {
+        const int64_t p1 = p + stride;
+        const bool two = p1 < n;
+        const PermPair a0 = in[p];
+        const PermPair a1 = two ? in[p1] : a0;
+        const PermPair b0 = in[a0.nx];
+        const PermPair b1 = in[a1.nx];
+        out[p] = PermPair{kMin ? std::min(a0.v, b0.v) : a0.v + b0.v, b0.nx};
+        if (two) out[p1] = PermPair{kMin ? std::min(a1.v, b1.v) : a1.v + b1.v, b1.nx};
+    }
+}
+
+// stage 2's start: the leaders are kept in `leader`, the lists are cut there
+__global__ __launch_bounds__(kPermThreads) void perm_cut_kernel(const int64_t* __restrict__ sigma,
+                                                                int64_t n,
+                                                                const PermPair* __restrict__ found,
+                                                                int64_t* __restrict__ leader,
+                                                                PermPair* __restrict__ out) {
+    LMI_PERM_FOR(p, n) {
+        const int64_t L = found[p].v;
+        leader[p] = L;
+        out[p] = (L == p) ? PermPair{0, p} : PermPair{1, in_range(sigma, p, n)};
+    }
+}
+
+// the cycle of p: its length m and p's rank t along sigma from the leader L
+struct PermRank {
+    int64_t L, m, t;
+};
+
+__device__ inline PermRank perm_rank(const int64_t* __restrict__ sigma, int64_t n,
+                                     const int64_t* __restrict__ leader,
+                                     const PermPair* __restrict__ dist, int64_t p) {
+    PermRank r;
+    r.L = leader[p];
+    r.m = dist[in_range(sigma, r.L, n)].v + 1;
+    const int64_t t = (r.m - dist[p].v) % r.m;
+    r.t = t < 0 ? t + r.m : t;                       // (negative only when sigma is no permutation)
+    return r;
+}
+
+// stage 3's input: the cycle length at every leader, 0 elsewhere
+__global__ __launch_bounds__(kPermThreads) void perm_length_kernel(const int64_t* __restrict__ sigma,
+                                                                   int64_t n,
+                                                                   const int64_t* __restrict__ leader,
+                                                                   const PermPair* __restrict__ dist,
+                                                                   int64_t* __restrict__ len) {
+    LMI_PERM_FOR(p, n) len[p] = (leader[p] == p) ? dist[in_range(sigma, p, n)].v + 1 : 0;
+}
+
+// exclusive prefix sums of v[0..n) in place, in three launches: the sum of
+// every tile, the prefix sums of those (one workgroup), the tiles again
+__device__ inline int64_t perm_thread_sum(const int64_t* __restrict__ v, int64_t a, int64_t n) {
+    int64_t s = 0;
+#pragma unroll
+    for (int i = 0; i < kPermScanItems; ++i)
+        if (a + i < n) s += v[a + i];
+    return s;
+}
+
+__global__ __launch_bounds__(kPermThreads) void perm_tile_sum_kernel(const int64_t* __restrict__ v,
+                                                                     int64_t n,
+                                                                     int64_t* __restrict__ tile_sum) {
+    __shared__ int64_t part[kPermThreads];
+    const int64_t a = (int64_t)blockIdx.x * kPermScanTile + (int64_t)threadIdx.x * kPermScanItems;
+    part[threadIdx.x] = perm_thread_sum(v, a, n);
+    __syncthreads();
+    for (int w = kPermThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = part[0];
+}
+
+__global__ __launch_bounds__(kPermScanThreads) void perm_tile_scan_kernel(int64_t* __restrict__ tile_sum,
+                                                                          int64_t tiles) {
+    __shared__ int64_t part[kPermScanThreads];
+    const int64_t per = (tiles + kPermScanThreads - 1) / kPermScanThreads;
+    const int64_t a = std::min<int64_t>((int64_t)threadIdx.x * per, tiles);
+    const int64_t b = std::min<int64_t>(a + per, tiles);
+    int64_t sum = 0;
+    for (int64_t i = a; i < b; ++i) sum += tile_sum[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    int64_t before = 0;
+    for (int t = 0; t < (int)threadIdx.x; ++t) before += part[t];
+    for (int64_t i = a; i < b; ++i) {
+        const int64_t x = tile_sum[i];
+        tile_sum[i] = before;
+        before += x;
+    }
+}
+
+__global__ __launch_bounds__(kPermThreads) void perm_tile_apply_kernel(int64_t* __restrict__ v, int64_t n,
+                                                                       const int64_t* __restrict__ tile_sum) {
+    __shared__ int64_t part[kPermThreads];
+    const int64_t a = (int64_t)blockIdx.x * kPermScanTile + (int64_t)threadIdx.x * kPermScanItems;
+    part[threadIdx.x] = perm_thread_sum(v, a, n);
+    __syncthreads();
+    int64_t before = tile_sum[blockIdx.x];
+    for (int t = 0; t < (int)threadIdx.x; ++t) before += part[t];
+#pragma unroll
+    for (int i = 0; i < kPermScanItems; ++i)
+        if (a + i < n) {
+            const int64_t x = v[a + i];
+            v[a + i] = before;
+            before += x;
+        }
+}
+
+// E[base[L] + t] = e_t
+__global__ __launch_bounds__(kPermThreads) void perm_place_kernel(const int64_t* __restrict__ sigma,
+                                                                  int64_t n,
+                                                                  const int64_t* __restrict__ leader,
+                                                                  const PermPair* __restrict__ dist,
+                                                                  const int64_t* __restrict__ base,
+                                                                  int64_t* __restrict__ E) {
+    LMI_PERM_FOR(p, n) {
+        const PermRank r = perm_rank(sigma, n, leader, dist, p);
+        const int64_t at = base[r.L] + r.t;
+        if (at >= 0 && at < n) E[at] = p;            // (outside only when sigma is no permutation)
+    }
+}
+
+__global__ __launch_bounds__(kPermThreads) void perm_partner_kernel(const int64_t* __restrict__ sigma,
+                                                                    int64_t n,
+                                                                    const int64_t* __restrict__ leader,
+                                                                    const PermPair* __restrict__ dist,
+                                                                    const int64_t* __restrict__ base,
+                                                                    const int64_t* __restrict__ E,
+                                                                    int64_t* __restrict__ partner1,
+                                                                    int64_t* __restrict__ partner2) {
+    LMI_PERM_FOR(p, n) {
+        const PermRank r = perm_rank(sigma, n, leader, dist, p);
+        const int64_t b = base[r.L];
+        const int64_t i1 = b + (r.t ? r.m - r.t : 0);
+        const int64_t i2 = b + r.m - 1 - r.t;
+        partner1[p] = (i1 >= 0 && i1 < n) ? E[i1] : p;
+        partner2[p] = (i2 >= 0 && i2 < n) ? E[i2] : p;
+    }
+}
+
+// One wave owns kGatherWaveRows consecutive rows j per pass: lane l < 8 reads
+// partner[base + l] and checks the pair, then the wave's lanes stride over the
+// 16-byte pieces of the rows that swap (partner > j).  `corpus` and `inv_norm`
+// are read and written through the same pointers (no __restrict__); a lane
+// holds both pieces of a pair before it stores either.
+__global__ __launch_bounds__(kGatherThreads) void swap_rows_kernel(uint4* corpus, float* inv_norm,
+                                                                   int64_t n, int32_t pieces,
+                                                                   const int64_t* __restrict__ partner,
+                                                                   int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t n_tiles = (n + kGatherTileRows - 1) / kGatherTileRows;
+    const int32_t total = kGatherWaveRows * pieces;
+    const int32_t step_r = 64 / pieces, step_c = 64 % pieces;
+    const int32_t r0 = lane / pieces, c0 = lane - r0 * pieces;
+    // partner[j] of the pass after this one is read before this pass's rows (-1: no row)
+    auto partner_of = [&](int64_t tile) -> int64_t {
+        const int64_t j = tile * kGatherTileRows + (int64_t)wave * kGatherWaveRows + lane;
+        return (tile < n_tiles && lane < kGatherWaveRows && j < n) ? partner[j] : -1;
+    };
+    int64_t ahead = partner_of(blockIdx.x);
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t base = tile * kGatherTileRows + (int64_t)wave * kGatherWaveRows;
+        const int64_t q = ahead;
+        ahead = partner_of(tile + gridDim.x);
+        int64_t to = -1;                             // the row that row base + lane swaps with
+        if (lane < kGatherWaveRows && base + lane < n) {
+            const int64_t j = base + lane;
+            // the whole pair is checked before its first write: q in range
+            // and partner[q] == j, so no row belongs to two pairs of a launch
+            if (q < 0 || q >= n || partner[q] != j) atomicOr(status, LMI_STATUS_INTERNAL);
+            else if (q > j) to = q;
+            if (to >= 0) {
+                const float a = inv_norm[j], b = inv_norm[to];
+                inv_norm[j] = b;
+                inv_norm[to] = a;
+            }
+        }
+        if (!__ballot(to >= 0)) continue;            // (wave-uniform: none of the 8 rows moves)
+        int32_t r = r0, c = c0;
+        for (int32_t q0 = lane; q0 < total + lane; q0 += 4 * 64) {
+            // (named registers, not arrays: no staging through LDS or scratch)
+            int64_t x0, x1, x2, x3;                  // piece of row j, -1: none
+            int64_t y0, y1, y2, y3;                  // the same piece of its partner
+            auto at = [&](int32_t p, int64_t& x, int64_t& y) {
+                const int64_t f = __shfl(to, p < total ? r : 0);    // (every lane takes part)
+                const bool on = p < total && f >= 0;
+                x = on ? (base + r) * pieces + c : -1;
+                y = on ? f * pieces + c : -1;
+                r += step_r;
+                c += step_c;
+                if (c >= pieces) {
+                    c -= pieces;
+                    ++r;
+                }
+            };
+            at(q0, x0, y0);
+            at(q0 + 64, x1, y1);
+            at(q0 + 128, x2, y2);
+            at(q0 + 192, x3, y3);
+            uint4 v0 = {}, v1 = {}, v2 = {}, v3 = {}, w0 = {}, w1 = {}, w2 = {}, w3 = {};
+            if (x0 >= 0) { v0 = corpus[x0]; w0 = corpus[y0]; }
+            if (x1 >= 0) { v1 = corpus[x1]; w1 = corpus[y1]; }
+            if (x2 >= 0) { v2 = corpus[x2]; w2 = corpus[y2]; }
+            if (x3 >= 0) { v3 = corpus[x3]; w3 = corpus[y3]; }
+            if (x0 >= 0) { corpus[x0] = w0; corpus[y0] = v0; }
+            if (x1 >= 0) { corpus[x1] = w1; corpus[y1] = v1; }
+            if (x2 >= 0) { corpus[x2] = w2; corpus[y2] = v2; }
+            if (x3 >= 0) { corpus[x3] = w3; corpus[y3] = v3; }
+        }
+    }
+}
+
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+}  // namespace
+}  // namespace lmi
+
+extern "C" size_t lmi_perm_involutions_ws_bytes(int64_t n) {
+    using namespace lmi;
+    if (n <= 0) return 0;
+    // two ping-pong arrays of n pairs, the leaders, the tile sums of the scan
+    return align_up((5 * (size_t)n + (size_t)perm_tiles(n)) * sizeof(int64_t), 16);
+}
+
+extern "C" int lmi_perm_involutions(const int64_t* src_pos, int64_t n, int64_t* partner1, int64_t* partner2,
+                                    int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
+    using namespace lmi;
+    LMI_CHECK_ARG(n >= 0, "perm involutions: n=%lld", (long long)n);
+    LMI_CHECK_ARG(status, "perm involutions: null status");
+    if (n == 0) return LMI_OK;
+    LMI_CHECK_ARG(src_pos && partner1 && partner2, "perm involutions: null pointer");
+    LMI_CHECK_ARG(aligned8(src_pos) && aligned8(partner1) && aligned8(partner2) &&
+                      (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+                  "perm involutions: misaligned pointer");
+    LMI_CHECK_ARG(partner1 != partner2 && src_pos != partner1 && src_pos != partner2,
+                  "perm involutions: src_pos, partner1 and partner2 must be different buffers");
+    const size_t need = lmi_perm_involutions_ws_bytes(n);
+    if (!workspace || ws_bytes < need || !aligned16(workspace)) {
+        set_error("perm involutions: workspace of %zu bytes, %zu needed (16-byte aligned)", ws_bytes, need);
+        return LMI_E_WORKSPACE;
+    }
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int64_t* w = static_cast<int64_t*>(workspace);
+    PermPair* P[2] = {reinterpret_cast<PermPair*>(w), reinterpret_cast<PermPair*>(w + 2 * n)};
+    int64_t* leader = w + 4 * n;
+    int64_t* tile_sum = w + 5 * n;
+    const int rounds = perm_rounds(n);
+    const unsigned grid = perm_grid(n);
+    const unsigned tiles = (unsigned)perm_tiles(n);
+    const dim3 blk(kPermThreads);
+    // validation (inv lives in P[1] until the first round writes there) and stage 1
+    int64_t* inv = w + 2 * n;
+    hipLaunchKernelGGL(perm_init_kernel, dim3(grid), blk, 0, s, src_pos, n, P[0], inv, status);
+    LMI_LAUNCH_CHECK("perm_init_kernel");
+    hipLaunchKernelGGL(perm_check_kernel, dim3(grid), blk, 0, s, src_pos, n, inv, status);
+    LMI_LAUNCH_CHECK("perm_check_kernel");
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(perm_double_kernel<true>, dim3(grid), blk, 0, s, P[r & 1], P[(r + 1) & 1], n);
+        LMI_LAUNCH_CHECK("perm_double_kernel<min>");
+    }
+    // stage 2: from the array stage 1 ended in to the other one, then ping-pong
+    PermPair* G[2] = {P[(rounds + 1) & 1], P[rounds & 1]};
+    hipLaunchKernelGGL(perm_cut_kernel, dim3(grid), blk, 0, s, src_pos, n, G[1], leader, G[0]);
+    LMI_LAUNCH_CHECK("perm_cut_kernel");
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(perm_double_kernel<false>, dim3(grid), blk, 0, s, G[r & 1], G[(r + 1) & 1], n);
+        LMI_LAUNCH_CHECK("perm_double_kernel<add>");
+    }
+    const PermPair* dist = G[rounds & 1];
+    // stage 3 in the array stage 2 did not end in: cycle lengths -> bases, and E
+    int64_t* base = reinterpret_cast<int64_t*>(G[(rounds + 1) & 1]);
+    int64_t* E = base + n;
+    hipLaunchKernelGGL(perm_length_kernel, dim3(grid), blk, 0, s, src_pos, n, leader, dist, base);
+    LMI_LAUNCH_CHECK("perm_length_kernel");
+    hipLaunchKernelGGL(perm_tile_sum_kernel, dim3(tiles), blk, 0, s, base, n, tile_sum);
+    LMI_LAUNCH_CHECK("perm_tile_sum_kernel");
+    hipLaunchKernelGGL(perm_tile_scan_kernel, dim3(1), dim3(kPermScanThreads), 0, s, tile_sum, (int64_t)tiles);
+    LMI_LAUNCH_CHECK("perm_tile_scan_kernel");
+    hipLaunchKernelGGL(perm_tile_apply_kernel, dim3(tiles), blk, 0, s, base, n, tile_sum);
+    LMI_LAUNCH_CHECK("perm_tile_apply_kernel");
+    hipLaunchKernelGGL(perm_place_kernel, dim3(grid), blk, 0, s, src_pos, n, leader, dist, base, E);
+    LMI_LAUNCH_CHECK("perm_place_kernel");
+    hipLaunchKernelGGL(perm_partner_kernel, dim3(grid), blk, 0, s, src_pos, n, leader, dist, base, E, partner1,
+                       partner2);
+    LMI_LAUNCH_CHECK("perm_partner_kernel");
+    return LMI_OK;
+}
+
+extern "C" int lmi_index_swap_rows(void* corpus, float* inv_norm, int64_t n, int32_t d_pad,
+                                   const int64_t* partner, int32_t* status, void* stream) {
+    using namespace lmi;
+    LMI_CHECK_ARG(n >= 0, "swap rows: n=%lld", (long long)n);
+    LMI_CHECK_ARG(d_pad > 0 && d_pad % 8 == 0, "swap rows: d_pad=%d (a positive multiple of 8)", d_pad);
+    if (n == 0) return LMI_OK;
+    LMI_CHECK_ARG(corpus && inv_norm && partner && status, "swap rows: null pointer");
+    LMI_CHECK_ARG(aligned16(corpus), "swap rows: corpus not 16-byte aligned");
+    LMI_CHECK_ARG(aligned8(partner) && (reinterpret_cast<uintptr_t>(inv_norm) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+                  "swap rows: misaligned pointer");
+    const int64_t tiles = (n + kGatherTileRows - 1) / kGatherTileRows;
+    const unsigned grid = (unsigned)std::min<int64_t>(tiles, kGatherMaxGrid);
+    hipLaunchKernelGGL(swap_rows_kernel, dim3(grid), dim3(kGatherThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<uint4*>(corpus), inv_norm, n,
+                       d_pad / 8, partner, status);
+    LMI_LAUNCH_CHECK("swap_rows_kernel");
+    return LMI_OK;
+}

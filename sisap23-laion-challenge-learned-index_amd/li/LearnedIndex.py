@@ -465,7 +465,8 @@ class LearnedIndex(Logger):
         self._adopt(new_index, nav2, search2, labels2)
         return nav2, search2, labels2
 
-    def rebucket(self, data_navigation, data_search, pred_categories, new_categories=None):
+    def rebucket(self, data_navigation, data_search, pred_categories, new_categories=None, *,
+                 inplace=False):
         """Give the indexed objects new bucket labels without a rebuild
         (DeviceIndex.relabel: the rows are permuted inside HBM; the corpus does
         not cross PCIe again).  `new_categories` default to the current
@@ -478,7 +479,9 @@ class LearnedIndex(Logger):
 
         to pass to later search / search_single calls, as `insert` does.
         Answers are bitwise those of an index built from the same frames with
-        the new labels."""
+        the new labels.  `inplace=True`: the rows change places inside the
+        index's own store (DeviceIndex.relabel(inplace=True): no second corpus
+        in HBM, no reserved capacity needed); the results are the same."""
         index = self._updatable_index(data_navigation, data_search, pred_categories)
         nav2 = data_navigation.drop(columns="category", errors="ignore")
         if new_categories is None:
@@ -487,7 +490,7 @@ class LearnedIndex(Logger):
         labels2 = np.array(new_categories).astype(np.int64).ravel()
         if labels2.shape != (nav2.shape[0],):
             raise ValueError("rebucket: new_categories must have one entry per object")
-        new_index = index.relabel(labels2, n_buckets=self._n_buckets(labels2))
+        new_index = index.relabel(labels2, n_buckets=self._n_buckets(labels2), inplace=inplace)
         nav2["category"] = labels2                     # what search() writes (:67)
         self._adopt(new_index, nav2, data_search, labels2)
         return nav2, data_search, labels2

@@ -30,6 +30,7 @@ LMI_STATUS_INTERNAL = 2
 LMI_STATUS_ROWS_NOT_F16 = 4
 LMI_STATUS_BAD_LABEL = 8
 LMI_STATUS_ROWS_LOW_NORM = 16
+LMI_STATUS_BAD_PERM = 32   # K10 (lmi_perm_involutions): src_pos is no permutation
 
 LMI_F32 = 0
 LMI_F16 = 1
@@ -105,6 +106,9 @@ EXPORTS = (
     "lmi_bucket_sort_labels_ws_bytes",
     "lmi_bucket_sort_labels",
     "lmi_index_gather_rows",
+    "lmi_perm_involutions_ws_bytes",
+    "lmi_perm_involutions",
+    "lmi_index_swap_rows",
     "lmi_timing_enable",
     "lmi_timing_read",
     "lmi_last_error",
@@ -235,6 +239,9 @@ _SIGNATURES = {
     "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),
     "lmi_bucket_sort_labels": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
     "lmi_index_gather_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I64, _P, _P]),
+    "lmi_perm_involutions_ws_bytes": (C.c_size_t, [_I64]),
+    "lmi_perm_involutions": (C.c_int, [_P, _I64, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_index_swap_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "lmi_timing_enable": (C.c_int, [_I32]),
     "lmi_timing_read": (C.c_int32, [_P, _I32]),
     "lmi_last_error": (C.c_char_p, []),

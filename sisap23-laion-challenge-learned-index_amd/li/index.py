@@ -512,7 +512,7 @@ class DeviceIndex:
         offset tables are gone (a captured graph would replay over moved rows
         through freed tables)."""
         if self.consumed:
-            raise RuntimeError("this index was updated in place (add / remove with inplace=True) and "
+            raise RuntimeError("this index was updated in place (add / remove / relabel with inplace=True) and "
                                "is consumed: use the index that call returned "
                                "(Searcher.with_index(new))")
 
@@ -678,7 +678,8 @@ class DeviceIndex:
         return order, off
 
     @torch.no_grad()
-    def relabel(self, labels, n_buckets: Optional[int] = None, *, timings=None) -> "DeviceIndex":
+    def relabel(self, labels, n_buckets: Optional[int] = None, *, inplace: bool = False,
+                timings=None) -> "DeviceIndex":
         """A NEW index over the same row sequence with the bucket labels
         `labels` (labels[s]: the bucket of sequence row s -- the constructor's
         rows with survivors renumbered and batches appended, as layout.order
@@ -689,7 +690,22 @@ class DeviceIndex:
         and a row gather on the device); the host uploads the old order /
         pos_to_id tables and downloads the new ones.  This index is not
         touched.  `timings` (measurement only): a dict that receives the
-        seconds spent in 'sort', 'tables', 'gather' and 'host'."""
+        seconds spent in 'sort', 'tables', 'gather' and 'host'.
+
+        inplace=True (K10): the rows change places inside this index's own
+        store, which the returned index takes over (same corpus.data_ptr(),
+        same capacity); no second corpus is allocated, and no reserved
+        capacity is needed, as the row count stays.  The gather is run as two
+        passes of disjoint row swaps (lmi_perm_involutions plans them,
+        lmi_index_swap_rows moves the rows).  The result is the same index,
+        bit for bit.  THIS index is consumed, as by add / remove in place: go
+        on with Searcher.with_index(new).  Every refusal -- this method's, and
+        a plan whose status is not clean -- comes before the first row moves
+        and leaves this index in use, unchanged.  The call waits for the whole
+        device before it moves a row and again before it returns.  `timings`
+        then receives 'plan' and 'swap' in place of 'gather', and 'plan_ms',
+        'plan_rounds', 'swap_ms' (both passes, by device events) and
+        'swapped_rows' (rows that change places, per pass)."""
         self._check_live()
         self._check_updatable()
         C_ = self.n_buckets if n_buckets is None else int(n_buckets)
@@ -730,27 +746,100 @@ class DeviceIndex:
         new.n_total = new.n_rows = n
         new.rank, new.world = 0, 1
         new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
-        new._alloc_store(n, capacity=self.capacity)   # (a reserved index stays reserved)
+        chunk_rows = self.chunk_rows if self._chunk_rows_given else None
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        check("lmi_index_gather_rows", lib.lmi_index_gather_rows(
-            ptr(self.corpus), ptr(self.inv_norm), n, self.d_pad, ptr(src_pos), ptr(new.corpus),
-            ptr(new.inv_norm), n, ptr(status), _lib.stream_handle(dev)))
-        st = int(status.item())  # (waits for the kernel: src_pos stays alive until here)
-        if st:
-            raise RuntimeError(f"index relabel: internal status {st}")
-        if self.inv_norm64 is not None:
-            new._set_inv_norm64()
-        mark("gather")
+        if inplace:
+            self._swap_into(new, src_pos, status, mark, timings)   # (consumes this index)
+        else:
+            new._alloc_store(n, capacity=self.capacity)   # (a reserved index stays reserved)
+            check("lmi_index_gather_rows", lib.lmi_index_gather_rows(
+                ptr(self.corpus), ptr(self.inv_norm), n, self.d_pad, ptr(src_pos), ptr(new.corpus),
+                ptr(new.inv_norm), n, ptr(status), _lib.stream_handle(dev)))
+            st = int(status.item())  # (waits for the kernel: src_pos stays alive until here)
+            if st:
+                raise RuntimeError(f"index relabel: internal status {st}")
+            if self.inv_norm64 is not None:
+                new._set_inv_norm64()
+            mark("gather")
         new.layout = BucketLayout(C_, order.cpu().numpy(), off.cpu().numpy())
         new.pos_to_id = p2id.cpu().numpy()
         new.bucket_size = new.layout.bucket_size.copy()
-        new._plan_tables(new.layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
+        new._plan_tables(new.layout.bucket_off.copy(), chunk_rows)
         new.gpos = torch.arange(n, dtype=torch.int32, device=dev)
         new.chunk_centroid = None
         new._desc = IndexDescHolder(new)
         new._ws = {}
         mark("host")
         return new
+
+    def _swap_into(self, new, src_pos, status, mark, timings):
+        """relabel(inplace=True)'s row move (K10): plan the gather by
+        `src_pos` as two involutions, read the plan's status, then swap the
+        rows of this index's own store in two passes and hand the store to
+        `new`.  This index is consumed once the first pass is enqueued."""
+        lib = _lib.load()
+        dev, n = self.device, self.n_rows
+        s = _lib.stream_handle(dev)
+        store, store_inv, cap = self._store, self._store_inv, self.capacity
+        low64 = self.inv_norm64 is not None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
+        p1 = p2 = None
+        if n:
+            p1 = torch.empty(n, dtype=torch.int64, device=dev)
+            p2 = torch.empty(n, dtype=torch.int64, device=dev)
+            need = lib.lmi_perm_involutions_ws_bytes(n)
+            ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+            if ev:
+                ev[0].record()
+            check("lmi_perm_involutions", lib.lmi_perm_involutions(
+                ptr(src_pos), n, ptr(p1), ptr(p2), ptr(status), ptr(ws), need, s))
+            if ev:
+                ev[1].record()
+            st = int(status.item())  # (the plan is judged before any row moves)
+            del ws
+            if st & _lib.LMI_STATUS_BAD_PERM:
+                raise RuntimeError("index relabel in place: the row order of the index and the new one "
+                                   "do not give a permutation of its rows (the index is unchanged)")
+            if st:
+                raise RuntimeError(f"index relabel in place: internal status {st} (the index is unchanged)")
+            if ev:
+                at = torch.arange(n, dtype=torch.int64, device=dev)
+                timings["swapped_rows"] = [2 * int((p > at).sum()) for p in (p1, p2)]
+                del at
+        mark("plan")
+        # everything queued on the device (replays on other streams that read
+        # this index) finishes before the first row moves
+        torch.cuda.synchronize(dev)
+        if n:
+            if ev:
+                ev[2].record()
+            rc = lib.lmi_index_swap_rows(ptr(store), ptr(store_inv), n, self.d_pad, ptr(p1), ptr(status), s)
+            if rc == _lib.LMI_E_INVALID:
+                check("lmi_index_swap_rows", rc)  # (refused on the host: nothing was launched)
+        # from here on rows may have moved: this object must not launch again
+        self._consume()
+        if n:
+            check("lmi_index_swap_rows", rc)
+            if ev:
+                ev[3].record()
+            check("lmi_index_swap_rows", lib.lmi_index_swap_rows(
+                ptr(store), ptr(store_inv), n, new.d_pad, ptr(p2), ptr(status), s))
+            if ev:
+                ev[4].record()
+        st = int(status.item())  # (waits for both passes: the partners stay alive until here)
+        torch.cuda.synchronize(dev)
+        if st:
+            raise RuntimeError(f"index relabel in place: internal status {st}; the index is consumed "
+                               "and the content of its store is undefined")
+        new._store, new._store_inv, new._capacity = store, store_inv, cap
+        new.corpus, new.inv_norm = store[:n], store_inv[:n]
+        if low64:
+            new._set_inv_norm64()
+        if ev and n:
+            timings["plan_ms"] = ev[0].elapsed_time(ev[1])
+            timings["plan_rounds"] = 2 * max(0, (n - 1).bit_length())
+            timings["swap_ms"] = [ev[2].elapsed_time(ev[3]), ev[3].elapsed_time(ev[4])]
+        mark("swap")
 
     def _batch_rows(self, rows) -> torch.Tensor:
         """The batch on the device as lmi_index_ingest_rows reads it: fp16 or
