@@ -270,6 +270,38 @@ int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_t nq, int32
                     float* out_d, int32_t* out_pos, int32_t* status,
                     void* workspace, size_t ws_bytes, void* stream);
 
+/* K2 tagged: lmi_bucket_topk with a predicate tested inside the scan.  Every
+ * stored row carries a 32-bit tag word, every query a 32-bit want word; a row
+ * is eligible for a query iff (tag & want) == want (all-of; want == 0 accepts
+ * every row).  A (query, probe) list is the exact top-k, by (distance, global
+ * position), of the eligible rows of the probed bucket, padded (+inf, -1) like
+ * a short bucket: the list lmi_bucket_topk gives on an index built from the
+ * eligible rows alone, bitwise in its distances.  A row that fails the
+ * predicate never enters a list and never tightens a pair's bound.
+ *   tags     device [n_rows] uint32, row order of idx->corpus
+ *   want     device [nq] uint32
+ * Every other argument, the outputs, the status bits and the workspace contract
+ * (lmi_scan_tagged_workspace_bytes) are lmi_bucket_topk's.  1 <= k <= LMI_MAX_K.
+ * The plan is lmi_bucket_topk's but that the 4-wave ring's shapes and the
+ * 8-wave ring's 15-entry lists go to the general kernel: the 8-wave ring
+ * (scan3_kernel MODE 4) for d_pad == 768, an fp16 corpus, LMI_Q_F16 and
+ * k <= 10, the general kernel (scan_kernel TAG) for everything else; the
+ * workspace has lmi_bucket_topk's size wherever both plans pick the same
+ * kernel family.
+ * LMI_E_INVALID (lmi_last_error says which) before any launch, device or no
+ * device, for: null tags or want; k > LMI_MAX_K; idx->corpus32 or corpus64 (the
+ * split mode); idx->chunk_centroid (sub-cluster layouts); any flag in qmode --
+ * the phases, the join and LMI_Q_SEED_ROUND0: the tagged scan is never seeded
+ * (its kernel has no scalar register left for the seed's pointer), and with
+ * join workgroups set on the calling thread the call is refused.
+ * Additions: LMI_ABI_VERSION does not change. */
+size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R,
+                                       int32_t k, int32_t qmode);
+int lmi_bucket_topk_tagged(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* want,
+                           const float* q, int32_t nq, int32_t ldq, const int32_t* classes,
+                           int32_t R, int32_t k, int32_t qmode, float* out_d, int32_t* out_pos,
+                           int32_t* status, void* workspace, size_t ws_bytes, void* stream);
+
 /* Merge G per-shard lists of the same rows (K3): in
  * device [G][rows][k] (d f32, pos int32, -1 = empty), out device [rows][k] =
  * the k smallest by (d, pos).  Used after the RCCL all-gather of a G-GPU index.

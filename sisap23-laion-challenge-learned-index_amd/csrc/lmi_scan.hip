@@ -825,6 +825,15 @@ __global__ __launch_bounds__(256) void set_bound_kernel(const int32_t* __restric
     ccount[pp] = n;
 }
 
+// the tagged scan on the 8-wave ring (scan3_kernel MODE 4): every query's
+// (1/|q|, want) as one pair
+__global__ __launch_bounds__(256) void want_pack_kernel(const float* __restrict__ invq,
+                                                        const uint32_t* __restrict__ want, int32_t nq,
+                                                        uint2* __restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq) out[q] = make_uint2(__float_as_uint(invq[q]), want[q]);
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -834,17 +843,19 @@ int split_parts() {
     return std::max(2, std::min(kSplitMaxParts, env_config().scan_split_parts));
 }
 
-ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo) {
+ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo, bool tagged) {
     ScanPlan w{};
     w.f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
     // the rings take an fp16 corpus, fp16-exact queries and d_pad == 768; the
     // diagnostic switches LMI_SCAN_V1 / LMI_SCAN_V2 force the general kernel /
     // the 4-wave ring.  The 8-wave ring has 10- and 15-entry lists; the
     // lower-bound passes (k > 16) run on it or on the general kernel
+    // (tagged: the 8-wave ring's 10-entry lists or the general kernel)
     const bool ring4 = w.f16math && idx->d_pad == v2::D && !env_config().scan_v1;
     const bool ring8 = ring4 && !env_config().scan_v2;
-    w.kl = k <= 10 ? 10 : (k <= 15 && ring8) ? 15 : 16;
-    w.family = ring8 && w.kl != 16 ? ScanKernel::Ring8 : ring4 && !lo ? ScanKernel::Ring4 : ScanKernel::General;
+    w.kl = k <= 10 ? 10 : (k <= 15 && ring8 && !tagged) ? 15 : 16;
+    w.family = ring8 && w.kl != 16 ? ScanKernel::Ring8
+               : ring4 && !lo && !tagged ? ScanKernel::Ring4 : ScanKernel::General;
     const bool v3 = w.family == ScanKernel::Ring8;
     w.qb = v3 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math ? 64 : 32);
     const size_t P = (size_t)nq * R;
@@ -988,6 +999,21 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     const int kl = p.kl, mode = c.wide ? c.wide->mode : 0;
     const bool lo = c.lo_g != nullptr, band = c.out_bound != nullptr, corpus_f16 = c.idx->dtype == LMI_F16;
     const bool plain = mode == 0 && !lo && !band;
+    if (c.tags != nullptr) {
+        // the tagged scan: the 8-wave ring's MODE 4 or the general kernel's TAG
+        if (!plain) return {nullptr, nullptr};
+        if (p.family == ScanKernel::Ring8)
+            return {kl == 10 ? launch_scan3_v<10, 0, false, 4> : nullptr, nullptr};
+        if (p.family != ScanKernel::General) return {nullptr, nullptr};
+        if (p.f16math)
+            return {nullptr, kl == 10 ? launch_scan<10, true, _Float16, false, true>
+                                      : launch_scan<16, true, _Float16, false, true>};
+        if (corpus_f16)
+            return {nullptr, kl == 10 ? launch_scan<10, false, _Float16, false, true>
+                                      : launch_scan<16, false, _Float16, false, true>};
+        return {nullptr, kl == 10 ? launch_scan<10, false, float, false, true>
+                                  : launch_scan<16, false, float, false, true>};
+    }
     if (p.family == ScanKernel::Ring8) {
         if (mode == 1 && !lo && !band && kl == 15) return {launch_scan3_v<15, 0, false, 1>, nullptr};
         if (mode == 2 && !lo && !band && kl == 10) return {launch_scan3_v<10, 0, false, 2>, nullptr};
@@ -1087,6 +1113,39 @@ extern "C" int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_
     return k <= LMI_MAX_K ? bucket_topk_impl(c) : bucket_topk_wide_k(c);
 }
 
+extern "C" size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R,
+                                                  int32_t k, int32_t qmode) {
+    using namespace lmi;
+    if (!idx || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
+    if (idx->corpus32 || idx->corpus64 || idx->chunk_centroid) return 0;
+    if (qmode != LMI_Q_F16 && qmode != LMI_Q_F32) return 0;
+    return scan_plan(idx, nq, R, k, qmode, false, true).total;
+}
+
+extern "C" int lmi_bucket_topk_tagged(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* want,
+                                      const float* q, int32_t nq, int32_t ldq, const int32_t* classes,
+                                      int32_t R, int32_t k, int32_t qmode, float* out_d, int32_t* out_pos,
+                                      int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
+    using namespace lmi;
+    // (every refusal comes before any launch and needs no device)
+    LMI_CHECK_ARG(idx != nullptr, "null index");
+    LMI_CHECK_ARG(tags != nullptr && want != nullptr, "lmi_bucket_topk_tagged: null tags or want");
+    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "lmi_bucket_topk_tagged: k=%d outside [1, %d]", k, LMI_MAX_K);
+    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
+                  "lmi_bucket_topk_tagged: the split mode (corpus32 / corpus64) takes no tags");
+    LMI_CHECK_ARG(!idx->chunk_centroid, "lmi_bucket_topk_tagged: sub-cluster layouts (chunk_centroid) take no tags");
+    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32,
+                  "lmi_bucket_topk_tagged: qmode 0x%x: LMI_Q_F16 or LMI_Q_F32 alone (no phase, join or seed flag)",
+                  qmode);
+    const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
+                     .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
+                     .workspace = workspace, .ws_bytes = ws_bytes,
+                     .stream = reinterpret_cast<hipStream_t>(stream), .tags = tags, .want = want};
+    // (with join workgroups set on this thread bucket_topk_impl refuses the
+    // call: the tagged scan runs in one launch)
+    return bucket_topk_impl(c);
+}
+
 int lmi::bucket_topk_impl(const ScanCall& c) {
     using namespace lmi;
     const lmi_index_desc* idx = c.idx;
@@ -1112,7 +1171,8 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     LMI_CHECK_ARG(idx->n_rows == 0 || (idx->corpus && idx->inv_norm && idx->gpos), "null corpus arrays");
     LMI_CHECK_ARG(idx->bucket_off && idx->chunk_first, "null bucket tables");
 
-    const ScanPlan w = c.plan ? *c.plan : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr);
+    LMI_CHECK_ARG((c.tags != nullptr) == (c.want != nullptr), "tags and want come together");
+    const ScanPlan w = c.plan ? *c.plan : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr, c.tags != nullptr);
     if (c.ws_bytes < w.total) {
         set_error("workspace %zu B < required %zu B", c.ws_bytes, w.total);
         return LMI_E_WORKSPACE;
@@ -1131,7 +1191,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     int phases = c.phases;
     {
         bool done;
-        LMI_TRY(join_gate(phases, v3 && wide == nullptr && lo_g == nullptr, &done));
+        LMI_TRY(join_gate(phases, v3 && wide == nullptr && lo_g == nullptr && c.tags == nullptr, &done));
         if (done) return LMI_OK;
     }
     const bool do_plan = phases & kPhasePlan, do_scan = phases & kPhaseScan, do_merge = phases & kPhaseMerge;
@@ -1272,6 +1332,8 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     a.partial = (uint64_t*)(ws + w.partial);
     a.gpos = idx->gpos;
     a.lo_g = lo_g;
+    a.tags = c.tags;
+    a.want = c.want;
 
     // (the phases split the general kernel's call as they split the rings':
     // everything a later phase reads -- the rounded queries, the tile plan,
@@ -1301,6 +1363,18 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         b.band = band ? c.seed_margin * (1.0f + 0x1p-20f) + 0x1p-22f : 0.0f;
         b.ng = ng;
         b.lag = std::max(0, std::min(3, env_config().scan_lag));
+        if (c.tags != nullptr) {
+            // MODE 4 reads (1/|q|, want) pairs: packed behind the plan's pair
+            // arrays, in the nearest-chunk-first plan's scratch (pref,
+            // pref_tmp: 2 P words >= 2 nq), which a tagged call never uses
+            uint2* iw = reinterpret_cast<uint2*>(ws + w.pref);
+            if (do_plan) {
+                hipLaunchKernelGGL(want_pack_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, a.invq, c.want, nq, iw);
+                LMI_LAUNCH_CHECK("want_pack_kernel");
+            }
+            b.invq = reinterpret_cast<const float*>(iw);
+            b.tags = c.tags;
+        }
         if (wide) {
             b.cand = wide->cand;
             b.ccount = wide->ccount;

@@ -79,6 +79,12 @@ constexpr int list_stride() { return KL == 10 ? 11 : KL; }
 template <int KL>
 constexpr size_t lds_bytes() { return (size_t)NSLOT * STAGE + (size_t)NW * 64 * list_stride<KL>() * 8 + 64; }
 static_assert(lds_bytes<15>() <= 160 * 1024, "LDS budget");
+// MODE 4 (tagged), behind lds_bytes<10>(): the 32 tag words of each of the
+// three blocks in flight (laid out like the blocks' norms), then every wave's
+// 32 want words (one per query column)
+constexpr int TAG_AREA = 3 * 128;
+constexpr int WANT_AREA = NW * 32 * 4;
+static_assert(lds_bytes<10>() + TAG_AREA + WANT_AREA <= 160 * 1024, "LDS budget");
 }  // namespace v3
 
 
@@ -121,6 +127,14 @@ __device__ __forceinline__ f32x16 mfma_drain_v(const f32x16& c) {
 
 // LDS list entries at a base VGPR + immediate offset (one address register
 // for a whole list; plain-C++ addressing would hoist one register per entry)
+__device__ __forceinline__ void lds_put_u32(uint32_t addr, uint32_t v) {
+    asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+__device__ __forceinline__ uint32_t lds_get_u32(uint32_t addr) {
+    uint32_t v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
+    return v;
+}
 template <int OFF>
 __device__ __forceinline__ void lds_put_u64_at(uint32_t addr, uint64_t v) {
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(OFF) : "memory");
@@ -292,6 +306,10 @@ __device__ __forceinline__ int opaque(int x) {
     asm volatile("" : "+v"(x));
     return x;
 }
+__device__ __forceinline__ uint32_t opaque_s(uint32_t x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
 __device__ __forceinline__ uint32_t opaque_u(uint32_t x) {
     asm volatile("" : "+v"(x));
     return x;
@@ -307,11 +325,25 @@ __device__ __forceinline__ uint32_t opaque_u(uint32_t x) {
 // first 15 of the two lanes' lists plus a bound below which every unlisted
 // row of the part that passed the filter lies (kBandSlot entries, see
 // chunk_merge_band_kernel).
+// MODE 4 (lmi_bucket_topk_tagged, KL = 10): the product scan plus the tag
+// test -- a row is a candidate of a pair only if (tag & want) == want.  The
+// block's 32 tag words arrive by a 4-byte LDS-DMA beside its norms (lanes 0-3
+// of each wave, the same addressing); the pair's want word waits in a
+// per-wave LDS slot written at the tile start.  The test sits in the
+// per-candidate walk (one LDS read of the tag word, one of the want word, at
+// addresses made inside the iteration): a candidate that fails is skipped
+// before the list is touched, so it enters no list and tightens no bound, and
+// nothing new is live across the MFMA stream or around the walk (the kernel
+// has no VGPR and no SGPR to spare: the mask-stage form -- the predicate ANDed
+// into `ok` -- spilled a query fragment into the stream).
+// Bounds, the thr_g atomicMin, the 32-block bound exchange, the tail handling
+// and the lists are MODE 0's; never seeded; invq holds (1/|q|, want) pairs.
 template <int KL, int ABL = 0, bool LO = false, int MODE = 0>
 __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     using namespace v3;
     static_assert(MODE == 0 || (ABL == 0 && !LO), "the wide modes are product variants");
     static_assert(MODE != 3 || KL == 10, "band lists are built from 10-entry lane lists");
+    static_assert(MODE != 4 || KL == 10, "the tagged scan has 10-entry lists");
     // diagnostic builds only (results wrong for ABL != 0): 1 no insertion,
     // 2 DMA + barriers only, 3 no DMA, 4 no DMA and no insertion, 5 no DMA and
     // no epilogue, 6 = 5 without barriers, 7 event counters, 14 no DMA wait,
@@ -331,7 +363,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     constexpr bool kNoIns = ABL == 1 || ABL == 4;
     constexpr bool kNoBar = ABL == 6 || ABL == 66 || ABL == 21 || ABL == 69 || ABL == 70;
     // bound exchange period in blocks (diagnostic: 40 none, 41 every 4, 42 every 8, 43 every 16)
-    constexpr int kXch = (ABL == 40 || MODE != 0) ? 0 : ABL == 41 ? 4 : ABL == 42 ? 8 : ABL == 43 ? 16 : 32;
+    constexpr int kXch = (ABL == 40 || (MODE != 0 && MODE != 4)) ? 0 : ABL == 41 ? 4 : ABL == 42 ? 8 : ABL == 43 ? 16 : 32;
     // (ABL 53, round 1's placement: an LDS-DMA issue holds its wave for ~45-60
     // cycles, so the two waves of a SIMD issued theirs at different MFMAs)
     constexpr int kDmaTT = 2, kDmaLate = 10;
@@ -361,11 +393,26 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     static_assert(MODE != 2 || (size_t)NW * 32 * (kXS * 8 + 4) <= (size_t)NW * 64 * LS * 8, "collect stage");
     uint64_t* xst = lists;
     uint32_t* xcnt = reinterpret_cast<uint32_t*>(lists + NW * 32 * kXS);
+    // MODE 4: the tag words of the blocks in flight and the waves' want words
+    unsigned char* tag_area = smem + lds_bytes<KL>();
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ng = a.ng;
+    // MODE 4 has no scalar register to spare for its two more pointers (the
+    // product scan uses every one, and a spilled scalar takes a VGPR, which
+    // pushes a query fragment into scratch): the arguments read once per tile
+    // or per block are re-read from the kernel-argument segment where they are
+    // used, through a pointer the compiler cannot hoist the loads above,
+    // instead of being held for the whole kernel.
+    using karg_t = const __attribute__((address_space(4))) Scan2Args*;
+    auto kargs = [] {
+        karg_t p = (karg_t)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+        return p;
+    };
+#define LMI_KARG(f) (MODE == 4 ? kargs()->f : a.f)
 
     // SIMD-balanced slot of this wave: order waves by (rank on their SIMD, SIMD)
     int simd, xcc;
@@ -407,13 +454,14 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
         __syncthreads();
         const int t = __builtin_amdgcn_readfirstlane(s_tile);
         if (t < 0) break;
-        const Tile tile = a.tiles[t];
-        const int64_t bstart = a.bucket_off[tile.c];
+        const Tile tile = LMI_KARG(tiles)[t];
+        const int64_t* boff = LMI_KARG(bucket_off);
+        const int64_t bstart = boff[tile.c];
         // (chunk-list mode: the bucket's own list rows, and of each list the
         // first sub_take rows, a sample)
         const int64_t row0 = bstart + (int64_t)tile.chunk * (MODE == 1 ? a.sub_rows[tile.c] : a.chunk_rows);
         const int nrows = __builtin_amdgcn_readfirstlane(
-            (int)std::min<int64_t>(MODE == 1 ? a.sub_take[tile.c] : a.chunk_rows, a.bucket_off[tile.c + 1] - row0));
+            (int)std::min<int64_t>(MODE == 1 ? a.sub_take[tile.c] : a.chunk_rows, boff[tile.c + 1] - row0));
         const uint32_t r0lo = __builtin_amdgcn_readfirstlane((uint32_t)row0);
         const uint32_t r0hi = __builtin_amdgcn_readfirstlane((uint32_t)(row0 >> 32));
         const int64_t row0u = (int64_t)(((uint64_t)r0hi << 32) | r0lo);
@@ -451,6 +499,23 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_t)(sl + (2 * w + 1) * PIECEP), 16,
                                                      vo_row, b * (32 * D * 2) + j * ROWB + 2 * D * 2,
                                                      0, kAux);
+            if constexpr (MODE == 4) {
+                // (the wave's 4 tag words ride with its 4 norms)
+                if (j == NST - 1 && lane < 4) {
+                    const uint32_t vo = (uint32_t)((4 * w + opaque(lane)) * 4);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rn, (lds_t)(ring + nb_area * STAGE + NORM_OFF + 16 * w),
+                                                             4, vo, b * 128, 0, 0);
+                    // (the tag words' descriptor is built here, once per block,
+                    // from values the tile holds anyway: kept for the whole
+                    // tile its four scalar registers spill; past the chunk's
+                    // end the words read 0)
+                    const int64_t trow = (int64_t)(((uint64_t)opaque_s(r0hi) << 32) | r0lo);
+                    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+                        (void*)(kargs()->tags + trow), (short)0, nrows * 4, 0x00020000);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, (lds_t)(tag_area + nb_area * 128 + 16 * w),
+                                                             4, vo, b * 128, 0, 0);
+                }
+            } else
             if (j == NST - 1 && lane < 4)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rn, (lds_t)(ring + nb_area * STAGE + NORM_OFF + 16 * w),
                                                          4, (uint32_t)((4 * w + opaque(lane)) * 4), b * 128, 0, 0);
@@ -492,7 +557,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                     lo_row = l;
                 }
             }
-            const half8* qrow = reinterpret_cast<const half8*>(a.qbuf + (size_t)q * D) + h;
+            const half8* qrow = reinterpret_cast<const half8*>(LMI_KARG(qbuf) + (size_t)q * D) + h;
             // dead columns of a partial wave multiply zeros: their results
             // are never read, and zero operands draw less MFMA power (the
             // chip holds a power-limited clock under this kernel; diagnostic
@@ -502,9 +567,16 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
             for (int s = 0; s < NQF; ++s) qf[s] = (live || ABL == 57) ? qrow[2 * s] : z;
             // dead slots (and exhausted pairs) reject everything
             thr = live && !done ? (uint32_t)(a.thr_g[pp] >> 32) : 0u;
-            if constexpr (!LO) {  // (the k > 16 passes are never seeded)
+            if constexpr (!LO && MODE != 4) {  // (the k > 16 passes and the tagged scan are never seeded)
                 if (a.pair_pos && live) thr = std::min(thr, round0_seed(a, pp));
             }
+            if constexpr (MODE == 4) {
+                // (invq holds (1/|q|, want) pairs here, see Scan2Args; both
+                // lanes of a column write the same want word)
+                const uint2 iw = live ? reinterpret_cast<const uint2*>(a.invq)[q] : make_uint2(0u, 0u);
+                my_invq = __uint_as_float(iw.x);
+                lds_put_u32((uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 128) + (uint32_t)col * 4u, iw.y);
+            } else
             my_invq = live ? a.invq[q] : 0.0f;
             if constexpr (MODE == 1) {
                 // (no bound until every bin holds a finished list's 15th)
@@ -701,8 +773,21 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                         const float n1 = *reinterpret_cast<const float*>(nb + i * 4);
                         const float d = fmaf(-select16(acc, rg), my_invq * n1, 1.0f);
                         const uint64_t key = make_key(d, rb + (uint32_t)i);
+                        // (MODE 4) the candidate's tag word and the pair's want
+                        // word, both from LDS at addresses made here from the
+                        // lane id: nothing new is live around the walk
+                        auto tag_ok = [&] {
+                            const int l2 = opaque(ln);
+                            const uint32_t ts = (uint32_t)(uintptr_t)tag_area + (uint32_t)((eb % 3) * 128);
+                            const uint32_t tg = lds_get_u32(ts + (uint32_t)((l2 >> 5) * 16 + i * 4));
+                            const uint32_t want = lds_get_u32(
+                                (uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 128) + (uint32_t)(l2 & 31) * 4u);
+                            return (tg & want) == want;
+                        };
                         if (LO && d == lo_d && eb * 32 + 4 * hh + i < lo_row) {
                             // at or before the pair's lower bound: not this pass's
+                        } else if (MODE == 4 && !tag_ok()) {
+                            // (MODE 4) the row lacks a wanted bit: not a candidate
                         } else if (cnt < KL) {
                             // append mode: the first KL candidates are stored
                             // unsorted; a full buffer is sorted once (stable)
@@ -905,14 +990,15 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                 if (P[i] >= L[KL - 1]) break;
                 list_insert<KL>(L, P[i]);
             }
-            uint64_t* out = a.partial + ((size_t)pp * a.max_chunks + tile.chunk) * KL;
+            uint64_t* out = LMI_KARG(partial) + ((size_t)pp * a.max_chunks + tile.chunk) * KL;
 #pragma unroll
             for (int i = 0; i < KL; ++i) out[i] = L[i];
-            if (MODE == 0 && L[KL - 1] != kEmptyKey) atomicMin(&a.thr_g[pp], (unsigned long long)L[KL - 1]);
+            if ((MODE == 0 || MODE == 4) && L[KL - 1] != kEmptyKey) atomicMin(&a.thr_g[pp], (unsigned long long)L[KL - 1]);
             if (MODE == 1 && L[KL - 1] != kEmptyKey)
                 atomicMin(&a.bins[(size_t)pp * a.nbins + tile.chunk % a.nbins], (uint32_t)(L[KL - 1] >> 32));
         }
     }
+#undef LMI_KARG
     if constexpr (ABL != 0) {
         if (tid == 0) {
             const uint64_t clk1 = __builtin_amdgcn_s_memtime();
@@ -934,7 +1020,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
 // in two launches); HIP events around it while lmi_timing_enable is on
 template <int KL, int ABL, bool LO = false, int MODE = 0>
 int launch_scan3_v(const Scan2Args& b, hipStream_t s) {
-    constexpr size_t lds = v3::lds_bytes<KL>();
+    constexpr size_t lds = v3::lds_bytes<KL>() + (MODE == 4 ? v3::TAG_AREA + v3::WANT_AREA : 0);
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {

@@ -18,6 +18,7 @@ using half8 = _Float16 __attribute__((ext_vector_type(8)));
 using half4 = _Float16 __attribute__((ext_vector_type(4)));
 using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
+using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kWaves = 4;
@@ -47,6 +48,8 @@ struct ScanArgs {
     uint64_t* partial;      // [P][max_chunks][KL]
     const int32_t* gpos;    // [n_rows] global positions (LO: ties at the lower bound)
     const unsigned long long* lo_g;  // [nq*R] LO: keep only keys above (d, gpos) of the pair
+    const uint32_t* tags;   // TAG: [n_rows] tag word of every row (row order of corpus)
+    const uint32_t* want;   // TAG: [nq] want word of every query; row eligible iff (tag & want) == want
 };
 
 
@@ -148,6 +151,12 @@ struct Scan2Args {
     int32_t nbins;
     const int32_t* sub_rows;  // MODE 1: [C] rows per list of each bucket (its chunks)
     const int32_t* sub_take;  //   and the rows scanned from the start of each (a sample)
+    // MODE 4 (lmi_bucket_topk_tagged): the rows' tag words ([n_rows], row order
+    // of corpus); a row is a candidate of a pair only if (tag & want) == want.
+    // The queries' want words come beside 1/|q|: invq is then [nq] pairs
+    // (1/|q|, want) (want_pack_kernel) -- one pointer less in scalar registers,
+    // of which the kernel has none to spare
+    const uint32_t* tags;
 };
 
 // s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] + vmcnt[5:4] at [15:14],
@@ -197,7 +206,7 @@ int timing_record(hipStream_t s, bool start, std::pair<hipEvent_t, hipEvent_t>& 
 
 // lmi_scan_v12.hip (explicitly instantiated there for the shapes the host
 // dispatch in lmi_scan.hip uses)
-template <int KL, bool F16MATH, typename TC, bool LO = false>
+template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
 int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s);
 template <int KL>
 int launch_scan2(const Scan2Args& b, hipStream_t s);
@@ -226,7 +235,10 @@ struct ScanPlan {
     size_t qbuf, invq, counts, pair_q, pair_bucket, tiles, ntiles, work, partial, ext_off,
         split_mask, thr_g, pref, pref_tmp, pref_tmp2, n_seed, pair_pos, seed_pos, total;
 };
-ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false);
+// tagged: the plan of lmi_bucket_topk_tagged -- the untagged plan but that the
+// 4-wave ring's and the 8-wave ring's 15-entry shapes go to the general kernel
+ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false,
+                   bool tagged = false);
 // the 8-wave ring serves this index and query class (the float64 mode's band lists)
 bool band_capable(const lmi_index_desc* idx, int qmode);
 size_t scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
@@ -317,6 +329,10 @@ struct ScanCall {
     // scan_plan() of this call where the caller holds it (it reads the scan's
     // region afterwards); null: built here
     const ScanPlan* plan = nullptr;
+    // lmi_bucket_topk_tagged: device [n_rows] tag words and [nq] want words
+    // (both or neither); only rows with (tag & want) == want are listed
+    const uint32_t* tags = nullptr;
+    const uint32_t* want = nullptr;
 };
 int bucket_topk_impl(const ScanCall& c);
 

@@ -52,12 +52,16 @@ __device__ inline bool above_lo(float d, uint64_t lo, const int32_t* __restrict_
     return o > hi || (o == hi && (uint32_t)gpos[row] > (uint32_t)lo);
 }
 
-template <int KL, bool LO = false>
+// TAG (lmi_bucket_topk_tagged): only rows whose tag word holds every bit of
+// the query's want word are candidates, (tag & want) == want; tags is read
+// like inv_norm.
+template <int KL, bool LO = false, bool TAG = false>
 __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint64_t* thr_slot,
                                      float invq, const float* __restrict__ inv_norm,
                                      uint32_t row_base, int valid_rows, uint64_t* queue,
                                      int lane, uint64_t lo = 0,
-                                     const int32_t* __restrict__ gpos = nullptr) {
+                                     const int32_t* __restrict__ gpos = nullptr,
+                                     const uint32_t* __restrict__ tags = nullptr, uint32_t want = 0u) {
     const int h = lane >> 5;
     uint64_t thr = *thr_slot;
     float bound = key_dist_bound(thr);
@@ -68,7 +72,8 @@ __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint6
         const bool valid = i < valid_rows;
         const float inv = valid ? inv_norm[row_base + i] : 0.0f;
         const float d = fmaf(-acc[reg], invq * inv, 1.0f);
-        if (valid && d <= bound && (!LO || above_lo(d, lo, gpos, row_base + (uint32_t)i))) {
+        const bool tag_ok = !TAG || (valid && (tags[row_base + i] & want) == want);
+        if (valid && d <= bound && tag_ok && (!LO || above_lo(d, lo, gpos, row_base + (uint32_t)i))) {
             const uint64_t key = make_key(d, row_base + (uint32_t)i);
             if (key < thr) {
                 queue[cnt * 64] = key;
@@ -88,7 +93,7 @@ __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint6
                                    (unsigned long long)L[KL - 1]);
 }
 
-template <int KL, bool F16MATH, typename TC, bool LO = false>
+template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
 __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
     using Cfg = ScanCfg<KL, F16MATH>;
     using QT = typename Cfg::QT;
@@ -153,11 +158,13 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
 
         uint64_t L[NQF][KL];
         uint64_t lo[NQF];
+        uint32_t want[NQF];
 #pragma unroll
         for (int f = 0; f < NQF; ++f) {
             list_clear<KL>(L[f]);
             const int r = 32 * f + col;
             lo[f] = (LO && r < tile.np) ? (uint64_t)a.lo_g[a.pair_q[tile.pp0 + r]] : 0ull;
+            want[f] = (TAG && r < tile.np) ? a.want[a.pair_q[tile.pp0 + r] / a.R] : 0u;
         }
 
         const int nsub = (nrows + 31) / 32;
@@ -250,8 +257,8 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
 #pragma unroll
             for (int f = 0; f < NQF; ++f) {
                 const int qslot = 32 * f + col;
-                tile_epilogue<KL, LO>(acc[f], L[f], &thr_s[qslot], invq_s[qslot], a.inv_norm,
-                                      row_base, valid_rows, queue, lane, lo[f], a.gpos);
+                tile_epilogue<KL, LO, TAG>(acc[f], L[f], &thr_s[qslot], invq_s[qslot], a.inv_norm,
+                                           row_base, valid_rows, queue, lane, lo[f], a.gpos, a.tags, want[f]);
             }
         }
         __syncthreads();  // all waves done with Qs -> reuse as merge buffer
@@ -567,7 +574,7 @@ __global__ __launch_bounds__(kThreads, 1) void scan2_kernel(Scan2Args a) {
 
 }  // namespace
 
-template <int KL, bool F16MATH, typename TC, bool LO>
+template <int KL, bool F16MATH, typename TC, bool LO, bool TAG>
 int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s) {
     const size_t lds = scan_lds_bytes<KL, F16MATH>(d_pad);
     if (lds > 160 * 1024) {
@@ -577,7 +584,7 @@ int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s) {
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan_kernel<KL, F16MATH, TC, LO>,
+        attr_err = hipFuncSetAttribute((const void*)scan_kernel<KL, F16MATH, TC, LO, TAG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     LMI_HIP_TRY(attr_err);
@@ -587,7 +594,7 @@ int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s) {
         const int rc = timing_record(s, true, ev);
         if (rc != LMI_OK) return rc;
     }
-    hipLaunchKernelGGL((scan_kernel<KL, F16MATH, TC, LO>), dim3(num_cus()), dim3(kThreads), lds, s, a);
+    hipLaunchKernelGGL((scan_kernel<KL, F16MATH, TC, LO, TAG>), dim3(num_cus()), dim3(kThreads), lds, s, a);
     LMI_LAUNCH_CHECK("scan_kernel");
     if (timed) return timing_record(s, false, ev);
     return LMI_OK;
@@ -634,6 +641,12 @@ template int launch_scan<16, false, float>(const ScanArgs&, int, hipStream_t);
 template int launch_scan<16, true, _Float16, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan<16, false, _Float16, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan<16, false, float, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<10, true, _Float16, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<16, true, _Float16, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<10, false, _Float16, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<16, false, _Float16, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<10, false, float, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan<16, false, float, false, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan2<10>(const Scan2Args&, hipStream_t);
 template int launch_scan2<16>(const Scan2Args&, hipStream_t);
 

@@ -200,7 +200,7 @@ class LearnedIndex(Logger):
         return (refs[0] is data_search and refs[1] is labels and refs[2] is data_navigation.index
                 and t[0] == self._identity(data_navigation, data_search, labels))
 
-    def attach(self, data_navigation, data_search, pred_categories, capacity=None):
+    def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None):
         """Build the HBM index of data_search (rows in data_navigation's id
         order, bucket labels `pred_categories`) now, outside any timed call,
         and trust these objects: later search / search_single calls that pass
@@ -210,10 +210,12 @@ class LearnedIndex(Logger):
         reference has no such step (it re-gathers every bucket per call).
         `capacity`: rows to allocate the HBM index for (DeviceIndex's
         `capacity`), so that insert / delete with inplace=True can update it
-        inside its own store."""
+        inside its own store.  `tags` (an addition; default none): one 32-bit
+        tag word per object, in data_navigation's order (DeviceIndex's
+        `tags`), for filtered search: search(..., want=...)."""
         self._trusted = None
         self._cat_written = None
-        self._device_index(data_navigation, data_search, pred_categories, capacity=capacity)
+        self._device_index(data_navigation, data_search, pred_categories, capacity=capacity, tags=tags)
         # strong references to the trusted objects: while they are held, their
         # id()s and buffers cannot be reused by new objects (ADVICE r3)
         self._trusted = (self._identity(data_navigation, data_search, pred_categories),
@@ -226,10 +228,11 @@ class LearnedIndex(Logger):
         self._trusted = None
         self._cat_written = None
 
-    def _device_index(self, data_navigation, data_search, labels, capacity=None):
+    def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None):
         """DeviceIndex of data_search rows in data_navigation order (with a
-        store of at least `capacity` rows when given)."""
-        from .index import DeviceIndex
+        store of at least `capacity` rows when given; with `tags` a tagged
+        one -- a call without `tags` reuses the cached index, tagged or not)."""
+        from .index import DeviceIndex, check_tags
         fits = lambda ix: capacity is None or ix.capacity >= int(capacity)
         if self._is_attached(data_navigation, data_search, labels) and fits(self._index):
             return self._index
@@ -238,7 +241,12 @@ class LearnedIndex(Logger):
         ids = np.asarray(data_navigation.index)
         key = (content_key(ds), content_key(labels), content_key(ids),
                content_key(np.asarray(ds.index)) if hasattr(ds, "index") else None)
-        if self._index is not None and self._cache_key == key and fits(self._index):
+        if tags is not None:
+            tags = check_tags(tags, labels.size)
+            key = key + (content_key(tags),)
+        cached = self._cache_key is not None and \
+            (self._cache_key == key or (tags is None and self._cache_key[:4] == key))
+        if self._index is not None and cached and fits(self._index):
             return self._index
         # fp16 data (the real clip768 'emb') stays fp16 on its way to HBM;
         # float64 data keeps its float64 values for the float64 mode
@@ -255,7 +263,7 @@ class LearnedIndex(Logger):
         self._searcher = None
         pg = self._proc_group()
         shard = {} if pg is None else dict(rank=pg[1], world=pg[2], chunk_rows=pg[3])
-        self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, **shard)
+        self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, tags=tags, **shard)
         self._cache_key = key
         return self._index
 
@@ -281,7 +289,7 @@ class LearnedIndex(Logger):
     # ---- search -------------------------------------------------------------
     def search(self, data_navigation, queries_navigation, data_search, queries_search,
                pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference",
-               stop_mass=None, min_buckets=1, timings=None):
+               stop_mass=None, min_buckets=1, timings=None, want=None):
         """Search for k nearest neighbors of each query (LearnedIndex.py:22-101).
         `semantics="exact"` (an addition; default off) returns the exact top-k of
         the union of the probed buckets instead of the reference's round merge.
@@ -292,7 +300,11 @@ class LearnedIndex(Logger):
         query does not probe is a round whose `pred_categories` entry matches
         no category (:75-:80): it keeps what it had.  `timings` (measurement
         only): Searcher.search's per-stage times, and `mean_probes` with the
-        rule on."""
+        rule on.  `want` (an addition; needs attach(..., tags=...)): filtered
+        search, only objects with (tag & want) == want answer -- an int under
+        the reference semantics (the answer of this search over the eligible
+        objects alone), an int or one word per query under semantics="exact"
+        (Searcher.search)."""
         from .index import check_stop
         check_stop(stop_mass, min_buckets)
         assert self.model is not None, 'Model is not trained, call `build` first.'
@@ -306,7 +318,7 @@ class LearnedIndex(Logger):
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist=dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
-                                                timings=timings)
+                                                timings=timings, want=want)
 
     def mean_probes(self, data_navigation, queries_navigation, data_search, pred_categories,
                     n_buckets, stop_mass, min_buckets=1):
@@ -403,7 +415,7 @@ class LearnedIndex(Logger):
         self._attached_labels = labels
 
     def insert(self, data_navigation, data_search, pred_categories, new_navigation, new_search,
-               inplace=False):
+               inplace=False, new_tags=None):
         """Add objects to the index without a rebuild: the router labels the
         new navigation rows (`predict`, as `build` labels the data), the frames
         and labels are concatenated on the host and the HBM index takes the
@@ -419,7 +431,8 @@ class LearnedIndex(Logger):
         existing ones raise ValueError.  `inplace` (default off): the rows
         move inside the index's own store (DeviceIndex.add(inplace=True); the
         index needs the room: attach(..., capacity=...)) -- same frames, same
-        answers, no second corpus in HBM."""
+        answers, no second corpus in HBM.  `new_tags` (a tagged index only):
+        the new objects' tag words, default 0 (DeviceIndex.add's `tags`)."""
         import pandas as pd
         assert self.model is not None, 'Model is not trained, call `build` first.'
         new_ids = np.asarray(new_navigation.index)
@@ -439,7 +452,7 @@ class LearnedIndex(Logger):
             rows = ds.loc[new_navigation.index].to_numpy(dtype=dt)
         else:
             rows = np.asarray(ds, dtype=dt)
-        new_index = index.add(rows, new_labels, ids=new_ids, inplace=inplace)
+        new_index = index.add(rows, new_labels, ids=new_ids, tags=new_tags, inplace=inplace)
         labels2 = np.concatenate([np.asarray(pred_categories).astype(np.int64), new_labels])
         nav2 = pd.concat([nav_old, nav_new])
         nav2["category"] = labels2                     # what search() writes (:67)

@@ -76,6 +76,8 @@ EXPORTS = (
     "lmi_plan_chunks",
     "lmi_scan_workspace_bytes",
     "lmi_bucket_topk",
+    "lmi_scan_tagged_workspace_bytes",
+    "lmi_bucket_topk_tagged",
     "lmi_merge_topk",
     "lmi_scan_f64_workspace_bytes",
     "lmi_bucket_topk_f64",
@@ -195,6 +197,9 @@ _SIGNATURES = {
     "lmi_scan_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,
                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_scan_tagged_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
+    "lmi_bucket_topk_tagged": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32,
+                                         _I32, _P, _P, _P, _P, C.c_size_t, _P]),
     "lmi_merge_topk": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "lmi_scan_f64_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_f64": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,

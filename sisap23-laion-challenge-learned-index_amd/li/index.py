@@ -348,6 +348,27 @@ class BucketLayout:
         shift = np.repeat(new_off[:-1] - surv_off[:-1], np.diff(surv_off))
         out[np.arange(kept.size, dtype=np.int64) + shift] = kept
 
+    @staticmethod
+    def updated_table(table, drop, surv_off, new_off, new_dst, new_values) -> np.ndarray:
+        """A per-position table (pos_to_id, tags_by_pos) after updated(): the
+        survivors' entries at the front of every bucket's new range, the new
+        rows' `new_values` at `new_dst`.  `drop`: the ascending dropped
+        positions; the other arguments as updated() returns them."""
+        table = np.asarray(table)
+        out = np.empty(int(new_off[-1]), table.dtype)
+        BucketLayout.place_survivors(np.delete(table, drop) if len(drop) else table, surv_off, new_off, out)
+        out[new_dst] = new_values
+        return out
+
+    @staticmethod
+    def relabel_source(old_order, new_order) -> np.ndarray:
+        """src[p]: the position at which a layout of order `old_order` holds
+        the row of position p of a layout of order `new_order` over the same
+        row sequence -- a per-position table moves as table[src]."""
+        inv = np.empty(old_order.size, np.int64)
+        inv[old_order] = np.arange(old_order.size, dtype=np.int64)
+        return inv[new_order]
+
     def shard(self, rank: int, world: int):
         """(global positions of the shard's rows, local bucket offsets [C+1])."""
         if world == 1:
@@ -361,6 +382,42 @@ class BucketLayout:
             parts.append(np.arange(lo, hi, dtype=np.int64))
             loc[c + 1] = loc[c] + (hi - lo)
         return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), loc
+
+
+# ---------------------------------------------------------------------------
+# tags (filtered search: lmi_bucket_topk_tagged)
+# ---------------------------------------------------------------------------
+def check_tags(tags, n: int) -> np.ndarray:
+    """`tags` (any integer array, one word per row, values in [0, 2^32)) as
+    uint32 [n]; ValueError otherwise."""
+    t = tags.cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)
+    if t.dtype.kind not in "iu":
+        raise ValueError("tags must be integers")
+    t = t.ravel()
+    if t.shape != (n,):
+        raise ValueError(f"tags must have one word per row ({n})")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= 1 << 32):
+        raise ValueError("tags must lie in [0, 2^32)")
+    return np.ascontiguousarray(t.astype(np.uint32))
+
+
+def eligible_counts(tags_by_pos, bucket_off, want: int) -> np.ndarray:
+    """int64 [C]: the rows of every bucket with (tag & want) == want -- a
+    segmented count over `bucket_off` ([C+1] positions into `tags_by_pos`),
+    done in torch.  The reference replay of a filtered search reads these as
+    its bucket sizes (the < k quirk, the empty-bucket skip)."""
+    w = int(want)
+    t = torch.from_numpy(np.ascontiguousarray(tags_by_pos, dtype=np.uint32).astype(np.int64))
+    ok = (t & w) == w
+    cs = torch.zeros(t.numel() + 1, dtype=torch.int64)
+    torch.cumsum(ok, 0, out=cs[1:])
+    off = torch.from_numpy(np.ascontiguousarray(bucket_off, dtype=np.int64))
+    return (cs[off[1:]] - cs[off[:-1]]).numpy()
+
+
+def _as_i32_bits(a: np.ndarray) -> torch.Tensor:
+    """uint32 words as an int32 tensor of the same bits (torch has no uint32 gather)."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32))
 
 
 # ---------------------------------------------------------------------------
@@ -401,12 +458,23 @@ class DeviceIndex:
     inv_norm64 = None
     _desc64 = None
     consumed = False   # True once an in-place update has taken this index's store (K9)
+    # filtered search: every row's 32-bit tag word -- tags_by_pos host uint32
+    # [n_total], parallel to pos_to_id; tags device [n_rows] (the words as
+    # int32 bits) = tags_by_pos[gpos], a striped shard's own rows'.  None: an
+    # untagged index
+    tags_by_pos = None
+    tags = None
 
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
                  storage: str = "auto", chunk_rows: Optional[int] = None,
                  rank: int = 0, world: int = 1, subcluster: bool = False,
-                 capacity: Optional[int] = None):
-        """`capacity` (None: as many rows as the index holds, today's
+                 capacity: Optional[int] = None, tags=None):
+        """`tags` (None: an untagged index): one 32-bit tag word per input row,
+        any integer array with values in [0, 2^32), for filtered search
+        (Searcher.lists / search with `want`: a row is eligible for a query iff
+        (tag & want) == want).  Not with subcluster=True (ValueError).
+
+        `capacity` (None: as many rows as the index holds, today's
         allocation): the rows the corpus and 1/||y|| stores are allocated for,
         so that add / remove with inplace=True can grow the index inside them
         (K9).  `corpus` and `inv_norm` are the leading [n_rows] views of the
@@ -427,6 +495,10 @@ class DeviceIndex:
         if ids.shape != (n,):
             raise ValueError("ids must have one entry per corpus row")
         self.pos_to_id = ids[self.layout.order]
+        if tags is not None:
+            if subcluster:
+                raise ValueError("tags: a sub-cluster layout (subcluster=True) takes no tags")
+            self.tags_by_pos = check_tags(tags, n)[self.layout.order]
         self.bucket_size = self.layout.bucket_size.copy()
         self.rank, self.world = rank, world
 
@@ -445,6 +517,8 @@ class DeviceIndex:
             self._fill(data, gpos, storage)
         self.gpos = torch.from_numpy(gpos.astype(np.int32)).to(self.device)
         self.n_rows = int(gpos.size)
+        if self.tags_by_pos is not None:
+            self.tags = _as_i32_bits(self.tags_by_pos[gpos]).to(self.device)
         cf = self._plan_tables(loc_off, chunk_rows)
         self.chunk_centroid = None
         if subcluster and self.n_chunks > 0:
@@ -478,14 +552,18 @@ class DeviceIndex:
     # ---- updates (K7: csrc/lmi_update.hip) ----------------------
     @classmethod
     def empty(cls, d: int, n_buckets: int, *, device=None, chunk_rows: Optional[int] = None,
-              capacity: Optional[int] = None) -> "DeviceIndex":
+              capacity: Optional[int] = None, tags=None) -> "DeviceIndex":
         """A one-GPU fp16 index of `n_buckets` empty buckets for rows of `d`
         values, to be filled by `add`: what a construction over zero rows
-        gives.  `capacity`: rows to reserve for add(..., inplace=True)."""
+        gives.  `capacity`: rows to reserve for add(..., inplace=True).
+        `tags`: True or an empty integer array for a tagged index (its rows
+        then come with add(..., tags=...)); None for an untagged one."""
         if int(d) < 1:
             raise ValueError("d must be positive")
+        if tags is not None:
+            tags = np.zeros(0, np.uint32) if tags is True else tags
         return cls(np.zeros((0, int(d)), np.float16), np.zeros((0,), np.int64), n_buckets,
-                   device=device, storage="f16", chunk_rows=chunk_rows, capacity=capacity)
+                   device=device, storage="f16", chunk_rows=chunk_rows, capacity=capacity, tags=tags)
 
     # ---- the row store (K9: reserved capacity; DESIGN.md §3) -------------------
     def _alloc_store(self, n_rows: int, dtype=torch.float16, zero: bool = False, capacity=None):
@@ -519,7 +597,7 @@ class DeviceIndex:
     def _consume(self):
         """Drop the device arrays and mark the index consumed."""
         self.consumed = True
-        for name in ("corpus", "inv_norm", "_store", "_store_inv", "gpos", "bucket_off_local",
+        for name in ("corpus", "inv_norm", "_store", "_store_inv", "gpos", "tags", "bucket_off_local",
                      "bucket_rows", "chunk_first", "_desc", "_desc32", "inv_norm64", "_desc64"):
             setattr(self, name, None)
         self._ws = {}
@@ -532,7 +610,7 @@ class DeviceIndex:
         self._check_updatable()
         if int(rows) < self.n_rows:
             raise ValueError(f"reserve: {int(rows)} rows are below the {self.n_rows} rows of the index")
-        new = self._successor(self.layout, self.pos_to_id, int(rows))
+        new = self._successor(self.layout, self.pos_to_id, int(rows), self.tags_by_pos)
         new.corpus.copy_(self.corpus)
         new.inv_norm.copy_(self.inv_norm)
         if self.inv_norm64 is not None:
@@ -540,7 +618,7 @@ class DeviceIndex:
         torch.cuda.current_stream(self.device).synchronize()
         return new
 
-    def _successor(self, layout, pos_to_id, capacity: int) -> "DeviceIndex":
+    def _successor(self, layout, pos_to_id, capacity: int, tags_by_pos=None) -> "DeviceIndex":
         """A one-GPU fp16 index over `layout` / `pos_to_id` with this one's
         shape and chunk rule: every table, and fresh stores of `capacity`
         rows (or more, when the layout holds more) whose rows the caller
@@ -555,12 +633,19 @@ class DeviceIndex:
         new.bucket_size = layout.bucket_size.copy()
         new._plan_tables(layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
         new.gpos = torch.arange(n_new, dtype=torch.int32, device=self.device)
+        new._set_tags(tags_by_pos)
         new.chunk_centroid = None
         new._ws = {}
         if capacity is not None:
             new._alloc_store(n_new, capacity=capacity)
             new._desc = IndexDescHolder(new)
         return new
+
+    def _set_tags(self, tags_by_pos):
+        """The tag tables of a one-GPU index (gpos = every position): the host
+        table and its upload; None: an untagged index."""
+        self.tags_by_pos = tags_by_pos
+        self.tags = None if tags_by_pos is None else _as_i32_bits(tags_by_pos).to(self.device)
 
     def _check_updatable(self):
         """What add / remove support, refused before any device work."""
@@ -576,8 +661,9 @@ class DeviceIndex:
             raise ValueError("index update: an index with a sub-cluster layout (chunk_centroid) is "
                              "not supported")
 
-    def add(self, rows, labels, ids=None, *, inplace: bool = False, slab_rows: Optional[int] = None,
-            direct_rows: Optional[int] = None, timings: Optional[dict] = None) -> "DeviceIndex":
+    def add(self, rows, labels, ids=None, tags=None, *, inplace: bool = False,
+            slab_rows: Optional[int] = None, direct_rows: Optional[int] = None,
+            timings: Optional[dict] = None) -> "DeviceIndex":
         """A NEW index with the batch appended to the row sequence: every row
         goes to the end of the bucket `labels` names for it (host or device
         integers), in batch order -- bitwise the index a construction from
@@ -585,7 +671,8 @@ class DeviceIndex:
         is not touched.  `rows`: host or device, [m, d] fp16, or fp32 whose
         values are fp16-exact (ValueError otherwise).  `ids` default to the
         ids after the largest one present; ids that repeat or are present
-        already raise ValueError.
+        already raise ValueError.  `tags` (a tagged index only, ValueError on
+        an untagged one): the new rows' tag words, default 0.
 
         inplace=True (K9): the rows move inside this index's own store, which
         the returned index takes over (same corpus.data_ptr()); no second
@@ -622,8 +709,14 @@ class DeviceIndex:
             raise ValueError("duplicate ids among the new rows")
         if m and np.isin(self.pos_to_id, ids).any():
             raise ValueError("ids of new rows are already in the index")
+        if tags is not None and self.tags_by_pos is None:
+            raise ValueError("tags: this index is untagged (build it with `tags`)")
+        new_tags = None
+        if self.tags_by_pos is not None:
+            new_tags = np.zeros(m, np.uint32) if tags is None else check_tags(tags, m)
         return self._updated(np.zeros(0, np.int64), rows, lab, ids, inplace=inplace,
-                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
+                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings,
+                             new_tags=new_tags)
 
     def remove(self, ids, *, inplace: bool = False, slab_rows: Optional[int] = None,
                direct_rows: Optional[int] = None, timings: Optional[dict] = None) -> "DeviceIndex":
@@ -740,6 +833,7 @@ class DeviceIndex:
         src_pos = inv[order]
         del inv, old_order
         p2id = torch.from_numpy(self.pos_to_id).to(dev)[src_pos]
+        old_tags, old_layout_order = self.tags_by_pos, self.layout.order
         mark("tables")
         new = object.__new__(DeviceIndex)
         new.device, new.n_buckets = dev, C_
@@ -766,6 +860,9 @@ class DeviceIndex:
         new.bucket_size = new.layout.bucket_size.copy()
         new._plan_tables(new.layout.bucket_off.copy(), chunk_rows)
         new.gpos = torch.arange(n, dtype=torch.int32, device=dev)
+        # the tags move as pos_to_id does (on the host, then uploaded)
+        new._set_tags(None if old_tags is None else
+                      old_tags[BucketLayout.relabel_source(old_layout_order, new.layout.order)])
         new.chunk_centroid = None
         new._desc = IndexDescHolder(new)
         new._ws = {}
@@ -860,7 +957,7 @@ class DeviceIndex:
 
     @torch.no_grad()
     def _updated(self, drop, rows, lab, ids, *, inplace=False, slab_rows=None, direct_rows=None,
-                 timings=None) -> "DeviceIndex":
+                 timings=None, new_tags=None) -> "DeviceIndex":
         """The index after dropping the global positions `drop` (ascending)
         and appending the batch: host tables by index arithmetic
         (BucketLayout.updated), rows by the K7 kernels into new stores -- or,
@@ -900,7 +997,12 @@ class DeviceIndex:
         BucketLayout.place_survivors(np.delete(self.pos_to_id, drop) if r else self.pos_to_id, surv_off,
                                      layout.bucket_off, p2id)
         p2id[new_dst] = ids
-        new = self._successor(layout, p2id, None if inplace else max(self.capacity, n_new))
+        t_by_pos = None
+        if self.tags_by_pos is not None:
+            t_by_pos = BucketLayout.updated_table(
+                self.tags_by_pos, drop, surv_off, layout.bucket_off, new_dst,
+                new_tags if new_tags is not None else np.zeros(m, np.uint32))
+        new = self._successor(layout, p2id, None if inplace else max(self.capacity, n_new), t_by_pos)
         ev = None
         if timings is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -1384,7 +1486,7 @@ def _workspace(ws, need: int, what: str) -> torch.Tensor:
 
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                 qmode: Optional[int] = None, stream=None, out=None, ws=None,
-                seed_round0: bool = False, phases: int = 0):
+                seed_round0: bool = False, phases: int = 0, want=None):
     """K2 on one shard.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
     `out` = such a triple to write into (the status word zeroed by the caller);
     `ws` = a caller-owned uint8 workspace (default: the index's cached one,
@@ -1392,7 +1494,10 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     passes its own).  `seed_round0` (LMI_Q_SEED_ROUND0, the thresholded
     replay only): probes r >= 1 keep only objects under the round-0 bound.
     `phases` (LMI_Q_PHASE_* bits, 0 = all): run only those phases of the call
-    (StreamedSearch overlaps one batch's plan with another's scan)."""
+    (StreamedSearch overlaps one batch's plan with another's scan).
+    `want` (a tagged index; device int32 [nq], the want words' bits, see
+    want_words): the tagged scan, lmi_bucket_topk_tagged -- only rows with
+    (tag & want) == want are listed; never seeded, no phases."""
     lib = _lib.load()
     q = _rows_f32(q, index.device)
     classes = _as_torch(classes, index.device, torch.int32)
@@ -1401,6 +1506,8 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
         raise ValueError("query shape does not match the index")
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    if want is not None:
+        return _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phases)
     desc = index.desc_for(k)
     if out is None:
         out_d = torch.empty((nq, R, k), dtype=torch.float32, device=index.device)
@@ -1419,6 +1526,74 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     check("lmi_bucket_topk", lib.lmi_bucket_topk(C.byref(desc), ptr(q), nq, q.stride(0),
                                                  ptr(classes), R, k, qmode | flags, ptr(out_d),
                                                  ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
+    return out_d, out_pos, status
+
+
+def want_words(index: DeviceIndex, want, nq: int, k_list: int, dist: str = "f32",
+               per_query: bool = True) -> torch.Tensor:
+    """The want words of a filtered scan as a device int32 [nq] tensor (the
+    uint32 words' bits), after every check a filtered call makes before it
+    launches or allocates anything: ValueError on an untagged index, on
+    dist="f64", on storage "f32x", on k_list > LMI_MAX_K, and for a `want` that
+    is neither an integer in [0, 2^32) nor (per_query) an integer array [nq]
+    of such."""
+    if index.tags is None:
+        raise ValueError("want: this index is untagged (build it with `tags`)")
+    if dist != "f32":
+        raise ValueError("want: filtered search is not offered with dist='f64'")
+    if index.storage == "f32x":
+        raise ValueError("want: filtered search is not offered on storage 'f32x' (the split mode)")
+    if k_list > _lib.LMI_MAX_K:
+        raise ValueError(f"want: filtered search takes lists of at most {_lib.LMI_MAX_K} entries, not {k_list}")
+    if isinstance(want, (int, np.integer)) and not isinstance(want, bool):
+        if not 0 <= int(want) < 1 << 32:
+            raise ValueError("want must lie in [0, 2^32)")
+        w = np.full(nq, int(want), np.uint32)
+    else:
+        if not per_query:
+            raise ValueError("want: semantics='reference' takes one want word for the whole batch (an int): "
+                             "its round merge couples the queries of a batch")
+        w = want.cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want)
+        if w.dtype.kind not in "iu" or w.shape != (nq,):
+            raise ValueError(f"want must be an integer or an integer array of shape [{nq}]")
+        if w.size and (int(w.min()) < 0 or int(w.max()) >= 1 << 32):
+            raise ValueError("want must lie in [0, 2^32)")
+        w = w.astype(np.uint32)
+    return _as_i32_bits(w).to(index.device)
+
+
+def _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phases):
+    """bucket_topk's tagged call (q, classes already on the device)."""
+    lib = _lib.load()
+    nq, R = classes.shape
+    if index.tags is None:
+        raise ValueError("want: this index is untagged (build it with `tags`)")
+    if phases:
+        raise ValueError("want: the tagged scan runs whole (no phases)")
+    if not (isinstance(want, torch.Tensor) and want.dtype == torch.int32 and want.shape == (nq,)
+            and want.device == q.device and want.is_contiguous()):
+        raise ValueError("want must be a device int32 tensor [nq] (want_words)")
+    desc = index.desc_for(k)
+    need = lib.lmi_scan_tagged_workspace_bytes(C.byref(desc), nq, R, k, qmode)
+    if need == 0 and nq:
+        raise ValueError("want: this index or call takes no tagged scan "
+                         "(k > 16, the split mode or a sub-cluster layout)")
+    if out is None:
+        out_d = torch.empty((nq, R, k), dtype=torch.float32, device=index.device)
+        out_pos = torch.empty((nq, R, k), dtype=torch.int32, device=index.device)
+        status = torch.zeros((1,), dtype=torch.int32, device=index.device)
+    else:
+        out_d, out_pos, status = out
+    if ws is None:
+        ws = index._ws.get("buf")
+        if ws is None or ws.numel() < need:
+            ws = index._ws["buf"] = torch.empty(max(need, 256), dtype=torch.uint8, device=index.device)
+    else:
+        _workspace(ws, need, "tagged scan")
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_bucket_topk_tagged", lib.lmi_bucket_topk_tagged(
+        C.byref(desc), ptr(index.tags), ptr(want), ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode,
+        ptr(out_d), ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
     return out_d, out_pos, status
 
 
@@ -1709,12 +1884,13 @@ class Searcher:
         return mode
 
     def _scan(self, q_search, classes, k_list: int, qmode: int, f64: bool, lap=None,
-              status_out=None, ws=None, seed_round0: bool = False):
+              status_out=None, ws=None, seed_round0: bool = False, want=None):
         """K2 on this shard (+ all-gather and K3 for G > 1 ranks, the status
         words riding along so every rank sees every rank's bits).  `lap`
         (measurement only) is called after the scan and after the exchange.
         `status_out` (a zeroed device int32 word): the status lands there.
-        `ws`: a caller-owned scan workspace (GraphedSearch's)."""
+        `ws`: a caller-owned scan workspace (GraphedSearch's).  `want`: the
+        want words of a filtered scan (want_words; float32 lists only)."""
         out = None
         if not self.exchange and status_out is not None:
             nq, R = classes.shape
@@ -1750,7 +1926,7 @@ class Searcher:
                                              out=out, ws=ws, seed_round0=seed_round0)
         else:
             d, pos, status = bucket_topk(self.index, q_search, classes, k_list, qmode=qmode, out=out,
-                                         ws=ws, seed_round0=seed_round0)
+                                         ws=ws, seed_round0=seed_round0, want=want)
         if lap:
             lap("scan")
         if self.exchange:
@@ -1764,16 +1940,23 @@ class Searcher:
 
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
-              min_probes: int = 1):
+              min_probes: int = 1, want=None):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
         `stop_mass`, `min_probes`: the router's stop rule (DeviceRouter.topr);
-        a dropped probe's list is (+inf, -1)."""
+        a dropped probe's list is (+inf, -1).  `want` (a tagged index; an int
+        or an integer array [nq], words in [0, 2^32)): filtered lists -- each
+        the exact top-k_list of the bucket's rows with (tag & want) == want,
+        padded (+inf, -1); the lists of an index built from those rows alone."""
         check_stop(stop_mass, min_probes)
         self.index._check_live()
+        if want is not None:
+            nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
+            want = want_words(self.index, want, nq, k_list, dist)
         if classes is None:
             classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
-        d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64")
+        d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
+                                    want=want)
         return classes, d, pos, status
 
     def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
@@ -1789,6 +1972,16 @@ class Searcher:
         if stop_mass is None:
             return self.router.topr(q_nav, R)[0]
         return self.router.topr(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)[0]
+
+    def eligible_bucket_size(self, want: int) -> np.ndarray:
+        """The eligible rows of every bucket of the whole index under the want
+        word `want` (eligible_counts, cached per word): the reference replay's
+        bucket_size of a filtered search."""
+        cache = self.__dict__.setdefault("_eligible", {})
+        w = int(want)
+        if w not in cache:
+            cache[w] = eligible_counts(self.index.tags_by_pos, self.index.layout.bucket_off, w)
+        return cache[w]
 
     def _device_tables(self):
         """bucket sizes and position -> id map in HBM for the device replay."""
@@ -1817,8 +2010,18 @@ class Searcher:
                use_threshold: bool = True, classes: Optional[torch.Tensor] = None,
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
-               min_probes: int = 1):
+               min_probes: int = 1, want=None):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `want` (a tagged index): filtered search -- only rows with
+        (tag & want) == want answer.  semantics="exact" takes an int or an
+        integer array [nq] (a word per query); semantics="reference" takes one
+        int for the whole batch (its round merge couples the batch's queries)
+        and answers as search() on the index built from the eligible rows
+        alone: the replay reads every bucket's eligible row count as its size.
+        The filtered scan is never seeded.  ValueError before anything is
+        launched on an untagged index, with dist="f64", storage "f32x", lists
+        of more than 16 entries or a malformed `want`.
 
         `stop_mass` (None: off): adaptive probing -- R is the cap, and each
         query stops at the first probe before which the router's probability
@@ -1864,6 +2067,10 @@ class Searcher:
         if k_round > _lib.LMI_REPLAY_DEVICE_MAX_KR or k > _lib.LMI_REPLAY_DEVICE_MAX_K:
             replay_on = "host"  # the device replay holds rows of <= 32 / 64 entries
         dev = self.index.device
+        want_w = None
+        if want is not None:
+            nq_w = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
+            want_w = want_words(self.index, want, nq_w, k_list, dist, per_query=semantics == "exact")
         sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
 
         def lap(name, t0):
@@ -1899,10 +2106,15 @@ class Searcher:
         # (valid while the merged width k is at most the round lists' k_round:
         # the running threshold then never exceeds round 0's k-th distance;
         # with k > k_round the first merge pads with 10000s)
-        seed = semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
+        seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
+                and want_w is None)
         d, pos, status = self._scan(q_search, classes, k_list, qmode, f64, lap_at if sync else None,
                                     status_out=None if ans is None else ans[3][0:1],
-                                    seed_round0=seed)
+                                    seed_round0=seed, want=want_w)
+        # (filtered: the replay's bucket sizes are the eligible row counts)
+        bsize = self.index.bucket_size
+        if want_w is not None and semantics == "reference":
+            bsize = self.eligible_bucket_size(int(want))
         t0 = tl[0]
         h_st = self._host("st", (2,), torch.int32)
 
@@ -1937,7 +2149,7 @@ class Searcher:
             t0 = lap("d2h", t0)
             if check_status(int(h_st[0])):
                 # the cached fp16 check was stale: redo with exact fp32 MFMA
-                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64)
+                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64, want=want_w)
                 rd, ra = exact(d, pos)
                 h_d.copy_(rd)
                 h_a.copy_(ra)
@@ -1946,6 +2158,8 @@ class Searcher:
             return done((h_d.numpy().copy(), h_a.numpy().view(np.uint32).copy()))
         if replay_on == "device":
             bsz, p2id = self._device_tables()
+            if want_w is not None:  # (here semantics == "reference")
+                bsz = torch.from_numpy(np.ascontiguousarray(bsize, dtype=np.int64)).to(dev)
 
             def run_replay(d, pos, ans):
                 replay_device(classes, d, pos, k_round=k_round, k_final=k, bucket_size=bsz,
@@ -1966,7 +2180,7 @@ class Searcher:
             if check_status(st0, st1):
                 ans = answer_buffer(nq, w_ans, dev)
                 d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                            status_out=ans[3][0:1], seed_round0=seed)
+                                            status_out=ans[3][0:1], seed_round0=seed, want=want_w)
                 h = run_replay(d, pos, ans)
                 torch.cuda.current_stream(dev).synchronize()
                 hd, ha, st0, st1 = answer_views(h, nq, w_ans)
@@ -1983,13 +2197,13 @@ class Searcher:
         t0 = lap("d2h", t0)
         if check_status(int(h_st[0])):
             d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                        seed_round0=seed)
+                                        seed_round0=seed, want=want_w)
             h_d.copy_(d)
             h_pos.copy_(pos)
             h_st[0:1].copy_(status)
             check_status(int(h_st[0]) & ~_lib.LMI_STATUS_QUERY_NOT_F16)
         out = replay(h_cls.numpy(), h_d.numpy(), h_pos.numpy(), k_round=k_round, k_final=k,
-                     bucket_size=self.index.bucket_size, pos_to_id=self.index.pos_to_id,
+                     bucket_size=bsize, pos_to_id=self.index.pos_to_id,
                      use_threshold=use_threshold)
         lap("replay", t0) if sync else None
         return done(out)
