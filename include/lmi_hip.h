@@ -302,6 +302,64 @@ int lmi_bucket_topk_tagged(const lmi_index_desc* idx, const uint32_t* tags, cons
                            int32_t R, int32_t k, int32_t qmode, float* out_d, int32_t* out_pos,
                            int32_t* status, void* workspace, size_t ws_bytes, void* stream);
 
+/* K11 range search: every row of the probed buckets within a per-query bound.
+ *
+ * lmi_bucket_range is the collect scan.  For pair p = q * R + r it writes
+ *   count[p]                 uint32: the rows of bucket classes[p] with
+ *                            d(q, row) <= bound[q] (inclusive), and with
+ *                            (tag & want[q]) == want[q] when tags / want are
+ *                            given (both or neither; null: untagged).  Exact
+ *                            whatever pair_cap is.
+ *   cand[p * pair_cap + i]   uint64, i < min(count[p], pair_cap): hits as
+ *                            (distance ordinal << 32 | shard-local row), the
+ *                            ordinal the order-preserving image of the float32
+ *                            distance; in the scan's arrival order (unsorted).
+ *                            A pair with count[p] > pair_cap holds pair_cap of
+ *                            its hits, which ones is not defined: scan it
+ *                            again with a larger pair_cap.
+ * d is the float32 distance the top-k lists of the same kernel family hold for
+ * that (query, row).  classes entries outside [0, n_buckets) probe nothing; a
+ * bucket named twice in one query's row answers twice.  bound: device [nq]
+ * float (-inf or any negative value: nothing).  qmode: LMI_Q_F16 or LMI_Q_F32
+ * alone.  An fp16 corpus with LMI_Q_F16 and d_pad 768, untagged, runs the
+ * 8-wave ring's collect scan (scan3_kernel MODE 2); every other call the
+ * general kernel's collect form (range_scan_kernel).  Refused before any
+ * launch, with a message: the split mode (corpus32 / corpus64), sub-cluster
+ * layouts (chunk_centroid), phase / join / seed flags, join workgroups set on
+ * the calling thread, pair_cap outside [1, 2^24], and on the general kernel a
+ * d_pad whose query tile exceeds a workgroup's LDS (d_pad > 1248;
+ * LMI_E_UNSUPPORTED).  lmi_range_workspace_bytes gives the workspace (0 for
+ * what the call refuses, that width included; tagged != 0: the call has tags).
+ *
+ * lmi_range_rescore_f64: float64 distances of the stored candidates, in the
+ * arithmetic and with the bits of lmi_bucket_topk_f64: d64[p * pair_cap + i]
+ * for i < count[p], and kept[p] = how many have d64 <= radius64[q].  Pairs
+ * with count[p] > pair_cap get kept[p] = 0 and no d64.  q: the float32 queries.
+ *
+ * lmi_range_pack: every pair with count[p] <= pair_cap writes its stored
+ * candidates to entries off[p] .. of out_d (float64), out_pos (global
+ * position) and out_q (query), unsorted; off: device [nq * R] int64, the
+ * exclusive prefix of the entries each pair writes.  With d64 / radius64 (both
+ * or neither) only candidates with d64 <= radius64[q] are written, d64 as the
+ * distance (off: the prefix of kept); else the float32 distance, widened.
+ * Pairs with count[p] > pair_cap write nothing: the second scan's call fills
+ * their entries.
+ * Additions: LMI_ABI_VERSION does not change. */
+size_t lmi_range_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t qmode,
+                                 int32_t tagged, int32_t pair_cap);
+int lmi_bucket_range(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* want,
+                     const float* q, int32_t nq, int32_t ldq, const int32_t* classes, int32_t R,
+                     int32_t qmode, const float* bound, int32_t pair_cap, uint64_t* cand,
+                     uint32_t* count, int32_t* status, void* workspace, size_t ws_bytes,
+                     void* stream);
+int lmi_range_rescore_f64(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq,
+                          int32_t R, const double* radius64, int32_t pair_cap, const uint64_t* cand,
+                          const uint32_t* count, double* d64, uint32_t* kept, void* stream);
+int lmi_range_pack(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t pair_cap,
+                   const uint64_t* cand, const uint32_t* count, const int64_t* off,
+                   const double* d64, const double* radius64, double* out_d, int32_t* out_pos,
+                   int32_t* out_q, void* stream);
+
 /* Merge G per-shard lists of the same rows (K3): in
  * device [G][rows][k] (d f32, pos int32, -1 = empty), out device [rows][k] =
  * the k smallest by (d, pos).  Used after the RCCL all-gather of a G-GPU index.

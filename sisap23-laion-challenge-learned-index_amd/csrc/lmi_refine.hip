@@ -689,8 +689,77 @@ int num_cus_ref() {
     return n;
 }
 
+// K11 range search in float64 (lmi_range_rescore_f64): one wave per pair holds
+// its query's q^ and walks the pair's collected candidates (keys of the collect
+// scan, lmi_range.hip): d64[pair * cap + i] = row_dist64 of candidate i -- the
+// bits lmi_bucket_topk_f64 gives that (query, row) -- and kept[pair] = how many
+// have d64 <= radius64[q].  A pair whose count exceeds cap is left to the
+// second scan's call (kept = 0).
+template <typename TC>
+__global__ __launch_bounds__(kRefT) void range_rescore_kernel(const TC* __restrict__ corpus, int32_t d,
+                                                              int32_t d_pad, int64_t n_rows,
+                                                              const float* __restrict__ q, int32_t ldq, int64_t P,
+                                                              int32_t R, const double* __restrict__ radius64,
+                                                              const uint64_t* __restrict__ cand,
+                                                              const uint32_t* __restrict__ count, int32_t cap,
+                                                              double* __restrict__ d64, uint32_t* __restrict__ kept) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (kRefT / 64) + (threadIdx.x >> 6);
+    if (p >= P) return;  // (wave-uniform)
+    const uint32_t n = count[p];
+    if (n == 0 || n > (uint32_t)cap) {
+        if (lane == 0) kept[p] = 0u;
+        return;
+    }
+    const int nps = (d + 255) / 256;
+    double qh[kMaxPieces][4];
+    query_hat<float>(q + (size_t)(p / R) * ldq, d, nps, qh);
+    const double r = radius64[p / R];
+    uint32_t nk = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t row = (uint32_t)cand[(size_t)p * cap + i];
+        // (a row past the shard cannot come from the scan; score row 0, keep nothing)
+        const bool ok = (int64_t)row < n_rows;
+        const double dv = row_dist64<TC>(corpus + (size_t)(ok ? row : 0u) * d_pad, d, nps, qh);
+        if (lane == 0) d64[(size_t)p * cap + i] = ok ? dv : __builtin_inf();
+        nk += (ok && dv <= r) ? 1u : 0u;
+    }
+    if (lane == 0) kept[p] = nk;
+}
+
 }  // namespace
 }  // namespace lmi
+
+extern "C" int lmi_range_rescore_f64(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq,
+                                     int32_t R, const double* radius64, int32_t pair_cap, const uint64_t* cand,
+                                     const uint32_t* count, double* d64, uint32_t* kept, void* stream) {
+    using namespace lmi;
+    LMI_CHECK_ARG(idx != nullptr, "lmi_range_rescore_f64: null index");
+    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
+                  "lmi_range_rescore_f64: the split mode (corpus32 / corpus64) takes no range search");
+    LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32, "lmi_range_rescore_f64: bad corpus dtype");
+    LMI_CHECK_ARG(idx->d >= 1 && idx->d <= 256 * kMaxPieces && idx->d_pad >= idx->d,
+                  "lmi_range_rescore_f64: d=%d outside [1, %d]", idx->d, 256 * kMaxPieces);
+    LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "lmi_range_rescore_f64: bad nq/R");
+    LMI_CHECK_ARG(pair_cap >= 1, "lmi_range_rescore_f64: pair_cap=%d < 1", pair_cap);
+    LMI_CHECK_ARG(ldq >= idx->d, "lmi_range_rescore_f64: ldq < d");
+    if (nq == 0) return LMI_OK;
+    LMI_CHECK_ARG(q && radius64 && cand && count && d64 && kept, "lmi_range_rescore_f64: null pointer");
+    LMI_CHECK_ARG(idx->n_rows == 0 || idx->corpus, "lmi_range_rescore_f64: null corpus");
+    const int64_t P = (int64_t)nq * R;
+    const dim3 grid((unsigned)((P + kRefT / 64 - 1) / (kRefT / 64)));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (idx->dtype == LMI_F16)
+        hipLaunchKernelGGL(range_rescore_kernel<_Float16>, grid, dim3(kRefT), 0, s,
+                           reinterpret_cast<const _Float16*>(idx->corpus), idx->d, idx->d_pad, idx->n_rows, q, ldq, P,
+                           R, radius64, cand, count, pair_cap, d64, kept);
+    else
+        hipLaunchKernelGGL(range_rescore_kernel<float>, grid, dim3(kRefT), 0, s,
+                           reinterpret_cast<const float*>(idx->corpus), idx->d, idx->d_pad, idx->n_rows, q, ldq, P, R,
+                           radius64, cand, count, pair_cap, d64, kept);
+    LMI_LAUNCH_CHECK("range_rescore_kernel");
+    return LMI_OK;
+}
 
 // ---------------------------------------------------------------------------
 // The split mode (ABI 9, idx->corpus32): a float32 corpus that is not

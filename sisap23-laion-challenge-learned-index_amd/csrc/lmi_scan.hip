@@ -1178,8 +1178,14 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         return LMI_E_WORKSPACE;
     }
     const bool ring = w.family != ScanKernel::General, v3 = w.family == ScanKernel::Ring8;
-    const ScanLaunch launch = pick_launch(w, c);
-    if (!launch.ring && !launch.general) {
+    // (the range search's collect form runs the general family's plan; its
+    // kernel is launch_range_scan, lmi_range.hip)
+    if (c.range != nullptr && (ring || c.wide != nullptr || lo_g != nullptr || out_bound != nullptr)) {
+        set_error("the range scan takes the general kernel's plan alone");
+        return LMI_E_UNSUPPORTED;
+    }
+    const ScanLaunch launch = c.range ? ScanLaunch{nullptr, nullptr} : pick_launch(w, c);
+    if (!c.range && !launch.ring && !launch.general) {
         set_error("no scan kernel takes this call's wide mode, lower bounds or band lists with %d-entry lists", w.kl);
         return LMI_E_UNSUPPORTED;
     }
@@ -1217,6 +1223,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         ++fills.n;
     };
     if (band) add(out_bound, 0x7f800000u, R);
+    if (c.range) add(c.range->ccount, 0u, R);
     if (idx->n_rows > 0) {
         add(ws + w.pair_bucket, 0xffffffffu, R);
         if (seed) add(ws + w.pair_pos, 0xffffffffu, R);
@@ -1394,6 +1401,9 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
             const ScanGrid grid(join_n);
             LMI_TRY(launch.ring(b, s));
         }
+    } else if (c.range && do_scan) {
+        const RangeArgs ra{a, c.range->bound, c.range->cand, c.range->ccount, c.range->cap};
+        LMI_TRY(launch_range_scan(ra, w.f16math, idx->dtype == LMI_F16, s));
     } else if (!ring && do_scan) {
         LMI_TRY(launch.general(a, idx->d_pad, s));
     }

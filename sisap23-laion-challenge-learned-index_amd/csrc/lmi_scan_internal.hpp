@@ -3,7 +3,8 @@
 // its one host entry, bucket_topk_impl; lmi_scan_wide.hip: k > 16;
 // lmi_scan_split.hip: the split mode's driver; lmi_scan_v12.hip: the round-1
 // and round-2 scan kernels, kept as fallbacks for shapes scan v3 does not take
-// and as A/B baselines) and with lmi_refine.hip, their one outside caller.
+// and as A/B baselines; lmi_range.hip: K11 range search, the general kernel's
+// collect form and its driver) and with lmi_refine.hip, their one outside caller.
 // Not an ABI.
 #pragma once
 #include "lmi_common.hpp"
@@ -291,6 +292,26 @@ struct WideScan {
     const int32_t* app_row;
     int32_t app_k;
 };
+// The general kernel's collect form (K11 range search, lmi_range.hip): every
+// row of a pair with d <= bound[q] (and (tag & want) == want when tagged) goes
+// to cand[pair id * cap + i] as make_key(d, row), i from ccount[pair id], which
+// counts every hit (slots past cap are counted, not stored).  No lists, no merge.
+struct RangeScan {
+    const float* bound;  // [nq] one bound per query (-inf: nothing)
+    uint64_t* cand;      // [nq*R][cap]
+    uint32_t* ccount;    // [nq*R], zeroed by the call's prep
+    int32_t cap;
+};
+struct RangeArgs {
+    ScanArgs s;
+    const float* bound;
+    uint64_t* cand;
+    uint32_t* ccount;
+    int32_t cap;
+};
+// range_scan_kernel for fp16 math / an fp16 or fp32 corpus / tags (a.s.tags)
+int launch_range_scan(const RangeArgs& a, bool f16math, bool corpus_f16, hipStream_t s);
+
 // One call of K2 up to the merged per-pair lists (bucket_topk_impl, lmi_scan.hip):
 // lmi_bucket_topk's arguments, a third output (out_row: the shard-local row of
 // every entry, -1 = empty; nullable), and the options below.
@@ -333,6 +354,9 @@ struct ScanCall {
     // (both or neither); only rows with (tag & want) == want are listed
     const uint32_t* tags = nullptr;
     const uint32_t* want = nullptr;
+    // K11 range search: the general kernel's collect form in place of the list
+    // scan (a plan of the general family, phases plan + scan, no prefill)
+    const RangeScan* range = nullptr;
 };
 int bucket_topk_impl(const ScanCall& c);
 

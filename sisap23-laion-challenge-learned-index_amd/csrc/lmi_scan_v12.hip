@@ -93,6 +93,12 @@ __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint6
                                    (unsigned long long)L[KL - 1]);
 }
 
+// Kept in lock-step: a copy of this kernel's query staging and MFMA loop lives in
+// range_scan_kernel (lmi_range.hip), the collect form the range search runs,
+// and of tile_epilogue's distance expression in its epilogue.  The range
+// search promises the distance bits of these lists (test_gpu_range.py's
+// bitwise round trip checks it), so a change to the staging, the MFMA order
+// or the fmaf here is made there too, in the same commit.
 template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
 __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
     using Cfg = ScanCfg<KL, F16MATH>;

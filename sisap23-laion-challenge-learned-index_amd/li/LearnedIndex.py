@@ -320,6 +320,30 @@ class LearnedIndex(Logger):
                                                 stop_mass=stop_mass, min_probes=min_buckets,
                                                 timings=timings, want=want)
 
+    def range_search(self, data_navigation, queries_navigation, data_search, queries_search,
+                     pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None):
+        """Every object within `radius` (a number or one value per query;
+        inclusive) of each query among its `n_buckets` probed buckets (an
+        addition; the reference has top-k search only) -> (lims int64
+        [nq + 1], dists float64 [total], anns uint32 [total]): query i owns
+        entries lims[i]:lims[i + 1], ordered by (distance, id position).  The
+        distances run in the arithmetic of `search` (dist_dtype: float64 unless
+        data and queries are both float32).  `stop_mass`, `min_buckets`,
+        `want`: as in search (want: an int or one word per query).
+        Searcher.range_search has the details and the refusals."""
+        from .index import check_stop
+        check_stop(stop_mass, min_buckets)
+        assert self.model is not None, 'Model is not trained, call `build` first.'
+        if _AUTO_ATTACH and self._trusted is None:
+            self.attach(data_navigation, data_search, pred_categories)
+        self._set_category(data_navigation, pred_categories)
+        index = self._device_index(data_navigation, data_search, pred_categories)
+        q_nav = data_X_to_torch(queries_navigation).to(index.device)
+        return self._get_searcher(index).range_search(
+            q_nav, _upload_queries(queries_search, index.device), n_buckets, radius,
+            dist=dist_dtype(data_search, queries_search), stop_mass=stop_mass, min_probes=min_buckets,
+            want=want)
+
     def mean_probes(self, data_navigation, queries_navigation, data_search, pred_categories,
                     n_buckets, stop_mass, min_buckets=1):
         """Mean number of buckets `search(..., stop_mass, min_buckets)` probes

@@ -78,6 +78,10 @@ EXPORTS = (
     "lmi_bucket_topk",
     "lmi_scan_tagged_workspace_bytes",
     "lmi_bucket_topk_tagged",
+    "lmi_range_workspace_bytes",
+    "lmi_bucket_range",
+    "lmi_range_rescore_f64",
+    "lmi_range_pack",
     "lmi_merge_topk",
     "lmi_scan_f64_workspace_bytes",
     "lmi_bucket_topk_f64",
@@ -200,6 +204,13 @@ _SIGNATURES = {
     "lmi_scan_tagged_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_tagged": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32,
                                          _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_range_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32, _I32]),
+    "lmi_bucket_range": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32,
+                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_range_rescore_f64": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P,
+                                        _P, _P]),
+    "lmi_range_pack": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 _P]),
     "lmi_merge_topk": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "lmi_scan_f64_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_f64": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,

@@ -1597,6 +1597,121 @@ def _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phas
     return out_d, out_pos, status
 
 
+def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
+    """What a range search refuses about the index, as a ValueError before
+    anything is launched or allocated: the split mode (storage "f32x"), float64
+    rows (corpus64), a sub-cluster layout, a stripe of a sharded index, and in
+    float64 a width the float64 search does not take, and in either
+    arithmetic a width whose query tile the collect scan cannot stage
+    (lmi_range_workspace_bytes answers 0: d_pad > 1248)."""
+    if index.storage == "f32x":
+        raise ValueError("range search is not offered on storage 'f32x' (the split mode)")
+    if index.corpus64 is not None:
+        raise ValueError("range search is not offered on an index that keeps float64 rows (corpus64)")
+    if index.chunk_centroid is not None:
+        raise ValueError("range search is not offered on a sub-cluster layout")
+    if index.world > 1:
+        raise ValueError("range search is not offered on a stripe of a sharded index (world > 1)")
+    if dist == "f64" and index.d > 1024:
+        raise ValueError(f"range search in float64 takes d <= 1024, not {index.d}")
+    # either arithmetic the storage can run in (a stale fp16 check falls back to fp32 math)
+    lib = _lib.load()
+    for qmode in ((_lib.LMI_Q_F16, _lib.LMI_Q_F32) if index.storage == "f16" else (_lib.LMI_Q_F32,)):
+        if lib.lmi_range_workspace_bytes(C.byref(index.desc), 1, 1, qmode, 0, 1) == 0:
+            raise ValueError(f"range search takes no d_pad = {index.d_pad}: the collect scan's query tile "
+                             "exceeds the LDS of a workgroup (d_pad <= 1248)")
+
+
+def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, radius, *,
+                 qmode: Optional[int] = None, pair_cap: int = 256, want=None, stream=None, ws=None,
+                 f64: bool = False):
+    """K11's collect scan on one shard (lmi_bucket_range): per (query, probe)
+    pair every row of the probed bucket with d <= radius[q], d the float32
+    distance of the top-k lists of the same kernel family (inclusive).  Returns
+    (count int32 [nq, R], cand int64 [nq, R, pair_cap], status int32 tensor) on
+    the device: count is exact whatever pair_cap; cand holds the first
+    min(count, pair_cap) hits to arrive, unsorted, as the bits of
+    (distance ordinal << 32 | shard-local row).  `radius`: a number or float32
+    values [nq] (the scan's bound as it stands).  `want` (a tagged index; a
+    device int32 [nq] tensor of want words, see want_words): only rows with
+    (tag & want) == want.  `f64`: scan with the float64 mode's descriptor
+    (desc_for(k, f64=True): low-norm rows with their true norm).  A bucket that
+    a query's classes row names twice is collected twice.  `ws` as bucket_topk."""
+    lib = _lib.load()
+    check_range_index(index)
+    if not 1 <= int(pair_cap) <= 1 << 24:
+        raise ValueError("pair_cap must lie in [1, 2^24]")
+    if want is not None and index.tags is None:
+        raise ValueError("want: this index is untagged (build it with `tags`)")
+    q = _rows_f32(q, index.device)
+    classes = _as_torch(classes, index.device, torch.int32)
+    nq, R = classes.shape
+    if q.shape[0] != nq or q.shape[1] != index.d:
+        raise ValueError("query shape does not match the index")
+    if want is not None and not (isinstance(want, torch.Tensor) and want.dtype == torch.int32
+                                 and want.shape == (nq,) and want.device == q.device and want.is_contiguous()):
+        raise ValueError("want must be a device int32 tensor [nq] (want_words)")
+    if isinstance(radius, torch.Tensor):
+        bound = radius.to(device=index.device, dtype=torch.float32).contiguous()
+    else:
+        bound = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(
+            np.asarray(radius, dtype=np.float32), (nq,)))).to(index.device)
+    if bound.shape != (nq,) or bool(torch.isnan(bound).any()):
+        raise ValueError(f"radius must be a number or [{nq}] values, none NaN")
+    if qmode is None:
+        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    desc = index.desc_for(1, f64=f64)
+    need = lib.lmi_range_workspace_bytes(C.byref(desc), nq, R, qmode, int(want is not None), int(pair_cap))
+    if need == 0:
+        raise ValueError("range search: this index or call takes no range scan")
+    if ws is None:
+        ws = index._ws.get("range")
+        if ws is None or ws.numel() < need:
+            ws = index._ws["range"] = torch.empty(max(need, 256), dtype=torch.uint8, device=index.device)
+    else:
+        _workspace(ws, need, "range scan")
+    count = torch.empty((nq, R), dtype=torch.int32, device=index.device)
+    cand = torch.empty((nq, R, int(pair_cap)), dtype=torch.int64, device=index.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=index.device)
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_bucket_range", lib.lmi_bucket_range(
+        C.byref(desc), ptr(index.tags) if want is not None else None, ptr(want), ptr(q), nq, q.stride(0),
+        ptr(classes), R, qmode, ptr(bound), int(pair_cap), ptr(cand), ptr(count), ptr(status), ptr(ws),
+        ws.numel(), s))
+    return count, cand, status
+
+
+def range_rescore_f64(index: DeviceIndex, q: torch.Tensor, radius64: torch.Tensor, count: torch.Tensor,
+                      cand: torch.Tensor, stream=None):
+    """Float64 distances of bucket_range's stored candidates
+    (lmi_range_rescore_f64: the bits lmi_bucket_topk_f64 gives each (query,
+    row)).  Returns (d64 float64 [nq, R, pair_cap], kept int32 [nq, R]), kept =
+    the candidates with d64 <= radius64[q]; pairs with count > pair_cap are left
+    out (kept 0).  q: the float32 queries; radius64: device float64 [nq]."""
+    lib = _lib.load()
+    nq, R, cap = cand.shape
+    d64 = torch.empty((nq, R, cap), dtype=torch.float64, device=index.device)
+    kept = torch.empty((nq, R), dtype=torch.int32, device=index.device)
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_range_rescore_f64", lib.lmi_range_rescore_f64(
+        C.byref(index.desc_for(1, f64=True)), ptr(q), nq, q.stride(0), R, ptr(radius64), cap, ptr(cand),
+        ptr(count), ptr(d64), ptr(kept), s))
+    return d64, kept
+
+
+def range_pack(index: DeviceIndex, count: torch.Tensor, cand: torch.Tensor, off: torch.Tensor, out,
+               d64=None, radius64=None, stream=None) -> None:
+    """lmi_range_pack: every pair with count <= pair_cap writes its candidates
+    (with d64 / radius64: those with d64 <= radius64[q]) to entries off[pair] ..
+    of out = (d float64, pos int32, query int32), unsorted."""
+    lib = _lib.load()
+    nq, R, cap = cand.shape
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_range_pack", lib.lmi_range_pack(
+        C.byref(index.desc), nq, R, cap, ptr(cand), ptr(count), ptr(off), ptr(d64), ptr(radius64),
+        ptr(out[0]), ptr(out[1]), ptr(out[2]), s))
+
+
 def bucket_topk_f64(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                     qmode: Optional[int] = None, eps: Optional[float] = None, stream=None,
                     fallback_count: bool = False, out=None, ws=None, seed_round0: bool = False,
@@ -1992,6 +2107,191 @@ class Searcher:
                  torch.from_numpy(np.ascontiguousarray(self.index.pos_to_id, dtype=np.int64)).to(dev))
             self._dev_tables = t
         return t
+
+    def range_search(self, q_nav, q_search, R: int, radius, *, classes: Optional[torch.Tensor] = None,
+                     dist: str = "f32", stop_mass=None, min_probes: int = 1, want=None,
+                     pair_cap: int = 256, timings: Optional[dict] = None):
+        """Every object of each query's probed buckets within `radius` of it
+        (K11) -> host arrays (lims int64 [nq + 1], dists float64 [total], anns
+        uint32 [total]): query i owns entries lims[i]:lims[i + 1], ordered by
+        (distance, global position); the comparison d <= radius is inclusive.
+
+        `radius`: a number or one value per query.  The probed buckets are the
+        router's top-R, cut short by `stop_mass` / `min_probes` as in search, or
+        the caller's `classes` [nq, R] (-1: no probe).  A classes row that
+        names a bucket twice returns that bucket's objects twice (nothing is
+        de-duplicated).  dist="f32": d is the scan's float32 distance -- the
+        value a top-k list of the same kernel family holds for that (query,
+        object) -- and the radius is rounded once to float32.  dist="f64": d is
+        the float64 distance of search(dist="f64") (lmi_bucket_topk_f64), the
+        radius float64; the scan collects under float32(radius + 2 eps), eps =
+        refine_eps, and the candidates are re-scored in float64.  `want` (a
+        tagged index; an int or one word per query): only objects with
+        (tag & want) == want answer.
+
+        `pair_cap`: candidate slots per (query, probe) of the first scan.  The
+        counts are exact whatever it is; if a pair's count exceeds it, one more
+        scan runs over those pairs alone with the largest count as its cap, so
+        the result does not depend on pair_cap.  Memory: the first scan holds
+        nq * R * pair_cap keys of 8 bytes.  The second scan's buffer is dense
+        too, nq * R * cmax keys with cmax the largest count of any pair
+        (twice that in float64, for the re-scored distances, and once more in
+        the workspace at d = 768), although only the overflowed pairs use it:
+        nothing compacts them, so one large bucket under a wide radius sets the
+        footprint of the whole batch (40 000 pairs with cmax = 80 000: 25.6 GB
+        of keys).  Split such a batch, or the radius, on the caller's side.
+        `timings` (measurement only;
+        the stages are then separated by stream synchronisations) receives
+        per-stage times in ms, `scans` (1 or 2), `results`, and `fp32_redo`
+        = 1 when the scan found the cached fp16 check stale and the call was
+        redone with exact fp32 MFMA.
+
+        ValueError before anything is launched on: a radius that is NaN or
+        not [nq]; storage "f32x"; an index with float64 rows; float64 queries
+        that float32 rounding changes; a sub-cluster layout; a striped index
+        or a Searcher with an exchange group; `want` on an untagged index; in
+        float64 d > 1024; in either arithmetic d_pad > 1248 (the collect
+        scan's query tile would not fit a workgroup's LDS)."""
+        import time
+        check_stop(stop_mass, min_probes)
+        ix = self.index
+        ix._check_live()
+        if dist not in ("f32", "f64"):
+            raise ValueError("dist must be 'f32' or 'f64'")
+        f64 = dist == "f64"
+        check_range_index(ix, dist)
+        if self.exchange:
+            raise ValueError("range search is not offered on a Searcher with an exchange group")
+        if not 1 <= int(pair_cap) <= 1 << 24:
+            raise ValueError("pair_cap must lie in [1, 2^24]")
+        nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
+        r64 = np.asarray(radius.cpu() if isinstance(radius, torch.Tensor) else radius, dtype=np.float64)
+        if r64.ndim == 0:
+            r64 = np.full(nq, float(r64))
+        if r64.shape != (nq,) or np.isnan(r64).any():
+            raise ValueError(f"radius must be a number or [{nq}] values, none NaN")
+        want_w = None
+        if want is not None:
+            want_w = want_words(ix, want, nq, 1, "f32")
+        dev = ix.device
+        q64 = (isinstance(q_search, torch.Tensor) and q_search.dtype == torch.float64) or \
+            (isinstance(q_search, np.ndarray) and q_search.dtype == np.float64)
+        q_search = _rows_q(q_search, dev)
+        if q64:
+            if not torch.equal(q_search.float().double(), q_search):
+                raise ValueError("range search takes float64 queries only where float32 holds their values")
+            q_search = q_search.float()
+        sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
+        tl = [time.perf_counter()]
+
+        def lap(name):
+            if sync:
+                sync()
+                t1 = time.perf_counter()
+                timings[name] = timings.get(name, 0.0) + (t1 - tl[0]) * 1e3
+                tl[0] = t1
+
+        if nq == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.float64), np.zeros(0, np.uint32)
+        qmode = self.qmode(q_search)
+        if classes is None:
+            classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
+        classes = _as_torch(classes, dev, torch.int32)
+        lap("router")
+        r_dev = torch.from_numpy(r64).to(dev) if f64 else None
+
+        def scan_bound(mode):
+            """The scan's float32 bound under `mode`'s arithmetic: the radius
+            rounded once, in float64 float32(r + 2 eps) rounded up."""
+            if not f64:
+                b32 = r64.astype(np.float32)
+            else:
+                eps = refine_eps(ix.d_pad, ix.storage == "f16" and mode == _lib.LMI_Q_F16)
+                wide = r64 + 2.0 * eps
+                b32 = wide.astype(np.float32)
+                b32 = np.where(b32.astype(np.float64) < wide, np.nextafter(b32, np.float32(np.inf)), b32)
+            return torch.from_numpy(np.ascontiguousarray(b32, dtype=np.float32)).to(dev)
+
+        def first_scan(mode):
+            bound = scan_bound(mode)
+            count, cand, status = bucket_range(ix, q_search, classes, bound, qmode=mode, pair_cap=pair_cap,
+                                               want=want_w, f64=f64)
+            # the one host read of the scan: the largest count, the total, the status
+            head = torch.stack([count.max().long(), count.sum(), status[0].long()]).cpu()
+            return bound, count, cand, int(head[0]), int(head[1]), int(head[2])
+
+        bound, count, cand, cmax, total, st = first_scan(qmode)
+        if st & _lib.LMI_STATUS_QUERY_NOT_F16:
+            # the cached fp16 check was stale: redo with exact fp32 MFMA, under
+            # the bound of that arithmetic (its eps is the wider one)
+            qmode = _lib.LMI_Q_F32
+            bound, count, cand, cmax, total, st = first_scan(qmode)
+            if timings is not None:
+                timings["fp32_redo"] = 1
+        if st:
+            raise RuntimeError(f"range_search: scan status {st}")
+        scans = [(count, cand)]
+        status2 = None
+        if cmax > pair_cap:
+            # the overflowed pairs alone, with room for the largest of them
+            over = count > pair_cap
+            classes2 = torch.where(over, classes, torch.full_like(classes, -1))
+            count2, cand2, status2 = bucket_range(ix, q_search, classes2, bound, qmode=qmode, pair_cap=cmax,
+                                                  want=want_w, f64=f64)
+            scans.append((count2, cand2))
+        lap("scan")
+
+        def second_read(kept):
+            """The second scan's host read: the total again and that scan's status."""
+            head = torch.stack([kept.sum(), status2[0].long()]).cpu()
+            if int(head[1]):
+                raise RuntimeError(f"range_search: second scan status {int(head[1])}")
+            return int(head[0])
+
+        if f64:
+            scored = [range_rescore_f64(ix, q_search, r_dev, c, x) for c, x in scans]
+            kept = scored[0][1] if len(scored) == 1 else scored[0][1] + scored[1][1]
+            total = int(kept.sum().item()) if len(scans) == 1 else second_read(kept)
+            lap("rescore")
+        else:
+            scored = [(None, None)] * len(scans)
+            # (the counts are exact whatever the cap; the entries a pack writes are
+            # its own scan's)
+            kept = count if len(scans) == 1 else torch.where(count > pair_cap, scans[1][0], count)
+            if len(scans) == 2:
+                total = second_read(kept)
+        per_q = kept.sum(dim=1, dtype=torch.int64)
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(per_q, 0, out=lims[1:])
+        flat = kept.reshape(-1).long()
+        off = (torch.cumsum(flat, 0) - flat).contiguous()
+        out = (torch.empty(total, dtype=torch.float64, device=dev),
+               torch.empty(total, dtype=torch.int32, device=dev),
+               torch.empty(total, dtype=torch.int32, device=dev))
+        if total:
+            for (c, x), (d64, _) in zip(scans, scored):
+                range_pack(ix, c, x, off, out, d64=d64, radius64=r_dev if f64 else None)
+        lap("pack")
+        # (query, distance, global position): three stable sorts, last key first
+        d, pos, qi = out
+        if total:
+            pos, o = torch.sort(pos, stable=True)
+            d, qi = d[o], qi[o]
+            d, o = torch.sort(d, stable=True)
+            pos, qi = pos[o], qi[o]
+            qi, o = torch.sort(qi, stable=True)
+            d, pos = d[o], pos[o]
+        _, p2id = self._device_tables()
+        ids = p2id[pos.long()].to(torch.int32)
+        lap("sort")
+        h_lims, h_d, h_a = lims.cpu(), d.cpu(), ids.cpu()
+        lap("d2h")
+        if timings is not None:
+            timings["scans"] = len(scans)
+            timings["results"] = total
+            if stop_mass is not None:
+                timings["mean_probes"] = float((classes >= 0).sum().item()) / max(1, nq)
+        return h_lims.numpy(), h_d.numpy(), h_a.numpy().view(np.uint32)
 
     def streamed(self, q_nav, q_search, R: int, k: int = 10, **kw) -> "StreamedSearch":
         """The step as a four-stage pipeline of captured graphs over a stream
