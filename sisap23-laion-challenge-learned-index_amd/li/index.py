@@ -21,9 +21,7 @@ every probed bucket whatever the bucket popularity.
 """
 from __future__ import annotations
 
-import bisect
 import ctypes as C
-import dataclasses
 import os
 import time
 from typing import Optional, Sequence
@@ -31,33 +29,12 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, index_update
 from ._lib import check, ptr
+from .index_update import DEFAULT_DIRECT_ROWS, DEFAULT_SLAB_ROWS, STAGING_MAX_BYTES  # noqa: F401
+from .layout import DEFAULT_CHUNK_ROWS, BucketLayout, check_tags, default_chunk_rows, eligible_counts  # noqa: F401
 
-DEFAULT_CHUNK_ROWS = 8192
-# In-place updates (K9): rows of a staged slab, the least rows of
-# a direct slab, and the cap on the staging buffer (the Infinity Cache's size)
-DEFAULT_SLAB_ROWS = 64 << 10
-DEFAULT_DIRECT_ROWS = 16 << 10
-STAGING_MAX_BYTES = 256 << 20
 SPLIT_D_PAD = 768  # the split mode's (storage "f32x") row width: the fp16 scan's
-
-
-def default_chunk_rows(world: int, n_rows: Optional[int] = None) -> int:
-    """The scan's chunk (rows) for a shard of a `world`-rank index: 8192 on one
-    GPU, 4096 on 2-4, 2048 on more, so a 1/world stripe still cuts into enough
-    tiles to fill 256 CUs (DESIGN.md §5 "Chunk size"; tools/gpu_shards.sh);
-    given the index's rows, halved (down to 1024) while a rank's shard would
-    hold fewer than 64 chunks (configs[1], 300K rows: 4096 -- the scan 0.63
-    instead of 0.75 ms, the float64 line +8%, the stream as fast; smaller
-    chunks speed the scan further but add plan and merge work to a launch
-    the host already bounds, profiles/r05aa_300K_chunk_rows.txt)."""
-    c = DEFAULT_CHUNK_ROWS if world <= 1 else 4096 if world <= 4 else 2048
-    if n_rows is not None:
-        per = n_rows / max(int(world), 1)
-        while c > 1024 and per / c < 64:
-            c //= 2
-    return c
 # LMI_Q_SEED_ROUND0 in the thresholded reference replay (LMI_NO_SEED=1: off,
 # for A/B measurements; results are the same either way)
 _SEED_ROUND0 = os.environ.get("LMI_NO_SEED") != "1"
@@ -164,257 +141,6 @@ def fp16_exact(x: torch.Tensor) -> bool:
     return bool(torch.equal(x.half().float(), x))
 
 
-# ---------------------------------------------------------------------------
-# bucket layout (host arithmetic, shared by every rank)
-# ---------------------------------------------------------------------------
-@dataclasses.dataclass
-class BucketLayout:
-    """Bucket-sorted order of the corpus.  Global position p holds row order[p]."""
-
-    n_buckets: int
-    order: np.ndarray        # int64 [n]: row index of each global position
-    bucket_off: np.ndarray   # int64 [C+1] global offsets
-
-    @classmethod
-    def from_labels(cls, labels, n_buckets: int) -> "BucketLayout":
-        lab = np.asarray(labels).astype(np.int64, copy=False).ravel()
-        if lab.size and (lab.min() < 0 or lab.max() >= n_buckets):
-            raise ValueError(f"labels must lie in [0, {n_buckets})")
-        order = np.argsort(lab, kind="stable").astype(np.int64)
-        size = np.bincount(lab, minlength=n_buckets).astype(np.int64)
-        off = np.zeros(n_buckets + 1, np.int64)
-        np.cumsum(size, out=off[1:])
-        return cls(n_buckets, order, off)
-
-    @property
-    def bucket_size(self) -> np.ndarray:
-        return np.diff(self.bucket_off)
-
-    def updated(self, drop_positions, new_labels):
-        """The layout after an update of the row sequence: the rows at the
-        global positions `drop_positions` are deleted from it and one row per
-        entry of `new_labels` is appended, in that order.  Returns
-
-            (layout, new_dst, surv_off, drop_before)
-
-        layout      equals from_labels over the updated label sequence (row
-                    indices renumbered: survivors keep their relative order,
-                    the new rows follow)
-        new_dst     int64 [m]: the global position of every new row -- behind
-                    its bucket's survivors, stable in batch order
-        surv_off    int64 [C+1]: prefix sums of the survivors per bucket; with
-                    the new offsets it places any per-position table of
-                    the survivors (place_survivors)
-        drop_before int64 [C+1]: how many dropped positions lie before each
-                    old bucket offset (lmi_index_move_rows' table)
-
-        Pure numpy, O(n + m) index arithmetic (slice copies per bucket) and
-        one stable sort of the m new labels; no sort over n."""
-        C_, off = self.n_buckets, self.bucket_off
-        n = int(off[-1])
-        drop = np.unique(np.asarray(drop_positions, dtype=np.int64).ravel())
-        if drop.size != np.asarray(drop_positions).size:
-            raise ValueError("drop_positions must be distinct")
-        if drop.size and (drop[0] < 0 or drop[-1] >= n):
-            raise ValueError(f"drop_positions must lie in [0, {n})")
-        lab = np.asarray(new_labels).astype(np.int64, copy=False).ravel()
-        if lab.size and (lab.min() < 0 or lab.max() >= C_):
-            raise ValueError(f"labels must lie in [0, {C_})")
-        m = int(lab.size)
-        drop_before = np.searchsorted(drop, off, side="left").astype(np.int64)
-        surv = np.diff(off) - np.diff(drop_before)
-        added = np.bincount(lab, minlength=C_).astype(np.int64)
-        new_off = np.zeros(C_ + 1, np.int64)
-        np.cumsum(surv + added, out=new_off[1:])
-        # survivors, in ascending old position (bucket by bucket): bucket c's
-        # start at new_off[c]
-        n_surv = n - int(drop.size)
-        surv_off = np.zeros(C_ + 1, np.int64)
-        np.cumsum(surv, out=surv_off[1:])
-        # new rows: stable rank inside the bucket, after its survivors
-        by_label = np.argsort(lab, kind="stable")
-        add_off = np.zeros(C_ + 1, np.int64)
-        np.cumsum(added, out=add_off[1:])
-        new_dst = np.empty(m, np.int64)
-        new_dst[by_label] = np.arange(m, dtype=np.int64) + np.repeat(
-            new_off[:-1] + surv - add_off[:-1], added)
-        # row indices of the updated sequence: the kept rows renumbered in
-        # their order, then the batch
-        kept = self.order
-        if drop.size:
-            keep_row = np.ones(n, bool)
-            keep_row[self.order[drop]] = False
-            renum = np.cumsum(keep_row) - 1
-            kept = renum[np.delete(self.order, drop)]
-        order = np.empty(n_surv + m, np.int64)
-        self.place_survivors(kept, surv_off, new_off, order)
-        order[new_dst] = n_surv + np.arange(m, dtype=np.int64)
-        return BucketLayout(C_, order, new_off), new_dst, surv_off, drop_before
-
-    def inplace_slabs(self, new_off, drop, slab_rows: int, direct_rows: int) -> np.ndarray:
-        """The plan of an update inside one buffer (lmi_index_move_rows_inplace):
-        int64 [k, 3] rows (a, b, staged) -- slabs [a, b) of this layout's
-        positions, in processing order.  `new_off`: the bucket offsets after
-        the update (updated()'s layout.bucket_off); `drop`: the ascending
-        dropped positions.  No drops: an add, every row moves right by its
-        bucket's new_off - bucket_off, which does not decrease along the
-        corpus; drops: a remove (no new rows), every survivor moves left by the
-        number of drops before it.
-
-        Rows that do not move are in no slab: an add's prefix up to and
-        including the first bucket that receives a row, a remove's prefix
-        before the first drop.  An add is cut from the end backwards, a remove
-        from the front forwards.  At the cursor the longest DIRECT slab is
-        taken -- its destinations lie outside [a, b): a + shift(a) >= b for an
-        add, dest(b - 1) < a for a remove -- when it has at least
-        `direct_rows` rows; otherwise a STAGED slab of at most `slab_rows`
-        rows.  Destinations of a slab then lie in its own range or in rows
-        earlier slabs have vacated, never in rows a later slab reads.
-        O(slabs * log) host arithmetic, no array over n."""
-        slab_rows, direct_rows = int(slab_rows), int(direct_rows)
-        if slab_rows < 1 or direct_rows < 1:
-            raise ValueError("slab_rows and direct_rows must be positive")
-        off = self.bucket_off
-        n = int(off[-1])
-        new_off = np.asarray(new_off, dtype=np.int64)
-        drop = np.asarray(drop, dtype=np.int64).ravel()
-        if new_off.shape != off.shape:
-            raise ValueError("new_off must have one entry per bucket offset")
-        out = []
-        if drop.size == 0:
-            shift = new_off[:-1] - off[:-1]
-            if (shift < 0).any() or (np.diff(shift) < 0).any():
-                raise ValueError("inplace_slabs: new_off is not this layout plus added rows")
-            moved = np.flatnonzero(shift > 0)
-            if n == 0 or moved.size == 0:
-                return np.zeros((0, 3), np.int64)
-            first = int(off[moved[0]])           # rows before it keep their place
-            # hi[c]: where the last row of bucket c lands (non-decreasing in c)
-            hi, lo, sh = (off[1:] - 1 + shift).tolist(), off[:-1].tolist(), shift.tolist()
-            e = n
-            while e > first:
-                c = bisect.bisect_left(hi, e)    # the first bucket with a row landing at or past e
-                a = max(lo[c], e - sh[c], first)
-                staged = e - a < direct_rows
-                if staged:
-                    a = max(first, e - slab_rows)
-                out.append((a, e, int(staged)))
-                e = a
-            return np.array(out, np.int64).reshape(-1, 3)
-        r = int(drop.size)
-        if (np.diff(drop) <= 0).any() or drop[0] < 0 or drop[-1] >= n:
-            raise ValueError(f"inplace_slabs: drop must be ascending, distinct and inside [0, {n})")
-        if int(new_off[-1]) != n - r:
-            raise ValueError("inplace_slabs: a remove in place takes no new rows")
-        n_surv = n - r
-        d = drop.tolist()
-        key = (drop - np.arange(r, dtype=np.int64)).tolist()   # survivors before each drop
-
-        def survivor(t):                         # position of the survivor of rank t
-            return t + bisect.bisect_right(key, t)
-
-        def next_survivor(s):                    # the first survivor at or after s (n: none)
-            t = s - bisect.bisect_left(d, s)
-            return survivor(t) if t < n_surv else n
-
-        s = next_survivor(d[0])
-        while s < n:
-            # (dest(i) = survivors before i: the last row with dest < s is the
-            # survivor of rank s - 1, at or after s as a drop lies before s)
-            b = survivor(s - 1) + 1 if s - 1 < n_surv else n
-            staged = b - s < direct_rows
-            if staged:
-                b = min(n, s + slab_rows)
-            out.append((s, b, int(staged)))
-            s = next_survivor(b)
-        return np.array(out, np.int64).reshape(-1, 3)
-
-    @staticmethod
-    def place_survivors(kept, surv_off, new_off, out) -> None:
-        """out[new_off[c] + j] = kept[surv_off[c] + j], j < surv_off[c+1] -
-        surv_off[c], for every bucket c: a per-position table of the survivors
-        (`kept`, in ascending old position) laid out at the front of every
-        bucket's new range.  One slice copy per bucket (memcpy speed; an index
-        array over n is several times slower), an index array when there are
-        more buckets than that pays for."""
-        C_ = int(surv_off.size) - 1
-        if C_ <= 1 << 14:
-            for c in range(C_):
-                a, b = int(surv_off[c]), int(surv_off[c + 1])
-                if b > a:
-                    t = int(new_off[c])
-                    out[t:t + (b - a)] = kept[a:b]
-            return
-        shift = np.repeat(new_off[:-1] - surv_off[:-1], np.diff(surv_off))
-        out[np.arange(kept.size, dtype=np.int64) + shift] = kept
-
-    @staticmethod
-    def updated_table(table, drop, surv_off, new_off, new_dst, new_values) -> np.ndarray:
-        """A per-position table (pos_to_id, tags_by_pos) after updated(): the
-        survivors' entries at the front of every bucket's new range, the new
-        rows' `new_values` at `new_dst`.  `drop`: the ascending dropped
-        positions; the other arguments as updated() returns them."""
-        table = np.asarray(table)
-        out = np.empty(int(new_off[-1]), table.dtype)
-        BucketLayout.place_survivors(np.delete(table, drop) if len(drop) else table, surv_off, new_off, out)
-        out[new_dst] = new_values
-        return out
-
-    @staticmethod
-    def relabel_source(old_order, new_order) -> np.ndarray:
-        """src[p]: the position at which a layout of order `old_order` holds
-        the row of position p of a layout of order `new_order` over the same
-        row sequence -- a per-position table moves as table[src]."""
-        inv = np.empty(old_order.size, np.int64)
-        inv[old_order] = np.arange(old_order.size, dtype=np.int64)
-        return inv[new_order]
-
-    def shard(self, rank: int, world: int):
-        """(global positions of the shard's rows, local bucket offsets [C+1])."""
-        if world == 1:
-            return np.arange(self.bucket_off[-1], dtype=np.int64), self.bucket_off.copy()
-        parts, loc = [], np.zeros(self.n_buckets + 1, np.int64)
-        for c in range(self.n_buckets):
-            a, b = self.bucket_off[c], self.bucket_off[c + 1]
-            n = b - a
-            lo = a + (n * rank) // world
-            hi = a + (n * (rank + 1)) // world
-            parts.append(np.arange(lo, hi, dtype=np.int64))
-            loc[c + 1] = loc[c] + (hi - lo)
-        return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), loc
-
-
-# ---------------------------------------------------------------------------
-# tags (filtered search: lmi_bucket_topk_tagged)
-# ---------------------------------------------------------------------------
-def check_tags(tags, n: int) -> np.ndarray:
-    """`tags` (any integer array, one word per row, values in [0, 2^32)) as
-    uint32 [n]; ValueError otherwise."""
-    t = tags.cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)
-    if t.dtype.kind not in "iu":
-        raise ValueError("tags must be integers")
-    t = t.ravel()
-    if t.shape != (n,):
-        raise ValueError(f"tags must have one word per row ({n})")
-    if t.size and (int(t.min()) < 0 or int(t.max()) >= 1 << 32):
-        raise ValueError("tags must lie in [0, 2^32)")
-    return np.ascontiguousarray(t.astype(np.uint32))
-
-
-def eligible_counts(tags_by_pos, bucket_off, want: int) -> np.ndarray:
-    """int64 [C]: the rows of every bucket with (tag & want) == want -- a
-    segmented count over `bucket_off` ([C+1] positions into `tags_by_pos`),
-    done in torch.  The reference replay of a filtered search reads these as
-    its bucket sizes (the < k quirk, the empty-bucket skip)."""
-    w = int(want)
-    t = torch.from_numpy(np.ascontiguousarray(tags_by_pos, dtype=np.uint32).astype(np.int64))
-    ok = (t & w) == w
-    cs = torch.zeros(t.numel() + 1, dtype=torch.int64)
-    torch.cumsum(ok, 0, out=cs[1:])
-    off = torch.from_numpy(np.ascontiguousarray(bucket_off, dtype=np.int64))
-    return (cs[off[1:]] - cs[off[:-1]]).numpy()
-
-
 def _as_i32_bits(a: np.ndarray) -> torch.Tensor:
     """uint32 words as an int32 tensor of the same bits (torch has no uint32 gather)."""
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32))
@@ -456,7 +182,7 @@ class DeviceIndex:
     # inv_norm with the true 1/||y|| of the rows whose norm lies in [10 eps64,
     # 10 eps32), for the float64 calls; None when no stored row does (_low_norm)
     inv_norm64 = None
-    _desc64 = None
+    _desc = _desc32 = _desc64 = None   # built on first use (desc, desc_for), dropped by _adopt_store
     consumed = False   # True once an in-place update has taken this index's store (K9)
     # filtered search: every row's 32-bit tag word -- tags_by_pos host uint32
     # [n_total], parallel to pos_to_id; tags device [n_rows] (the words as
@@ -523,7 +249,6 @@ class DeviceIndex:
         self.chunk_centroid = None
         if subcluster and self.n_chunks > 0:
             self._subcluster_layout(loc_off, cf)
-        self._desc = IndexDescHolder(self)
         self._ws = {}
 
     def _plan_tables(self, loc_off, chunk_rows):
@@ -574,10 +299,18 @@ class DeviceIndex:
         cap = self._capacity if capacity is None else capacity
         cap = max(int(cap), n_rows) if cap is not None else n_rows
         make = torch.zeros if zero else torch.empty
-        self._store = make((cap, self.d_pad), dtype=dtype, device=self.device)
-        self._store_inv = torch.empty((cap,), dtype=torch.float32, device=self.device)
-        self._capacity = cap
-        self.corpus, self.inv_norm = self._store[:n_rows], self._store_inv[:n_rows]
+        self._adopt_store(make((cap, self.d_pad), dtype=dtype, device=self.device),
+                          torch.empty((cap,), dtype=torch.float32, device=self.device), n_rows)
+
+    def _adopt_store(self, store, store_inv, n_rows: int, inv64: bool = False):
+        """Take `store` / `store_inv` (fresh, or a consumed index's): the capacity is its rows, `corpus` /
+        `inv_norm` the leading [n_rows] views, and descriptors over an earlier store are dropped.
+        `inv64`: the rows are in it already and call for an inv_norm64 (_set_inv_norm64)."""
+        self._store, self._store_inv, self._capacity = store, store_inv, int(store.shape[0])
+        self.corpus, self.inv_norm = store[:n_rows], store_inv[:n_rows]
+        self._desc = self._desc32 = self._desc64 = None
+        if inv64:
+            self._set_inv_norm64()
 
     @property
     def capacity(self) -> int:
@@ -610,7 +343,8 @@ class DeviceIndex:
         self._check_updatable()
         if int(rows) < self.n_rows:
             raise ValueError(f"reserve: {int(rows)} rows are below the {self.n_rows} rows of the index")
-        new = self._successor(self.layout, self.pos_to_id, int(rows), self.tags_by_pos)
+        new = self._successor(self.layout, self.pos_to_id, self.tags_by_pos)
+        new._alloc_store(self.n_rows, capacity=int(rows))
         new.corpus.copy_(self.corpus)
         new.inv_norm.copy_(self.inv_norm)
         if self.inv_norm64 is not None:
@@ -618,11 +352,11 @@ class DeviceIndex:
         torch.cuda.current_stream(self.device).synchronize()
         return new
 
-    def _successor(self, layout, pos_to_id, capacity: int, tags_by_pos=None) -> "DeviceIndex":
-        """A one-GPU fp16 index over `layout` / `pos_to_id` with this one's
-        shape and chunk rule: every table, and fresh stores of `capacity`
-        rows (or more, when the layout holds more) whose rows the caller
-        writes."""
+    def _successor(self, layout, pos_to_id, tags_by_pos) -> "DeviceIndex":
+        """A one-GPU fp16 index over `layout` / `pos_to_id` / `tags_by_pos`
+        (None: untagged) with this one's shape and chunk rule: the one place
+        besides __init__ that makes a DeviceIndex.  Every table and scalar is
+        set; the caller gives it a row store (_alloc_store, _adopt_store)."""
         n_new = int(layout.bucket_off[-1])
         new = object.__new__(DeviceIndex)
         new.device, new.layout, new.n_buckets = self.device, layout, layout.n_buckets
@@ -633,19 +367,11 @@ class DeviceIndex:
         new.bucket_size = layout.bucket_size.copy()
         new._plan_tables(layout.bucket_off.copy(), self.chunk_rows if self._chunk_rows_given else None)
         new.gpos = torch.arange(n_new, dtype=torch.int32, device=self.device)
-        new._set_tags(tags_by_pos)
+        new.tags_by_pos = tags_by_pos
+        new.tags = None if tags_by_pos is None else _as_i32_bits(tags_by_pos).to(self.device)
         new.chunk_centroid = None
         new._ws = {}
-        if capacity is not None:
-            new._alloc_store(n_new, capacity=capacity)
-            new._desc = IndexDescHolder(new)
         return new
-
-    def _set_tags(self, tags_by_pos):
-        """The tag tables of a one-GPU index (gpos = every position): the host
-        table and its upload; None: an untagged index."""
-        self.tags_by_pos = tags_by_pos
-        self.tags = None if tags_by_pos is None else _as_i32_bits(tags_by_pos).to(self.device)
 
     def _check_updatable(self):
         """What add / remove support, refused before any device work."""
@@ -714,9 +440,8 @@ class DeviceIndex:
         new_tags = None
         if self.tags_by_pos is not None:
             new_tags = np.zeros(m, np.uint32) if tags is None else check_tags(tags, m)
-        return self._updated(np.zeros(0, np.int64), rows, lab, ids, inplace=inplace,
-                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings,
-                             new_tags=new_tags)
+        return index_update.update(self, np.zeros(0, np.int64), rows, lab, ids, new_tags, inplace=inplace,
+                                   slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
 
     def remove(self, ids, *, inplace: bool = False, slab_rows: Optional[int] = None,
                direct_rows: Optional[int] = None, timings: Optional[dict] = None) -> "DeviceIndex":
@@ -736,39 +461,12 @@ class DeviceIndex:
             missing = np.setdiff1d(uniq, self.pos_to_id[drop])
             raise KeyError(f"ids not in the index: {missing[:8].tolist()}"
                            + (" ..." if missing.size > 8 else ""))
-        return self._updated(drop, None, np.zeros(0, np.int64), np.zeros(0, np.int64), inplace=inplace,
-                             slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
+        none = np.zeros(0, np.int64)
+        return index_update.update(self, drop, None, none, none, none.astype(np.uint32), inplace=inplace,
+                                   slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
 
     # ---- re-bucket (K8: csrc/lmi_rebucket.hip) ------------------
-    @staticmethod
-    def _sorted_by_bucket(lab: torch.Tensor, n_buckets: int):
-        """(order, bucket_off) of the device labels `lab` (int32 / int64), both
-        int64 on the device: BucketLayout.from_labels' tables.  Up to
-        LMI_REBUCKET_MAX_BUCKETS buckets by lmi_bucket_sort_labels; above, by
-        torch.sort(stable=True) on the device."""
-        dev, n = lab.device, int(lab.numel())
-        if n_buckets > _lib.LMI_REBUCKET_MAX_BUCKETS:
-            if n and (int(lab.min()) < 0 or int(lab.max()) >= n_buckets):
-                raise ValueError(f"labels must lie in [0, {n_buckets})")
-            order = torch.sort(lab, stable=True).indices
-            off = torch.zeros(n_buckets + 1, dtype=torch.int64, device=dev)
-            torch.cumsum(torch.bincount(lab, minlength=n_buckets), 0, out=off[1:])
-            return order, off
-        lib = _lib.load()
-        order = torch.empty(n, dtype=torch.int64, device=dev)
-        off = torch.empty(n_buckets + 1, dtype=torch.int64, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        need = lib.lmi_bucket_sort_labels_ws_bytes(n, n_buckets)
-        ws = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
-        check("lmi_bucket_sort_labels", lib.lmi_bucket_sort_labels(
-            ptr(lab), lab.element_size(), n, n_buckets, ptr(off), ptr(order), ptr(status), ptr(ws),
-            ws.numel() * 8, _lib.stream_handle(dev)))
-        st = int(status.item())  # (before `order` indexes anything: a bad label leaves holes in it)
-        if st & _lib.LMI_STATUS_BAD_LABEL:
-            raise ValueError(f"labels must lie in [0, {n_buckets})")
-        if st:
-            raise RuntimeError(f"index relabel: internal status {st}")
-        return order, off
+    _sorted_by_bucket = staticmethod(index_update.sorted_by_bucket)
 
     @torch.no_grad()
     def relabel(self, labels, n_buckets: Optional[int] = None, *, inplace: bool = False,
@@ -814,286 +512,7 @@ class DeviceIndex:
         if lab.dtype not in (torch.int32, torch.int64):
             lab = lab.to(torch.int64)
         lab = lab.reshape(-1).to(dev).contiguous()
-        lib = _lib.load()
-        lap = [time.perf_counter()]
-
-        def mark(name):
-            if timings is not None:
-                torch.cuda.synchronize(dev)
-                lap.append(time.perf_counter())
-                timings[name] = timings.get(name, 0.0) + lap[-1] - lap[-2]
-
-        order, off = self._sorted_by_bucket(lab, C_)
-        mark("sort")
-        # src_pos[p]: where the old index holds the row of new position p (the
-        # inverse of the old order, read at the new one); pos_to_id moves as the rows do
-        old_order = torch.from_numpy(self.layout.order).to(dev)
-        inv = torch.empty(n, dtype=torch.int64, device=dev)
-        inv[old_order] = torch.arange(n, dtype=torch.int64, device=dev)
-        src_pos = inv[order]
-        del inv, old_order
-        p2id = torch.from_numpy(self.pos_to_id).to(dev)[src_pos]
-        old_tags, old_layout_order = self.tags_by_pos, self.layout.order
-        mark("tables")
-        new = object.__new__(DeviceIndex)
-        new.device, new.n_buckets = dev, C_
-        new.n_total = new.n_rows = n
-        new.rank, new.world = 0, 1
-        new.d, new.d_pad, new.storage = self.d, self.d_pad, self.storage
-        chunk_rows = self.chunk_rows if self._chunk_rows_given else None
-        status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        if inplace:
-            self._swap_into(new, src_pos, status, mark, timings)   # (consumes this index)
-        else:
-            new._alloc_store(n, capacity=self.capacity)   # (a reserved index stays reserved)
-            check("lmi_index_gather_rows", lib.lmi_index_gather_rows(
-                ptr(self.corpus), ptr(self.inv_norm), n, self.d_pad, ptr(src_pos), ptr(new.corpus),
-                ptr(new.inv_norm), n, ptr(status), _lib.stream_handle(dev)))
-            st = int(status.item())  # (waits for the kernel: src_pos stays alive until here)
-            if st:
-                raise RuntimeError(f"index relabel: internal status {st}")
-            if self.inv_norm64 is not None:
-                new._set_inv_norm64()
-            mark("gather")
-        new.layout = BucketLayout(C_, order.cpu().numpy(), off.cpu().numpy())
-        new.pos_to_id = p2id.cpu().numpy()
-        new.bucket_size = new.layout.bucket_size.copy()
-        new._plan_tables(new.layout.bucket_off.copy(), chunk_rows)
-        new.gpos = torch.arange(n, dtype=torch.int32, device=dev)
-        # the tags move as pos_to_id does (on the host, then uploaded)
-        new._set_tags(None if old_tags is None else
-                      old_tags[BucketLayout.relabel_source(old_layout_order, new.layout.order)])
-        new.chunk_centroid = None
-        new._desc = IndexDescHolder(new)
-        new._ws = {}
-        mark("host")
-        return new
-
-    def _swap_into(self, new, src_pos, status, mark, timings):
-        """relabel(inplace=True)'s row move (K10): plan the gather by
-        `src_pos` as two involutions, read the plan's status, then swap the
-        rows of this index's own store in two passes and hand the store to
-        `new`.  This index is consumed once the first pass is enqueued."""
-        lib = _lib.load()
-        dev, n = self.device, self.n_rows
-        s = _lib.stream_handle(dev)
-        store, store_inv, cap = self._store, self._store_inv, self.capacity
-        low64 = self.inv_norm64 is not None
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
-        p1 = p2 = None
-        if n:
-            p1 = torch.empty(n, dtype=torch.int64, device=dev)
-            p2 = torch.empty(n, dtype=torch.int64, device=dev)
-            need = lib.lmi_perm_involutions_ws_bytes(n)
-            ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
-            if ev:
-                ev[0].record()
-            check("lmi_perm_involutions", lib.lmi_perm_involutions(
-                ptr(src_pos), n, ptr(p1), ptr(p2), ptr(status), ptr(ws), need, s))
-            if ev:
-                ev[1].record()
-            st = int(status.item())  # (the plan is judged before any row moves)
-            del ws
-            if st & _lib.LMI_STATUS_BAD_PERM:
-                raise RuntimeError("index relabel in place: the row order of the index and the new one "
-                                   "do not give a permutation of its rows (the index is unchanged)")
-            if st:
-                raise RuntimeError(f"index relabel in place: internal status {st} (the index is unchanged)")
-            if ev:
-                at = torch.arange(n, dtype=torch.int64, device=dev)
-                timings["swapped_rows"] = [2 * int((p > at).sum()) for p in (p1, p2)]
-                del at
-        mark("plan")
-        # everything queued on the device (replays on other streams that read
-        # this index) finishes before the first row moves
-        torch.cuda.synchronize(dev)
-        if n:
-            if ev:
-                ev[2].record()
-            rc = lib.lmi_index_swap_rows(ptr(store), ptr(store_inv), n, self.d_pad, ptr(p1), ptr(status), s)
-            if rc == _lib.LMI_E_INVALID:
-                check("lmi_index_swap_rows", rc)  # (refused on the host: nothing was launched)
-        # from here on rows may have moved: this object must not launch again
-        self._consume()
-        if n:
-            check("lmi_index_swap_rows", rc)
-            if ev:
-                ev[3].record()
-            check("lmi_index_swap_rows", lib.lmi_index_swap_rows(
-                ptr(store), ptr(store_inv), n, new.d_pad, ptr(p2), ptr(status), s))
-            if ev:
-                ev[4].record()
-        st = int(status.item())  # (waits for both passes: the partners stay alive until here)
-        torch.cuda.synchronize(dev)
-        if st:
-            raise RuntimeError(f"index relabel in place: internal status {st}; the index is consumed "
-                               "and the content of its store is undefined")
-        new._store, new._store_inv, new._capacity = store, store_inv, cap
-        new.corpus, new.inv_norm = store[:n], store_inv[:n]
-        if low64:
-            new._set_inv_norm64()
-        if ev and n:
-            timings["plan_ms"] = ev[0].elapsed_time(ev[1])
-            timings["plan_rounds"] = 2 * max(0, (n - 1).bit_length())
-            timings["swap_ms"] = [ev[2].elapsed_time(ev[3]), ev[3].elapsed_time(ev[4])]
-        mark("swap")
-
-    def _batch_rows(self, rows) -> torch.Tensor:
-        """The batch on the device as lmi_index_ingest_rows reads it: fp16 or
-        fp32 with contiguous rows (a device tensor of that form as it is)."""
-        if not isinstance(rows, torch.Tensor):
-            a = np.asarray(rows)
-            a = a if a.dtype in (np.float16, np.float32, np.float64) else a.astype(np.float32)
-            rows = torch.from_numpy(np.ascontiguousarray(a))
-        if rows.dtype == torch.float64:
-            f = rows.float()
-            if not torch.equal(f.double(), rows):
-                raise ValueError("index update: float64 rows must be fp16-representable")
-            rows = f
-        elif rows.dtype not in (torch.float16, torch.float32):
-            rows = rows.float()
-        rows = rows.to(self.device)
-        return rows if rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1] else rows.contiguous()
-
-    @torch.no_grad()
-    def _updated(self, drop, rows, lab, ids, *, inplace=False, slab_rows=None, direct_rows=None,
-                 timings=None, new_tags=None) -> "DeviceIndex":
-        """The index after dropping the global positions `drop` (ascending)
-        and appending the batch: host tables by index arithmetic
-        (BucketLayout.updated), rows by the K7 kernels into new stores -- or,
-        `inplace`, by the K9 chain inside this index's own."""
-        lib = _lib.load()
-        m, r = int(lab.size), int(drop.size)
-        n_old, n_new = self.n_rows, self.n_rows - r + m
-        if inplace and n_new > self.capacity:
-            raise ValueError(f"index update in place: {n_new} rows exceed the capacity of "
-                             f"{self.capacity} rows (build the index with `capacity`, or `reserve`)")
-        layout, new_dst, surv_off, drop_before = self.layout.updated(drop, lab)
-        dev = self.device
-        s = _lib.stream_handle(dev)
-        status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        tmp = None
-        # the successor needs an inv_norm64 only when this index has one or the
-        # batch brings such a row (the ingest's LMI_STATUS_ROWS_LOW_NORM): an
-        # update of an index without them launches and reads nothing more
-        low64 = self.inv_norm64 is not None
-        if inplace and m:
-            # the batch first, into a temporary [m, d_pad] buffer: its status
-            # word is read before any row of the store moves
-            x = self._batch_rows(rows)
-            tmp = torch.empty((m, self.d_pad), dtype=torch.float16, device=dev)
-            tmp_inv = torch.empty((m,), dtype=torch.float32, device=dev)
-            seq = torch.arange(m, dtype=torch.int64, device=dev)
-            check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
-                ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
-                self.d, self.d_pad, ptr(seq), ptr(tmp), ptr(tmp_inv), m, ptr(status), s))
-            st = int(status.item())
-            if st & _lib.LMI_STATUS_ROWS_NOT_F16:
-                raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
-            if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
-                raise RuntimeError(f"index update: internal status {st} (the index is unchanged)")
-            del x, tmp_inv, seq
-        p2id = np.empty(n_new, np.int64)
-        BucketLayout.place_survivors(np.delete(self.pos_to_id, drop) if r else self.pos_to_id, surv_off,
-                                     layout.bucket_off, p2id)
-        p2id[new_dst] = ids
-        t_by_pos = None
-        if self.tags_by_pos is not None:
-            t_by_pos = BucketLayout.updated_table(
-                self.tags_by_pos, drop, surv_off, layout.bucket_off, new_dst,
-                new_tags if new_tags is not None else np.zeros(m, np.uint32))
-        new = self._successor(layout, p2id, None if inplace else max(self.capacity, n_new), t_by_pos)
-        ev = None
-        if timings is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        d_drop = torch.from_numpy(drop.astype(np.int64)).to(dev) if r else None
-        d_before = torch.from_numpy(drop_before).to(dev) if r else None
-        d_dst = torch.from_numpy(new_dst).to(dev) if m else None
-        if not inplace:
-            if ev:
-                ev[0].record()
-            if n_old - r > 0:
-                check("lmi_index_move_rows", lib.lmi_index_move_rows(
-                    ptr(self.corpus), ptr(self.inv_norm), n_old, self.d_pad, ptr(self.bucket_off_local),
-                    ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
-                    ptr(new.corpus), ptr(new.inv_norm), n_new, ptr(status), s))
-            if ev:
-                ev[1].record()
-            if m:
-                x = self._batch_rows(rows)
-                check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
-                    ptr(x), _lib.LMI_F16 if x.dtype == torch.float16 else _lib.LMI_F32, m, x.stride(0),
-                    self.d, self.d_pad, ptr(d_dst), ptr(new.corpus), ptr(new.inv_norm), n_new,
-                    ptr(status), s))
-            st = int(status.item())  # (waits for both kernels: the inputs above stay alive until here)
-            if st & _lib.LMI_STATUS_ROWS_NOT_F16:
-                raise ValueError("index update: float32 rows must be fp16-representable (storage 'f16')")
-            if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
-                raise RuntimeError(f"index update: internal status {st}")
-            if low64 or st & _lib.LMI_STATUS_ROWS_LOW_NORM:
-                new._set_inv_norm64()
-            if ev:
-                timings["move_ms"] = ev[0].elapsed_time(ev[1])
-                timings["moved_rows"] = n_old - r
-            return new
-        # ---- in place (K9): the slab plan, then the whole chain in one call ----
-        row_bytes = 2 * self.d_pad + 4
-        if slab_rows is None:
-            slab_rows = max(1, min(DEFAULT_SLAB_ROWS, STAGING_MAX_BYTES // row_bytes))
-        if direct_rows is None:
-            direct_rows = DEFAULT_DIRECT_ROWS
-        slabs = np.ascontiguousarray(self.layout.inplace_slabs(layout.bucket_off, drop, slab_rows,
-                                                               direct_rows))
-        staged = slabs[slabs[:, 2] == 1]
-        stage_rows = int((staged[:, 1] - staged[:, 0]).max()) if staged.size else 0
-        stage = stage_inv = None
-        if stage_rows:
-            stage = torch.empty((stage_rows, self.d_pad), dtype=torch.float16, device=dev)
-            stage_inv = torch.empty((stage_rows,), dtype=torch.float32, device=dev)
-        store, store_inv, cap = self._store, self._store_inv, self.capacity
-        old_off = self.bucket_off_local
-        # everything queued on the device (replays on other streams that read
-        # this index) finishes before the first row moves
-        torch.cuda.synchronize(dev)
-        if ev:
-            ev[0].record()
-        rc = lib.lmi_index_move_rows_inplace(
-            ptr(store), ptr(store_inv), n_old, n_new, cap, self.d_pad, ptr(old_off),
-            ptr(new.bucket_off_local), self.n_buckets, ptr(d_drop), r, ptr(d_before),
-            _lib.LMI_INPLACE_REMOVE if r else _lib.LMI_INPLACE_ADD, slabs.ctypes.data,
-            int(slabs.shape[0]), ptr(stage), ptr(stage_inv), stage_rows,
-            _lib.LMI_INPLACE_MEMCPY if os.environ.get("LMI_INPLACE_MEMCPY") == "1" else 0,
-            ptr(status), s)
-        if rc == _lib.LMI_E_INVALID:
-            check("lmi_index_move_rows_inplace", rc)  # (refused on the host: nothing was launched)
-        # from here on rows may have moved: this object must not launch again
-        self._consume()
-        check("lmi_index_move_rows_inplace", rc)
-        if ev:
-            ev[1].record()
-        if m:
-            # the batch, from the temporary to its places behind the moved rows
-            check("lmi_index_ingest_rows", lib.lmi_index_ingest_rows(
-                ptr(tmp), _lib.LMI_F16, m, self.d_pad, self.d, self.d_pad, ptr(d_dst), ptr(store),
-                ptr(store_inv), n_new, ptr(status), s))
-        st = int(status.item())  # (waits for the chain: the buffers above stay alive until here)
-        torch.cuda.synchronize(dev)
-        if st & ~_lib.LMI_STATUS_ROWS_LOW_NORM:
-            raise RuntimeError(f"index update in place: internal status {st}; the index is consumed "
-                               "and the content of its store is undefined")
-        new._store, new._store_inv, new._capacity = store, store_inv, cap
-        new.corpus, new.inv_norm = store[:n_new], store_inv[:n_new]
-        if low64 or st & _lib.LMI_STATUS_ROWS_LOW_NORM:
-            new._set_inv_norm64()
-        new._desc = IndexDescHolder(new)
-        if ev:
-            timings["move_ms"] = ev[0].elapsed_time(ev[1])
-            timings["direct_slabs"] = int((slabs[:, 2] == 0).sum())
-            timings["staged_slabs"] = int((slabs[:, 2] == 1).sum())
-            timings["moved_rows"] = int((slabs[:, 1] - slabs[:, 0]).sum())
-            timings["staged_rows"] = int((staged[:, 1] - staged[:, 0]).sum())
-            timings["staging_rows"] = stage_rows
-        return new
+        return index_update.relabel(self, lab, C_, inplace, timings)
 
     @torch.no_grad()
     def _fill(self, data, gpos, storage):
@@ -1286,6 +705,8 @@ class DeviceIndex:
     @property
     def desc(self) -> _lib.IndexDesc:
         self._check_live()
+        if self._desc is None:
+            self._desc = IndexDescHolder(self)
         return self._desc.desc
 
     def desc_for(self, k: int, f64: bool = False) -> _lib.IndexDesc:
@@ -1301,7 +722,7 @@ class DeviceIndex:
             return self._desc64.desc
         if self.storage != "f32x" or k <= _lib.LMI_MAX_K:
             return self.desc
-        if getattr(self, "_desc32", None) is None:
+        if self._desc32 is None:
             self._desc32 = IndexDescHolder(self, general32=True)
         return self._desc32.desc
 

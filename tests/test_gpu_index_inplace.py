@@ -439,3 +439,106 @@ def test_learned_index_insert_and_delete_in_place():
         assert np.array_equal(a[i], b[i]), i
     for i in (3, 7):
         assert np.array_equal(a[i][0], b[i][0]) and np.array_equal(a[i][1], b[i][1]), i
+
+
+@pytest.mark.parametrize("d", [32, 40], ids=["d32", "d40pad64"])
+def test_mixed_chain_of_updates_equals_rebuild_in_every_table(d):
+    """One tagged index with a capacity and a low-norm row through add, remove,
+    relabel and reserve, copying and in place in turn: after every step the
+    from-scratch construction over the row sequence, and beside _same what the
+    successor and the store hand-over set -- tags, inv_norm64, the capacity
+    rule, the store pointers, the predecessor consumed or still intact."""
+    from li.index import DeviceIndex, DeviceRouter, Searcher
+    n0, cap0, plan = 300, 400, dict(slab_rows=16, direct_rows=8)
+    w = workloads.clustered(n=n0 + 60, d=d, nq=16, C=7, seed=21, label_mode="router")
+    rng = np.random.Generator(np.random.PCG64(d))
+    pool = w["x"].copy()
+    pool[5] = 0
+    pool[5, 3] = 2.0 ** -24                        # norm below 10 eps(float32): inv_norm64 exists
+    pool[n0] = 0
+    pool[n0, d - 1] = 2.0 ** -24                   # ... and the first batch brings another
+
+    def labels(n, C_=7):                           # seven buckets, bucket 3 stays empty; five, bucket 2
+        return rng.choice(np.array([0, 1, 2, 4, 5, 6] if C_ == 7 else [0, 1, 3, 4]), n)
+
+    seq = dict(x=pool[:n0], labels=labels(n0), ids=np.arange(1, n0 + 1, dtype=np.int64),
+               tags=rng.integers(0, 1 << 32, n0, dtype=np.uint64).astype(np.uint32))
+
+    def rebuild(C_=7):
+        return DeviceIndex(seq["x"], seq["labels"], C_, ids=seq["ids"], tags=seq["tags"], device=DEV)
+
+    last = {}                                      # the rebuild the index in hand was last compared with
+
+    def check(got, capacity, C_=None):
+        want = last["want"] = rebuild(C_) if C_ else last["want"]
+        _same(got, want)
+        assert got.tags.dtype == want.tags.dtype and torch.equal(got.tags, want.tags)
+        assert got.tags_by_pos.dtype == np.uint32 and np.array_equal(got.tags_by_pos, want.tags_by_pos)
+        assert want.inv_norm64 is not None and torch.equal(got.inv_norm64, want.inv_norm64)
+        assert got.capacity == capacity == got._store.shape[0] == got._store_inv.shape[0]
+        assert not got.consumed
+
+    def step(index, call, capacity, C_=7, inplace=False):
+        ptrs = (index._store.data_ptr(), index._store_inv.data_ptr())
+        new = call(index)
+        if inplace:
+            assert index.consumed and index._store is None and index.corpus is None
+            assert (new._store.data_ptr(), new._store_inv.data_ptr()) == ptrs
+        else:                                      # the predecessor: live, and still its own rebuild
+            check(index, index.capacity)
+            assert (index._store.data_ptr(), index._store_inv.data_ptr()) == ptrs
+            assert new._store.data_ptr() != ptrs[0]
+        check(new, capacity, C_)
+        return new
+
+    def added(a, b, C_=7):
+        lab, tags = labels(b - a, C_), rng.integers(0, 1 << 32, b - a, dtype=np.uint64).astype(np.uint32)
+        ids = np.arange(1000 + a, 1000 + b, dtype=np.int64)
+        for k, v in (("x", pool[a:b]), ("labels", lab), ("ids", ids), ("tags", tags)):
+            seq[k] = np.concatenate([seq[k], v])
+        return pool[a:b], lab, ids, tags
+
+    def removed(count):
+        gone = rng.choice(seq["ids"][(seq["ids"] != 6) & (seq["ids"] != 1000 + n0)], count, replace=False)
+        keep = ~np.isin(seq["ids"], gone)
+        for k in seq:
+            seq[k] = seq[k][keep]
+        return gone
+
+    def relabelled(C_):
+        seq["labels"] = labels(len(seq["ids"]), C_)
+        return seq["labels"]
+
+    index = rebuild()
+    assert index.capacity == n0
+    index = DeviceIndex(seq["x"], seq["labels"], 7, ids=seq["ids"], tags=seq["tags"], device=DEV, capacity=cap0)
+    check(index, cap0, 7)
+    searcher = Searcher(index, DeviceRouter(w["layers"], device=DEV))
+    t = {}
+    batch = added(n0, n0 + 20)
+    index = step(index, lambda ix: ix.add(*batch, inplace=True, timings=t, **plan), cap0, inplace=True)
+    assert t["staged_slabs"] > 0 and t["direct_slabs"] > 0 and t["move_ms"] >= 0 and t["staging_rows"] <= 16
+    batch = added(0, 0)                            # a batch of 0 rows
+    index = step(index, lambda ix: ix.add(*batch, inplace=True, **plan), cap0, inplace=True)
+    lab = relabelled(7)
+    index = step(index, lambda ix: ix.relabel(torch.from_numpy(lab).to(DEV), inplace=True), cap0, inplace=True)
+    gone = removed(37)
+    index = step(index, lambda ix: ix.remove(gone), cap0)
+    gone = removed(0)                              # removes 0 ids
+    index = step(index, lambda ix: ix.remove(gone), cap0)
+    lab = relabelled(5)                            # to another bucket count
+    index = step(index, lambda ix: ix.relabel(lab, 5), cap0, C_=5)
+    batch = added(n0 + 20, n0 + 45, 5)
+    index = step(index, lambda ix: ix.add(*batch), cap0, C_=5)
+    gone = removed(60)
+    index = step(index, lambda ix: ix.remove(gone, inplace=True, **plan), cap0, C_=5, inplace=True)
+    index = step(index, lambda ix: ix.reserve(cap0 + 50), cap0 + 50, C_=5)
+    t = {}
+    lab = relabelled(7)                            # ... and back, for the router's seven classes
+    index = step(index, lambda ix: ix.relabel(lab, 7, inplace=True, timings=t), cap0 + 50, inplace=True)
+    assert {"sort", "tables", "host", "plan", "swap", "plan_ms", "plan_rounds", "swap_ms", "swapped_rows"} <= set(t)
+    assert "gather" not in t and len(t["swap_ms"]) == 2 and index.bucket_size[3] == 0
+    qn, q = torch.from_numpy(w["qn"]).to(DEV), torch.from_numpy(w["q"]).to(DEV)
+    got = searcher.with_index(index).search(qn, q, 3, k=10, use_threshold=True, want=1)
+    want = searcher.with_index(rebuild()).search(qn, q, 3, k=10, use_threshold=True, want=1)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
