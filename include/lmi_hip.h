@@ -302,6 +302,52 @@ int lmi_bucket_topk_tagged(const lmi_index_desc* idx, const uint32_t* tags, cons
                            int32_t R, int32_t k, int32_t qmode, float* out_d, int32_t* out_pos,
                            int32_t* status, void* workspace, size_t ws_bytes, void* stream);
 
+/* K2 masked: the tagged scan with all-of and none-of bits in one predicate.  A
+ * row is eligible for a query iff (tag & mask) == value, with
+ *   value = want            the bits the row must have
+ *   mask  = want | avoid    those and the bits it must not have
+ * so (tag & want) == want and (tag & avoid) == 0.  lmi_bucket_topk_tagged is
+ * this call with mask = want.  The kernels, the plan, the lists, the workspace
+ * (lmi_scan_tagged_workspace_bytes) and every refusal are lmi_bucket_topk_tagged's.
+ *   value, mask            device [nq] uint32 each
+ *   host_value, host_mask  host [nq] copies of the two, or both null.  Where
+ *                          they are given, a query with (value & ~mask) != 0 --
+ *                          a bit both wanted and avoided, which the test would
+ *                          read as wanted -- is LMI_E_INVALID before any launch,
+ *                          device or no device; null: the caller has checked.
+ * lmi_bucket_range_masked is lmi_bucket_range with the same two words and the
+ * same host copies (tags, value and mask: all or none; untagged calls take
+ * lmi_bucket_range).
+ * Additions: LMI_ABI_VERSION does not change. */
+int lmi_bucket_topk_masked(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* value,
+                           const uint32_t* mask, const uint32_t* host_value, const uint32_t* host_mask,
+                           const float* q, int32_t nq, int32_t ldq, const int32_t* classes, int32_t R,
+                           int32_t k, int32_t qmode, float* out_d, int32_t* out_pos, int32_t* status,
+                           void* workspace, size_t ws_bytes, void* stream);
+int lmi_bucket_range_masked(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* value,
+                            const uint32_t* mask, const uint32_t* host_value, const uint32_t* host_mask,
+                            const float* q, int32_t nq, int32_t ldq, const int32_t* classes, int32_t R,
+                            int32_t qmode, const float* bound, int32_t pair_cap, uint64_t* cand,
+                            uint32_t* count, int32_t* status, void* workspace, size_t ws_bytes,
+                            void* stream);
+
+/* Tag edits in place: tags[rows[i]] = (tags[rows[i]] & ~clear[i]) | set[i] for
+ * i < n, on the device tag words of a tagged index (the array the tagged scans
+ * read), in stream order.  One launch of a grid-stride kernel; no atomics: the
+ * rows of one call must be distinct (the caller guarantees it).
+ *   tags             device [n_rows] uint32
+ *   rows             device [n] int64 shard-local rows
+ *   clear, set       device [n] uint32
+ * A rows[i] outside [0, n_rows) writes nothing for that entry and raises
+ * LMI_STATUS_INTERNAL in *status (device int32).  n == 0 is a no-op.
+ * LMI_E_INVALID before any launch: n or n_rows < 0, a null pointer with n > 0.
+ * The recipe for deletes by tombstone: set one reserved bit on the rows to hide
+ * (a 4-byte scatter each), pass that bit as `avoid` (mask) to every search, and
+ * compact the marked rows later in one batch.
+ * Additions: LMI_ABI_VERSION does not change. */
+int lmi_index_edit_tags(uint32_t* tags, int64_t n_rows, const int64_t* rows, const uint32_t* clear,
+                        const uint32_t* set, int64_t n, int32_t* status, void* stream);
+
 /* K11 range search: every row of the probed buckets within a per-query bound.
  *
  * lmi_bucket_range is the collect scan.  For pair p = q * R + r it writes

@@ -46,10 +46,13 @@ struct RangeCfg {
     using QT = typename std::conditional<F16MATH, _Float16, float>::type;
 };
 
+// (per query slot: 1/|q|, the bound, the pair id, the tag value word; 16 bytes
+// for the tile counter; then the slots' tag mask words)
 template <bool F16MATH>
 size_t range_lds_bytes(int d_pad) {
     using Cfg = RangeCfg<F16MATH>;
-    return (size_t)Cfg::QB * (d_pad + Cfg::QPAD) * sizeof(typename Cfg::QT) + (size_t)Cfg::QB * 16 + 16;
+    return (size_t)Cfg::QB * (d_pad + Cfg::QPAD) * sizeof(typename Cfg::QT) + (size_t)Cfg::QB * 16 + 16 +
+           (size_t)Cfg::QB * 4;
 }
 
 template <bool F16MATH, typename TC, bool TAG>
@@ -68,6 +71,7 @@ __global__ __launch_bounds__(kThreads, 1) void range_scan_kernel(RangeArgs ra) {
     int32_t* pid_s = reinterpret_cast<int32_t*>(bound_s + QB);
     uint32_t* want_s = reinterpret_cast<uint32_t*>(pid_s + QB);
     int& s_tile = *reinterpret_cast<int*>(want_s + QB);
+    uint32_t* mask_s = want_s + QB + 4;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -111,7 +115,9 @@ __global__ __launch_bounds__(kThreads, 1) void range_scan_kernel(RangeArgs ra) {
                 invq_s[r] = live ? a.invq[q] : 0.0f;
                 bound_s[r] = live ? ra.bound[q] : -__builtin_inff();  // dead slots take nothing
                 pid_s[r] = pid;
-                want_s[r] = (TAG && live) ? a.want[q] : 0u;
+                // (TAG: a.want holds (1/|q|, value, mask) triples)
+                want_s[r] = (TAG && live) ? a.want[3 * (size_t)q + 1] : 0u;
+                if (TAG) mask_s[r] = live ? a.want[3 * (size_t)q + 2] : 0u;
             }
         }
         __syncthreads();
@@ -207,7 +213,7 @@ __global__ __launch_bounds__(kThreads, 1) void range_scan_kernel(RangeArgs ra) {
             for (int f = 0; f < NQF; ++f) {
                 const int qslot = 32 * f + col;
                 const float invq = invq_s[qslot], bound = bound_s[qslot];
-                const uint32_t want = want_s[qslot];
+                const uint32_t want = want_s[qslot], tmask = TAG ? mask_s[qslot] : 0u;
                 float dv[16];
                 uint32_t mask = 0;
 #pragma unroll
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(kThreads, 1) void range_scan_kernel(RangeArgs ra) {
                     const bool valid = i < valid_rows;
                     const float inv = valid ? a.inv_norm[row_base + i] : 0.0f;
                     dv[reg] = fmaf(-acc[f][reg], invq * inv, 1.0f);
-                    const bool tag_ok = !TAG || (valid && (a.tags[row_base + i] & want) == want);
+                    const bool tag_ok = !TAG || (valid && (a.tags[row_base + i] & tmask) == want);
                     mask |= (valid && dv[reg] <= bound && tag_ok) ? (1u << reg) : 0u;
                 }
                 if (!__any(mask != 0)) continue;
@@ -426,9 +432,21 @@ extern "C" int lmi_bucket_range(const lmi_index_desc* idx, const uint32_t* tags,
                                 int32_t qmode, const float* bound, int32_t pair_cap, uint64_t* cand,
                                 uint32_t* count, int32_t* status, void* workspace, size_t ws_bytes,
                                 void* stream) {
+    return lmi_bucket_range_masked(idx, tags, want, want, nullptr, nullptr, q, nq, ldq, classes, R, qmode, bound,
+                                   pair_cap, cand, count, status, workspace, ws_bytes, stream);
+}
+
+extern "C" int lmi_bucket_range_masked(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* want,
+                                       const uint32_t* mask, const uint32_t* host_value,
+                                       const uint32_t* host_mask, const float* q, int32_t nq, int32_t ldq,
+                                       const int32_t* classes, int32_t R, int32_t qmode, const float* bound,
+                                       int32_t pair_cap, uint64_t* cand, uint32_t* count, int32_t* status,
+                                       void* workspace, size_t ws_bytes, void* stream) {
     using namespace lmi;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     LMI_TRY(range_check(idx, tags != nullptr, want != nullptr, nq, R, qmode, pair_cap));
+    LMI_CHECK_ARG((want != nullptr) == (mask != nullptr), "lmi_bucket_range: value and mask come together");
+    LMI_TRY(masked_words_check("lmi_bucket_range_masked", host_value, host_mask, nq));
     LMI_CHECK_ARG(ldq >= idx->d, "lmi_bucket_range: ldq < d");
     LMI_CHECK_ARG(join_wgs() == 0, "lmi_bucket_range: the range scan runs in one launch (join workgroups are set)");
     if (nq == 0) return LMI_OK;
@@ -459,6 +477,7 @@ extern "C" int lmi_bucket_range(const lmi_index_desc* idx, const uint32_t* tags,
         const RangeScan rs{bound, cand, count, pair_cap};
         c.tags = tags;
         c.want = want;
+        c.mask = mask;
         c.range = &rs;
         return bucket_topk_impl(c);
     }

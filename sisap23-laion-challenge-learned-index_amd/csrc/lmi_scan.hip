@@ -826,12 +826,17 @@ __global__ __launch_bounds__(256) void set_bound_kernel(const int32_t* __restric
 }
 
 // the tagged scan on the 8-wave ring (scan3_kernel MODE 4): every query's
-// (1/|q|, want) as one pair
+// (1/|q|, value, mask) as one triple
 __global__ __launch_bounds__(256) void want_pack_kernel(const float* __restrict__ invq,
-                                                        const uint32_t* __restrict__ want, int32_t nq,
-                                                        uint2* __restrict__ out) {
+                                                        const uint32_t* __restrict__ value,
+                                                        const uint32_t* __restrict__ mask, int32_t nq,
+                                                        uint32_t* __restrict__ out) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) out[q] = make_uint2(__float_as_uint(invq[q]), want[q]);
+    if (q < nq) {
+        out[3 * (size_t)q] = __float_as_uint(invq[q]);
+        out[3 * (size_t)q + 1] = value[q];
+        out[3 * (size_t)q + 2] = mask[q];
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1122,28 +1127,65 @@ extern "C" size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int
     return scan_plan(idx, nq, R, k, qmode, false, true).total;
 }
 
+namespace lmi {
+namespace {
+// lmi_bucket_topk_tagged (mask = want) and lmi_bucket_topk_masked, `fn` the
+// entry's name for the messages
+int topk_masked(const char* fn, const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* value,
+                const uint32_t* mask, const float* q, int32_t nq, int32_t ldq, const int32_t* classes, int32_t R,
+                int32_t k, int32_t qmode, float* out_d, int32_t* out_pos, int32_t* status, void* workspace,
+                size_t ws_bytes, void* stream) {
+    // (every refusal comes before any launch and needs no device)
+    LMI_CHECK_ARG(idx != nullptr, "null index");
+    LMI_CHECK_ARG(tags != nullptr && value != nullptr && mask != nullptr, "%s: null tags or want", fn);
+    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: k=%d outside [1, %d]", fn, k, LMI_MAX_K);
+    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64, "%s: the split mode (corpus32 / corpus64) takes no tags", fn);
+    LMI_CHECK_ARG(!idx->chunk_centroid, "%s: sub-cluster layouts (chunk_centroid) take no tags", fn);
+    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32,
+                  "%s: qmode 0x%x: LMI_Q_F16 or LMI_Q_F32 alone (no phase, join or seed flag)", fn, qmode);
+    const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
+                     .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
+                     .workspace = workspace, .ws_bytes = ws_bytes,
+                     .stream = reinterpret_cast<hipStream_t>(stream), .tags = tags, .want = value, .mask = mask};
+    // (with join workgroups set on this thread bucket_topk_impl refuses the
+    // call: the tagged scan runs in one launch)
+    return bucket_topk_impl(c);
+}
+}  // namespace
+
+int masked_words_check(const char* fn, const uint32_t* host_value, const uint32_t* host_mask, int32_t nq) {
+    LMI_CHECK_ARG((host_value != nullptr) == (host_mask != nullptr), "%s: host_value and host_mask come together", fn);
+    if (host_value == nullptr) return LMI_OK;
+    for (int32_t i = 0; i < nq; ++i)
+        LMI_CHECK_ARG((host_value[i] & ~host_mask[i]) == 0u,
+                      "%s: query %d: value 0x%x has bits outside mask 0x%x (a bit both wanted and avoided)", fn, i,
+                      host_value[i], host_mask[i]);
+    return LMI_OK;
+}
+}  // namespace lmi
+
 extern "C" int lmi_bucket_topk_tagged(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* want,
                                       const float* q, int32_t nq, int32_t ldq, const int32_t* classes,
                                       int32_t R, int32_t k, int32_t qmode, float* out_d, int32_t* out_pos,
                                       int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
+    return lmi::topk_masked("lmi_bucket_topk_tagged", idx, tags, want, want, q, nq, ldq, classes, R, k, qmode, out_d,
+                            out_pos, status, workspace, ws_bytes, stream);
+}
+
+extern "C" int lmi_bucket_topk_masked(const lmi_index_desc* idx, const uint32_t* tags, const uint32_t* value,
+                                      const uint32_t* mask, const uint32_t* host_value,
+                                      const uint32_t* host_mask, const float* q, int32_t nq, int32_t ldq,
+                                      const int32_t* classes, int32_t R, int32_t k, int32_t qmode, float* out_d,
+                                      int32_t* out_pos, int32_t* status, void* workspace, size_t ws_bytes,
+                                      void* stream) {
     using namespace lmi;
-    // (every refusal comes before any launch and needs no device)
     LMI_CHECK_ARG(idx != nullptr, "null index");
-    LMI_CHECK_ARG(tags != nullptr && want != nullptr, "lmi_bucket_topk_tagged: null tags or want");
-    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "lmi_bucket_topk_tagged: k=%d outside [1, %d]", k, LMI_MAX_K);
-    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
-                  "lmi_bucket_topk_tagged: the split mode (corpus32 / corpus64) takes no tags");
-    LMI_CHECK_ARG(!idx->chunk_centroid, "lmi_bucket_topk_tagged: sub-cluster layouts (chunk_centroid) take no tags");
-    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32,
-                  "lmi_bucket_topk_tagged: qmode 0x%x: LMI_Q_F16 or LMI_Q_F32 alone (no phase, join or seed flag)",
-                  qmode);
-    const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
-                     .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
-                     .workspace = workspace, .ws_bytes = ws_bytes,
-                     .stream = reinterpret_cast<hipStream_t>(stream), .tags = tags, .want = want};
-    // (with join workgroups set on this thread bucket_topk_impl refuses the
-    // call: the tagged scan runs in one launch)
-    return bucket_topk_impl(c);
+    LMI_CHECK_ARG(tags != nullptr && value != nullptr && mask != nullptr,
+                  "lmi_bucket_topk_masked: null tags, value or mask");
+    LMI_CHECK_ARG(nq >= 0, "lmi_bucket_topk_masked: nq < 0");
+    LMI_TRY(masked_words_check("lmi_bucket_topk_masked", host_value, host_mask, nq));
+    return topk_masked("lmi_bucket_topk_masked", idx, tags, value, mask, q, nq, ldq, classes, R, k, qmode, out_d,
+                       out_pos, status, workspace, ws_bytes, stream);
 }
 
 int lmi::bucket_topk_impl(const ScanCall& c) {
@@ -1171,7 +1213,8 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     LMI_CHECK_ARG(idx->n_rows == 0 || (idx->corpus && idx->inv_norm && idx->gpos), "null corpus arrays");
     LMI_CHECK_ARG(idx->bucket_off && idx->chunk_first, "null bucket tables");
 
-    LMI_CHECK_ARG((c.tags != nullptr) == (c.want != nullptr), "tags and want come together");
+    LMI_CHECK_ARG((c.tags != nullptr) == (c.want != nullptr) && (c.tags != nullptr) == (c.mask != nullptr),
+                  "tags, value and mask come together");
     const ScanPlan w = c.plan ? *c.plan : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr, c.tags != nullptr);
     if (c.ws_bytes < w.total) {
         set_error("workspace %zu B < required %zu B", c.ws_bytes, w.total);
@@ -1340,7 +1383,21 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     a.gpos = idx->gpos;
     a.lo_g = lo_g;
     a.tags = c.tags;
-    a.want = c.want;
+    if (c.tags != nullptr) {
+        // every tagged kernel reads (1/|q|, value, mask) triples: packed behind
+        // the plan's pair arrays, in the nearest-chunk-first plan's scratch
+        // (pref, pref_tmp, pref_tmp2: laid out one after the other, 3 P words
+        // >= 3 nq), which a tagged call never uses.  The 8-wave ring takes them
+        // as its invq (no pointer more in its scalar registers), the general
+        // kernel and the range scan as their want.
+        uint32_t* iw = reinterpret_cast<uint32_t*>(ws + w.pref);
+        if (do_plan) {
+            hipLaunchKernelGGL(want_pack_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, a.invq, c.want, c.mask,
+                               nq, iw);
+            LMI_LAUNCH_CHECK("want_pack_kernel");
+        }
+        a.want = iw;
+    }
 
     // (the phases split the general kernel's call as they split the rings':
     // everything a later phase reads -- the rounded queries, the tile plan,
@@ -1371,15 +1428,8 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         b.ng = ng;
         b.lag = std::max(0, std::min(3, env_config().scan_lag));
         if (c.tags != nullptr) {
-            // MODE 4 reads (1/|q|, want) pairs: packed behind the plan's pair
-            // arrays, in the nearest-chunk-first plan's scratch (pref,
-            // pref_tmp: 2 P words >= 2 nq), which a tagged call never uses
-            uint2* iw = reinterpret_cast<uint2*>(ws + w.pref);
-            if (do_plan) {
-                hipLaunchKernelGGL(want_pack_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, a.invq, c.want, nq, iw);
-                LMI_LAUNCH_CHECK("want_pack_kernel");
-            }
-            b.invq = reinterpret_cast<const float*>(iw);
+            // (MODE 4 reads the triples packed above in place of 1/|q| alone)
+            b.invq = reinterpret_cast<const float*>(a.want);
             b.tags = c.tags;
         }
         if (wide) {

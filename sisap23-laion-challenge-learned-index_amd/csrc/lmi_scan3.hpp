@@ -81,9 +81,9 @@ constexpr size_t lds_bytes() { return (size_t)NSLOT * STAGE + (size_t)NW * 64 * 
 static_assert(lds_bytes<15>() <= 160 * 1024, "LDS budget");
 // MODE 4 (tagged), behind lds_bytes<10>(): the 32 tag words of each of the
 // three blocks in flight (laid out like the blocks' norms), then every wave's
-// 32 want words (one per query column)
+// 32 (value, mask) pairs (one per query column, 8 bytes each)
 constexpr int TAG_AREA = 3 * 128;
-constexpr int WANT_AREA = NW * 32 * 4;
+constexpr int WANT_AREA = NW * 32 * 8;
 static_assert(lds_bytes<10>() + TAG_AREA + WANT_AREA <= 160 * 1024, "LDS budget");
 }  // namespace v3
 
@@ -326,18 +326,19 @@ __device__ __forceinline__ uint32_t opaque_u(uint32_t x) {
 // row of the part that passed the filter lies (kBandSlot entries, see
 // chunk_merge_band_kernel).
 // MODE 4 (lmi_bucket_topk_tagged, KL = 10): the product scan plus the tag
-// test -- a row is a candidate of a pair only if (tag & want) == want.  The
+// test -- a row is a candidate of a pair only if (tag & mask) == value
+// (mask = want | avoid, value = want: every wanted bit and no avoided one).  The
 // block's 32 tag words arrive by a 4-byte LDS-DMA beside its norms (lanes 0-3
-// of each wave, the same addressing); the pair's want word waits in a
+// of each wave, the same addressing); the pair's (value, mask) words wait in a
 // per-wave LDS slot written at the tile start.  The test sits in the
-// per-candidate walk (one LDS read of the tag word, one of the want word, at
-// addresses made inside the iteration): a candidate that fails is skipped
+// per-candidate walk (one LDS read of the tag word, one 8-byte read of the pair's
+// two words, at addresses made inside the iteration): a candidate that fails is skipped
 // before the list is touched, so it enters no list and tightens no bound, and
 // nothing new is live across the MFMA stream or around the walk (the kernel
 // has no VGPR and no SGPR to spare: the mask-stage form -- the predicate ANDed
 // into `ok` -- spilled a query fragment into the stream).
 // Bounds, the thr_g atomicMin, the 32-block bound exchange, the tail handling
-// and the lists are MODE 0's; never seeded; invq holds (1/|q|, want) pairs.
+// and the lists are MODE 0's; never seeded; invq holds (1/|q|, value, mask) triples.
 template <int KL, int ABL = 0, bool LO = false, int MODE = 0>
 __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     using namespace v3;
@@ -571,11 +572,12 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                 if (a.pair_pos && live) thr = std::min(thr, round0_seed(a, pp));
             }
             if constexpr (MODE == 4) {
-                // (invq holds (1/|q|, want) pairs here, see Scan2Args; both
-                // lanes of a column write the same want word)
-                const uint2 iw = live ? reinterpret_cast<const uint2*>(a.invq)[q] : make_uint2(0u, 0u);
-                my_invq = __uint_as_float(iw.x);
-                lds_put_u32((uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 128) + (uint32_t)col * 4u, iw.y);
+                // (invq holds (1/|q|, value, mask) triples here, see Scan2Args;
+                // both lanes of a column write the same two words)
+                const uint32_t* iw = reinterpret_cast<const uint32_t*>(a.invq) + 3 * (size_t)q;
+                my_invq = live ? __uint_as_float(iw[0]) : 0.0f;
+                const uint64_t vm = live ? ((uint64_t)iw[2] << 32) | iw[1] : 0ull;
+                lds_put_u64_at<0>((uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 256) + (uint32_t)col * 8u, vm);
             } else
             my_invq = live ? a.invq[q] : 0.0f;
             if constexpr (MODE == 1) {
@@ -773,21 +775,21 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                         const float n1 = *reinterpret_cast<const float*>(nb + i * 4);
                         const float d = fmaf(-select16(acc, rg), my_invq * n1, 1.0f);
                         const uint64_t key = make_key(d, rb + (uint32_t)i);
-                        // (MODE 4) the candidate's tag word and the pair's want
-                        // word, both from LDS at addresses made here from the
+                        // (MODE 4) the candidate's tag word and the pair's value
+                        // and mask words, all from LDS at addresses made here from the
                         // lane id: nothing new is live around the walk
                         auto tag_ok = [&] {
                             const int l2 = opaque(ln);
                             const uint32_t ts = (uint32_t)(uintptr_t)tag_area + (uint32_t)((eb % 3) * 128);
                             const uint32_t tg = lds_get_u32(ts + (uint32_t)((l2 >> 5) * 16 + i * 4));
-                            const uint32_t want = lds_get_u32(
-                                (uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 128) + (uint32_t)(l2 & 31) * 4u);
-                            return (tg & want) == want;
+                            const uint64_t vm = lds_get_u64_at<0>(
+                                (uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 256) + (uint32_t)(l2 & 31) * 8u);
+                            return (tg & (uint32_t)(vm >> 32)) == (uint32_t)vm;
                         };
                         if (LO && d == lo_d && eb * 32 + 4 * hh + i < lo_row) {
                             // at or before the pair's lower bound: not this pass's
                         } else if (MODE == 4 && !tag_ok()) {
-                            // (MODE 4) the row lacks a wanted bit: not a candidate
+                            // (MODE 4) the row lacks a wanted bit or has an avoided one: not a candidate
                         } else if (cnt < KL) {
                             // append mode: the first KL candidates are stored
                             // unsorted; a full buffer is sorted once (stable)

@@ -50,7 +50,10 @@ struct ScanArgs {
     const int32_t* gpos;    // [n_rows] global positions (LO: ties at the lower bound)
     const unsigned long long* lo_g;  // [nq*R] LO: keep only keys above (d, gpos) of the pair
     const uint32_t* tags;   // TAG: [n_rows] tag word of every row (row order of corpus)
-    const uint32_t* want;   // TAG: [nq] want word of every query; row eligible iff (tag & want) == want
+    // TAG: [nq] triples (1/|q|, value, mask) of every query (want_pack_kernel);
+    // value = the wanted bits, mask = wanted | avoided; row eligible iff
+    // (tag & mask) == value
+    const uint32_t* want;
 };
 
 
@@ -153,10 +156,10 @@ struct Scan2Args {
     const int32_t* sub_rows;  // MODE 1: [C] rows per list of each bucket (its chunks)
     const int32_t* sub_take;  //   and the rows scanned from the start of each (a sample)
     // MODE 4 (lmi_bucket_topk_tagged): the rows' tag words ([n_rows], row order
-    // of corpus); a row is a candidate of a pair only if (tag & want) == want.
-    // The queries' want words come beside 1/|q|: invq is then [nq] pairs
-    // (1/|q|, want) (want_pack_kernel) -- one pointer less in scalar registers,
-    // of which the kernel has none to spare
+    // of corpus); a row is a candidate of a pair only if (tag & mask) == value.
+    // The queries' two words come beside 1/|q|: invq is then [nq] triples
+    // (1/|q|, value, mask) (want_pack_kernel) -- no pointer more in scalar
+    // registers, of which the kernel has none to spare
     const uint32_t* tags;
 };
 
@@ -293,7 +296,7 @@ struct WideScan {
     int32_t app_k;
 };
 // The general kernel's collect form (K11 range search, lmi_range.hip): every
-// row of a pair with d <= bound[q] (and (tag & want) == want when tagged) goes
+// row of a pair with d <= bound[q] (and (tag & mask) == value when tagged) goes
 // to cand[pair id * cap + i] as make_key(d, row), i from ccount[pair id], which
 // counts every hit (slots past cap are counted, not stored).  No lists, no merge.
 struct RangeScan {
@@ -350,15 +353,20 @@ struct ScanCall {
     // scan_plan() of this call where the caller holds it (it reads the scan's
     // region afterwards); null: built here
     const ScanPlan* plan = nullptr;
-    // lmi_bucket_topk_tagged: device [n_rows] tag words and [nq] want words
-    // (both or neither); only rows with (tag & want) == want are listed
+    // lmi_bucket_topk_masked: device [n_rows] tag words and [nq] value and mask
+    // words (all or none); only rows with (tag & mask) == value are listed
+    // (lmi_bucket_topk_tagged: mask = want)
     const uint32_t* tags = nullptr;
-    const uint32_t* want = nullptr;
+    const uint32_t* want = nullptr;  // the value words
+    const uint32_t* mask = nullptr;
     // K11 range search: the general kernel's collect form in place of the list
     // scan (a plan of the general family, phases plan + scan, no prefill)
     const RangeScan* range = nullptr;
 };
 int bucket_topk_impl(const ScanCall& c);
+// the masked entries' host copies of their words (both or neither; null: not
+// checked): every value word inside its mask word, else LMI_E_INVALID
+int masked_words_check(const char* fn, const uint32_t* host_value, const uint32_t* host_mask, int32_t nq);
 
 // ---- k > LMI_MAX_K (lmi_scan_wide.hip) ---------------------------------------
 // passes_of() passes of kp-entry lists; bucket_topk_passes fills [nq*R][ldo]

@@ -52,16 +52,17 @@ __device__ inline bool above_lo(float d, uint64_t lo, const int32_t* __restrict_
     return o > hi || (o == hi && (uint32_t)gpos[row] > (uint32_t)lo);
 }
 
-// TAG (lmi_bucket_topk_tagged): only rows whose tag word holds every bit of
-// the query's want word are candidates, (tag & want) == want; tags is read
-// like inv_norm.
+// TAG (lmi_bucket_topk_masked): only rows whose tag word holds every wanted
+// bit and no avoided bit of the query are candidates, (tag & tmask) == want
+// (want: the value word, tmask = wanted | avoided); tags is read like inv_norm.
 template <int KL, bool LO = false, bool TAG = false>
 __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint64_t* thr_slot,
                                      float invq, const float* __restrict__ inv_norm,
                                      uint32_t row_base, int valid_rows, uint64_t* queue,
                                      int lane, uint64_t lo = 0,
                                      const int32_t* __restrict__ gpos = nullptr,
-                                     const uint32_t* __restrict__ tags = nullptr, uint32_t want = 0u) {
+                                     const uint32_t* __restrict__ tags = nullptr, uint32_t want = 0u,
+                                     uint32_t tmask = 0u) {
     const int h = lane >> 5;
     uint64_t thr = *thr_slot;
     float bound = key_dist_bound(thr);
@@ -72,7 +73,7 @@ __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint6
         const bool valid = i < valid_rows;
         const float inv = valid ? inv_norm[row_base + i] : 0.0f;
         const float d = fmaf(-acc[reg], invq * inv, 1.0f);
-        const bool tag_ok = !TAG || (valid && (tags[row_base + i] & want) == want);
+        const bool tag_ok = !TAG || (valid && (tags[row_base + i] & tmask) == want);
         if (valid && d <= bound && tag_ok && (!LO || above_lo(d, lo, gpos, row_base + (uint32_t)i))) {
             const uint64_t key = make_key(d, row_base + (uint32_t)i);
             if (key < thr) {
@@ -164,13 +165,15 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
 
         uint64_t L[NQF][KL];
         uint64_t lo[NQF];
-        uint32_t want[NQF];
+        uint32_t want[NQF], tmask[NQF];  // (TAG: the value and mask words, a.want's triples)
 #pragma unroll
         for (int f = 0; f < NQF; ++f) {
             list_clear<KL>(L[f]);
             const int r = 32 * f + col;
             lo[f] = (LO && r < tile.np) ? (uint64_t)a.lo_g[a.pair_q[tile.pp0 + r]] : 0ull;
-            want[f] = (TAG && r < tile.np) ? a.want[a.pair_q[tile.pp0 + r] / a.R] : 0u;
+            const size_t wq = (TAG && r < tile.np) ? 3 * (size_t)(a.pair_q[tile.pp0 + r] / a.R) : 0;
+            want[f] = (TAG && r < tile.np) ? a.want[wq + 1] : 0u;
+            tmask[f] = (TAG && r < tile.np) ? a.want[wq + 2] : 0u;
         }
 
         const int nsub = (nrows + 31) / 32;
@@ -264,7 +267,7 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
             for (int f = 0; f < NQF; ++f) {
                 const int qslot = 32 * f + col;
                 tile_epilogue<KL, LO, TAG>(acc[f], L[f], &thr_s[qslot], invq_s[qslot], a.inv_norm,
-                                           row_base, valid_rows, queue, lane, lo[f], a.gpos, a.tags, want[f]);
+                                           row_base, valid_rows, queue, lane, lo[f], a.gpos, a.tags, want[f], tmask[f]);
             }
         }
         __syncthreads();  // all waves done with Qs -> reuse as merge buffer

@@ -289,7 +289,7 @@ class LearnedIndex(Logger):
     # ---- search -------------------------------------------------------------
     def search(self, data_navigation, queries_navigation, data_search, queries_search,
                pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference",
-               stop_mass=None, min_buckets=1, timings=None, want=None):
+               stop_mass=None, min_buckets=1, timings=None, want=None, avoid=None):
         """Search for k nearest neighbors of each query (LearnedIndex.py:22-101).
         `semantics="exact"` (an addition; default off) returns the exact top-k of
         the union of the probed buckets instead of the reference's round merge.
@@ -304,7 +304,8 @@ class LearnedIndex(Logger):
         search, only objects with (tag & want) == want answer -- an int under
         the reference semantics (the answer of this search over the eligible
         objects alone), an int or one word per query under semantics="exact"
-        (Searcher.search)."""
+        (Searcher.search).  `avoid` (the same forms): and only objects with
+        (tag & avoid) == 0 -- with `retag`, deletes by tombstone."""
         from .index import check_stop
         check_stop(stop_mass, min_buckets)
         assert self.model is not None, 'Model is not trained, call `build` first.'
@@ -318,10 +319,11 @@ class LearnedIndex(Logger):
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist=dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
-                                                timings=timings, want=want)
+                                                timings=timings, want=want, avoid=avoid)
 
     def range_search(self, data_navigation, queries_navigation, data_search, queries_search,
-                     pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None):
+                     pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None,
+                     avoid=None):
         """Every object within `radius` (a number or one value per query;
         inclusive) of each query among its `n_buckets` probed buckets (an
         addition; the reference has top-k search only) -> (lims int64
@@ -329,7 +331,7 @@ class LearnedIndex(Logger):
         entries lims[i]:lims[i + 1], ordered by (distance, id position).  The
         distances run in the arithmetic of `search` (dist_dtype: float64 unless
         data and queries are both float32).  `stop_mass`, `min_buckets`,
-        `want`: as in search (want: an int or one word per query).
+        `want`, `avoid`: as in search (each an int or one word per query).
         Searcher.range_search has the details and the refusals."""
         from .index import check_stop
         check_stop(stop_mass, min_buckets)
@@ -342,7 +344,7 @@ class LearnedIndex(Logger):
         return self._get_searcher(index).range_search(
             q_nav, _upload_queries(queries_search, index.device), n_buckets, radius,
             dist=dist_dtype(data_search, queries_search), stop_mass=stop_mass, min_probes=min_buckets,
-            want=want)
+            want=want, avoid=avoid)
 
     def mean_probes(self, data_navigation, queries_navigation, data_search, pred_categories,
                     n_buckets, stop_mass, min_buckets=1):
@@ -483,6 +485,32 @@ class LearnedIndex(Logger):
         search2 = pd.concat([data_search, new_search])
         self._adopt(new_index, nav2, search2, labels2)
         return nav2, search2, labels2
+
+    def retag(self, ids, set_bits=0, clear_bits=0, tags=None):
+        """Change the tag words of attached objects in place, without a rebuild
+        and without new frames: tag = (tag & ~clear_bits) | set_bits on the
+        objects `ids` (DeviceIndex.edit_tags), or tag = `tags` (set_tags; then
+        set_bits and clear_bits stay 0).  The attached index is edited as it
+        stands -- later search calls with the same objects see the new tags --
+        and the tags this object remembers the index by change with it, so an
+        attach(..., tags=<the old words>) builds anew instead of reusing the
+        edited index.  Needs attach(..., tags=...) first (ValueError)."""
+        index = self._index
+        if index is None or index.tags_by_pos is None:
+            raise ValueError("retag: no tagged index is attached (attach(..., tags=...))")
+        if tags is not None:
+            if not (isinstance(set_bits, int) and set_bits == 0 and isinstance(clear_bits, int) and clear_bits == 0):
+                raise ValueError("retag: give `tags`, or set_bits / clear_bits, not both")
+            index.set_tags(ids, tags)
+        else:
+            index.edit_tags(ids, set_bits=set_bits, clear_bits=clear_bits)
+        key = self._cache_key
+        if key is not None and len(key) == 5 and key[0] != "updated":
+            seq = np.empty(index.n_total, np.uint32)   # (the words in the frames' order, as attach took them)
+            seq[index.layout.order] = index.tags_by_pos
+            self._cache_key = key[:4] + (content_key(seq),)
+            if self._trusted is not None and self._trusted[1] == key:
+                self._trusted = (self._trusted[0], self._cache_key, self._trusted[2])
 
     def delete(self, data_navigation, data_search, pred_categories, ids, inplace=False):
         """Remove the objects with the given ids without a rebuild

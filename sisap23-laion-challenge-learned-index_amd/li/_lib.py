@@ -78,6 +78,9 @@ EXPORTS = (
     "lmi_bucket_topk",
     "lmi_scan_tagged_workspace_bytes",
     "lmi_bucket_topk_tagged",
+    "lmi_bucket_topk_masked",
+    "lmi_bucket_range_masked",
+    "lmi_index_edit_tags",
     "lmi_range_workspace_bytes",
     "lmi_bucket_range",
     "lmi_range_rescore_f64",
@@ -204,6 +207,11 @@ _SIGNATURES = {
     "lmi_scan_tagged_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_tagged": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32,
                                          _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_bucket_topk_masked": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32,
+                                         _I32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_bucket_range_masked": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32,
+                                          _I32, _P, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_index_edit_tags": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P]),
     "lmi_range_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32, _I32]),
     "lmi_bucket_range": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32,
                                    _P, _P, _P, _P, C.c_size_t, _P]),

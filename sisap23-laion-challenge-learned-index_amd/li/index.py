@@ -190,6 +190,7 @@ class DeviceIndex:
     # untagged index
     tags_by_pos = None
     tags = None
+    tags_version = 0  # edit_tags / set_tags calls so far (Searcher drops its eligible-count cache on a change)
 
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
                  storage: str = "auto", chunk_rows: Optional[int] = None,
@@ -464,6 +465,34 @@ class DeviceIndex:
         none = np.zeros(0, np.int64)
         return index_update.update(self, drop, None, none, none, none.astype(np.uint32), inplace=inplace,
                                    slab_rows=slab_rows, direct_rows=direct_rows, timings=timings)
+
+    # ---- tag edits in place (csrc/lmi_tags.hip) -----------------
+    def edit_tags(self, ids, set_bits=0, clear_bits=0) -> None:
+        """tag = (tag & ~clear_bits) | set_bits on the stored objects `ids`, in
+        THIS index: no successor, nothing consumed, no row moves.  `set_bits`,
+        `clear_bits`: an int or one word per id, in [0, 2^32).  The host table
+        (tags_by_pos) and the device words (tags; one 4-byte scatter per id, in
+        stream order on the current stream) change together, and tags_version
+        counts the call.  Deletes by tombstone: edit_tags(ids, set_bits=T),
+        search(..., avoid=T), and later remove(ids_with(want=T)) in one batch.
+        ValueError before anything is launched: an untagged index, a striped
+        shard (world > 1), duplicate ids, words outside [0, 2^32); an id the
+        index does not hold raises as `remove` reports it (a KeyError that is a
+        ValueError too); a consumed index raises as every call on it does."""
+        index_update.edit_tags(self, ids, set_bits, clear_bits)
+
+    def set_tags(self, ids, tags) -> None:
+        """The tag words of the stored objects `ids` := `tags` (an int or one
+        word per id): edit_tags with every bit cleared first."""
+        index_update.edit_tags(self, ids, tags, 0xFFFFFFFF)
+
+    def ids_with(self, want: int = 0, avoid: int = 0) -> np.ndarray:
+        """int64: the ids of the stored objects with (tag & want) == want and
+        (tag & avoid) == 0, in position order; read from the host table."""
+        if self.tags_by_pos is None:
+            raise ValueError("ids_with: this index is untagged (build it with `tags`)")
+        value, mask = value_mask(_tag_word(want, "want"), _tag_word(avoid, "avoid"))
+        return self.pos_to_id[(self.tags_by_pos & mask) == value].astype(np.int64)
 
     # ---- re-bucket (K8: csrc/lmi_rebucket.hip; DESIGN.md §3) ------------------
     _sorted_by_bucket = staticmethod(index_update.sorted_by_bucket)
@@ -907,7 +936,7 @@ def _workspace(ws, need: int, what: str) -> torch.Tensor:
 
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                 qmode: Optional[int] = None, stream=None, out=None, ws=None,
-                seed_round0: bool = False, phases: int = 0, want=None):
+                seed_round0: bool = False, phases: int = 0, want=None, avoid=None):
     """K2 on one shard.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
     `out` = such a triple to write into (the status word zeroed by the caller);
     `ws` = a caller-owned uint8 workspace (default: the index's cached one,
@@ -917,8 +946,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     `phases` (LMI_Q_PHASE_* bits, 0 = all): run only those phases of the call
     (StreamedSearch overlaps one batch's plan with another's scan).
     `want` (a tagged index; device int32 [nq], the want words' bits, see
-    want_words): the tagged scan, lmi_bucket_topk_tagged -- only rows with
-    (tag & want) == want are listed; never seeded, no phases."""
+    want_words): the tagged scan, lmi_bucket_topk_masked -- only rows with
+    (tag & want) == want are listed; never seeded, no phases.  `avoid` (the
+    same form; alone it means want = 0): and only rows with (tag & avoid) == 0.
+    At this level the words are on the device: that no query wants and avoids
+    one bit is the caller's check (mask_words makes it on the host)."""
     lib = _lib.load()
     q = _rows_f32(q, index.device)
     classes = _as_torch(classes, index.device, torch.int32)
@@ -927,8 +959,8 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
         raise ValueError("query shape does not match the index")
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
-    if want is not None:
-        return _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phases)
+    if want is not None or avoid is not None:
+        return _bucket_topk_tagged(index, q, classes, k, qmode, want, avoid, stream, out, ws, phases)
     desc = index.desc_for(k)
     if out is None:
         out_d = torch.empty((nq, R, k), dtype=torch.float32, device=index.device)
@@ -958,42 +990,107 @@ def want_words(index: DeviceIndex, want, nq: int, k_list: int, dist: str = "f32"
     dist="f64", on storage "f32x", on k_list > LMI_MAX_K, and for a `want` that
     is neither an integer in [0, 2^32) nor (per_query) an integer array [nq]
     of such."""
+    return _as_i32_bits(_host_words(index, want, nq, k_list, dist, per_query, "want")).to(index.device)
+
+
+def _host_words(index, word, nq, k_list, dist, per_query, name) -> np.ndarray:
+    """want_words' checks on the words `word` of the keyword `name`; host uint32 [nq]."""
     if index.tags is None:
-        raise ValueError("want: this index is untagged (build it with `tags`)")
+        raise ValueError(f"{name}: this index is untagged (build it with `tags`)")
     if dist != "f32":
-        raise ValueError("want: filtered search is not offered with dist='f64'")
+        raise ValueError(f"{name}: filtered search is not offered with dist='f64'")
     if index.storage == "f32x":
-        raise ValueError("want: filtered search is not offered on storage 'f32x' (the split mode)")
+        raise ValueError(f"{name}: filtered search is not offered on storage 'f32x' (the split mode)")
     if k_list > _lib.LMI_MAX_K:
-        raise ValueError(f"want: filtered search takes lists of at most {_lib.LMI_MAX_K} entries, not {k_list}")
-    if isinstance(want, (int, np.integer)) and not isinstance(want, bool):
-        if not 0 <= int(want) < 1 << 32:
-            raise ValueError("want must lie in [0, 2^32)")
-        w = np.full(nq, int(want), np.uint32)
-    else:
-        if not per_query:
-            raise ValueError("want: semantics='reference' takes one want word for the whole batch (an int): "
-                             "its round merge couples the queries of a batch")
-        w = want.cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want)
-        if w.dtype.kind not in "iu" or w.shape != (nq,):
-            raise ValueError(f"want must be an integer or an integer array of shape [{nq}]")
-        if w.size and (int(w.min()) < 0 or int(w.max()) >= 1 << 32):
-            raise ValueError("want must lie in [0, 2^32)")
-        w = w.astype(np.uint32)
-    return _as_i32_bits(w).to(index.device)
+        raise ValueError(f"{name}: filtered search takes lists of at most {_lib.LMI_MAX_K} entries, not {k_list}")
+    if isinstance(word, (int, np.integer)) and not isinstance(word, bool):
+        if not 0 <= int(word) < 1 << 32:
+            raise ValueError(f"{name} must lie in [0, 2^32)")
+        return np.full(nq, int(word), np.uint32)
+    if not per_query:
+        raise ValueError(f"{name}: semantics='reference' takes one {name} word for the whole batch (an int): "
+                         "its round merge couples the queries of a batch")
+    w = word.cpu().numpy() if isinstance(word, torch.Tensor) else np.asarray(word)
+    if w.dtype.kind not in "iu" or w.shape != (nq,):
+        raise ValueError(f"{name} must be an integer or an integer array of shape [{nq}]")
+    if w.size and (int(w.min()) < 0 or int(w.max()) >= 1 << 32):
+        raise ValueError(f"{name} must lie in [0, 2^32)")
+    return w.astype(np.uint32)
 
 
-def _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phases):
+def _tag_word(word, name: str) -> int:
+    if not isinstance(word, (int, np.integer)) or isinstance(word, bool) or not 0 <= int(word) < 1 << 32:
+        raise ValueError(f"{name} must be an integer in [0, 2^32)")
+    return int(word)
+
+
+def value_mask(want, avoid):
+    """(value, mask) of the scan's one test (tag & mask) == value from the
+    all-of word(s) `want` and the none-of word(s) `avoid` (ints or uint32
+    arrays of one shape): value = want, mask = want | avoid.  ValueError where
+    a word wants and avoids the same bit: the test would read it as wanted."""
+    w, a = np.asarray(want, dtype=np.uint32), np.asarray(avoid, dtype=np.uint32)
+    both = w & a
+    if both.any():
+        i = int(np.flatnonzero(both.ravel())[0])
+        raise ValueError(f"want and avoid share bits (0x{int(both.ravel()[i]):x}"
+                         + (f" at query {i}" if both.ndim else "") + "): a bit cannot be both wanted and avoided")
+    return w, w | a
+
+
+def mask_words(index: DeviceIndex, want, avoid, nq: int, k_list: int, dist: str = "f32",
+               per_query: bool = True) -> torch.Tensor:
+    """The words of a filtered scan with `want` and / or `avoid` (each None, an
+    int or, per_query, an integer array [nq]; None: 0) as one device int32
+    [2, nq] tensor -- row 0 the value words (want), row 1 the mask words
+    (want | avoid) -- after every check of want_words on each of the two and
+    value_mask's: all on the host, before anything is launched or allocated.
+    bucket_topk / bucket_range take it as their `want`."""
+    value, mask = value_mask(*(_host_words(index, 0 if word is None else word, nq, k_list, dist, per_query, name)
+                               for name, word in (("want", want), ("avoid", avoid))))
+    return _as_i32_bits(np.stack([value, mask])).to(index.device)
+
+
+def filter_words(index: DeviceIndex, want, avoid, nq: int, k_list: int, dist: str = "f32",
+                 per_query: bool = True):
+    """What Searcher's calls hand their scans as `want` for the keywords `want`
+    and `avoid`: None (neither given), want_words (want alone: the call as it
+    was before `avoid`) or mask_words."""
+    if avoid is None:
+        return None if want is None else want_words(index, want, nq, k_list, dist, per_query)
+    return mask_words(index, want, avoid, nq, k_list, dist, per_query)
+
+
+def _tag_words(want, avoid, nq, device):
+    """bucket_topk's / bucket_range's (value, mask) device tensors from their
+    `want` ([nq], or mask_words' [2, nq]) and `avoid` ([nq] or None)."""
+    def ok(t, shape):
+        return (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape
+                and t.device == device and t.is_contiguous())
+    if want is not None and ok(want, (2, nq)):
+        if avoid is not None:
+            raise ValueError("avoid: the [2, nq] words of mask_words hold the avoided bits already")
+        return want[0], want[1]
+    if want is not None and not ok(want, (nq,)):
+        raise ValueError("want must be a device int32 tensor [nq] (want_words) or [2, nq] (mask_words)")
+    if avoid is None:
+        return want, want
+    if not ok(avoid, (nq,)):
+        raise ValueError("avoid must be a device int32 tensor [nq] (want_words)")
+    if want is None:
+        return torch.zeros_like(avoid), avoid
+    return want, torch.bitwise_or(want, avoid)
+
+
+def _bucket_topk_tagged(index, q, classes, k, qmode, want, avoid, stream, out, ws, phases):
     """bucket_topk's tagged call (q, classes already on the device)."""
     lib = _lib.load()
     nq, R = classes.shape
     if index.tags is None:
-        raise ValueError("want: this index is untagged (build it with `tags`)")
+        raise ValueError("want / avoid: this index is untagged (build it with `tags`)")
     if phases:
-        raise ValueError("want: the tagged scan runs whole (no phases)")
-    if not (isinstance(want, torch.Tensor) and want.dtype == torch.int32 and want.shape == (nq,)
-            and want.device == q.device and want.is_contiguous()):
-        raise ValueError("want must be a device int32 tensor [nq] (want_words)")
+        raise ValueError("want / avoid: the tagged scan runs whole (no phases)")
+    value, mask = _tag_words(want, avoid, nq, q.device)
     desc = index.desc_for(k)
     need = lib.lmi_scan_tagged_workspace_bytes(C.byref(desc), nq, R, k, qmode)
     if need == 0 and nq:
@@ -1012,9 +1109,9 @@ def _bucket_topk_tagged(index, q, classes, k, qmode, want, stream, out, ws, phas
     else:
         _workspace(ws, need, "tagged scan")
     s = stream if stream is not None else _lib.stream_handle(index.device)
-    check("lmi_bucket_topk_tagged", lib.lmi_bucket_topk_tagged(
-        C.byref(desc), ptr(index.tags), ptr(want), ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode,
-        ptr(out_d), ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
+    check("lmi_bucket_topk_masked", lib.lmi_bucket_topk_masked(
+        C.byref(desc), ptr(index.tags), ptr(value), ptr(mask), None, None, ptr(q), nq, q.stride(0), ptr(classes),
+        R, k, qmode, ptr(out_d), ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
     return out_d, out_pos, status
 
 
@@ -1044,8 +1141,8 @@ def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
 
 
 def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, radius, *,
-                 qmode: Optional[int] = None, pair_cap: int = 256, want=None, stream=None, ws=None,
-                 f64: bool = False):
+                 qmode: Optional[int] = None, pair_cap: int = 256, want=None, avoid=None, stream=None,
+                 ws=None, f64: bool = False):
     """K11's collect scan on one shard (lmi_bucket_range): per (query, probe)
     pair every row of the probed bucket with d <= radius[q], d the float32
     distance of the top-k lists of the same kernel family (inclusive).  Returns
@@ -1055,23 +1152,23 @@ def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, rad
     (distance ordinal << 32 | shard-local row).  `radius`: a number or float32
     values [nq] (the scan's bound as it stands).  `want` (a tagged index; a
     device int32 [nq] tensor of want words, see want_words): only rows with
-    (tag & want) == want.  `f64`: scan with the float64 mode's descriptor
+    (tag & want) == want; `avoid` (the same form): and (tag & avoid) == 0, as
+    bucket_topk takes the two.  `f64`: scan with the float64 mode's descriptor
     (desc_for(k, f64=True): low-norm rows with their true norm).  A bucket that
     a query's classes row names twice is collected twice.  `ws` as bucket_topk."""
     lib = _lib.load()
     check_range_index(index)
     if not 1 <= int(pair_cap) <= 1 << 24:
         raise ValueError("pair_cap must lie in [1, 2^24]")
-    if want is not None and index.tags is None:
-        raise ValueError("want: this index is untagged (build it with `tags`)")
+    tagged = want is not None or avoid is not None
+    if tagged and index.tags is None:
+        raise ValueError("want / avoid: this index is untagged (build it with `tags`)")
     q = _rows_f32(q, index.device)
     classes = _as_torch(classes, index.device, torch.int32)
     nq, R = classes.shape
     if q.shape[0] != nq or q.shape[1] != index.d:
         raise ValueError("query shape does not match the index")
-    if want is not None and not (isinstance(want, torch.Tensor) and want.dtype == torch.int32
-                                 and want.shape == (nq,) and want.device == q.device and want.is_contiguous()):
-        raise ValueError("want must be a device int32 tensor [nq] (want_words)")
+    value, mask = _tag_words(want, avoid, nq, q.device) if tagged else (None, None)
     if isinstance(radius, torch.Tensor):
         bound = radius.to(device=index.device, dtype=torch.float32).contiguous()
     else:
@@ -1082,7 +1179,7 @@ def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, rad
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     desc = index.desc_for(1, f64=f64)
-    need = lib.lmi_range_workspace_bytes(C.byref(desc), nq, R, qmode, int(want is not None), int(pair_cap))
+    need = lib.lmi_range_workspace_bytes(C.byref(desc), nq, R, qmode, int(tagged), int(pair_cap))
     if need == 0:
         raise ValueError("range search: this index or call takes no range scan")
     if ws is None:
@@ -1095,10 +1192,10 @@ def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, rad
     cand = torch.empty((nq, R, int(pair_cap)), dtype=torch.int64, device=index.device)
     status = torch.zeros((1,), dtype=torch.int32, device=index.device)
     s = stream if stream is not None else _lib.stream_handle(index.device)
-    check("lmi_bucket_range", lib.lmi_bucket_range(
-        C.byref(desc), ptr(index.tags) if want is not None else None, ptr(want), ptr(q), nq, q.stride(0),
-        ptr(classes), R, qmode, ptr(bound), int(pair_cap), ptr(cand), ptr(count), ptr(status), ptr(ws),
-        ws.numel(), s))
+    check("lmi_bucket_range_masked", lib.lmi_bucket_range_masked(
+        C.byref(desc), ptr(index.tags) if tagged else None, ptr(value), ptr(mask), None, None, ptr(q), nq,
+        q.stride(0), ptr(classes), R, qmode, ptr(bound), int(pair_cap), ptr(cand), ptr(count), ptr(status),
+        ptr(ws), ws.numel(), s))
     return count, cand, status
 
 
@@ -1476,18 +1573,21 @@ class Searcher:
 
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
-              min_probes: int = 1, want=None):
+              min_probes: int = 1, want=None, avoid=None):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
         `stop_mass`, `min_probes`: the router's stop rule (DeviceRouter.topr);
         a dropped probe's list is (+inf, -1).  `want` (a tagged index; an int
         or an integer array [nq], words in [0, 2^32)): filtered lists -- each
         the exact top-k_list of the bucket's rows with (tag & want) == want,
-        padded (+inf, -1); the lists of an index built from those rows alone."""
+        padded (+inf, -1); the lists of an index built from those rows alone.
+        `avoid` (the same forms; alone it means want = 0): and only rows with
+        (tag & avoid) == 0.  A query that wants and avoids one bit is a
+        ValueError, like every refusal of `want`, before anything is launched."""
         check_stop(stop_mass, min_probes)
         self.index._check_live()
-        if want is not None:
+        if want is not None or avoid is not None:
             nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-            want = want_words(self.index, want, nq, k_list, dist)
+            want = filter_words(self.index, want, avoid, nq, k_list, dist)
         if classes is None:
             classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
@@ -1509,15 +1609,19 @@ class Searcher:
             return self.router.topr(q_nav, R)[0]
         return self.router.topr(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)[0]
 
-    def eligible_bucket_size(self, want: int) -> np.ndarray:
-        """The eligible rows of every bucket of the whole index under the want
-        word `want` (eligible_counts, cached per word): the reference replay's
+    def eligible_bucket_size(self, want: int, avoid: int = 0) -> np.ndarray:
+        """The eligible rows of every bucket of the whole index under the words
+        `want` and `avoid` (eligible_counts, cached per pair until the index's
+        tags are edited: DeviceIndex.tags_version): the reference replay's
         bucket_size of a filtered search."""
-        cache = self.__dict__.setdefault("_eligible", {})
-        w = int(want)
-        if w not in cache:
-            cache[w] = eligible_counts(self.index.tags_by_pos, self.index.layout.bucket_off, w)
-        return cache[w]
+        version = self.index.tags_version
+        if self.__dict__.get("_eligible_version") != version:
+            self._eligible, self._eligible_version = {}, version
+        key = (int(want), int(avoid))
+        if key not in self._eligible:
+            self._eligible[key] = eligible_counts(self.index.tags_by_pos, self.index.layout.bucket_off,
+                                                  key[0], key[1])
+        return self._eligible[key]
 
     def _device_tables(self):
         """bucket sizes and position -> id map in HBM for the device replay."""
@@ -1530,7 +1634,7 @@ class Searcher:
         return t
 
     def range_search(self, q_nav, q_search, R: int, radius, *, classes: Optional[torch.Tensor] = None,
-                     dist: str = "f32", stop_mass=None, min_probes: int = 1, want=None,
+                     dist: str = "f32", stop_mass=None, min_probes: int = 1, want=None, avoid=None,
                      pair_cap: int = 256, timings: Optional[dict] = None):
         """Every object of each query's probed buckets within `radius` of it
         (K11) -> host arrays (lims int64 [nq + 1], dists float64 [total], anns
@@ -1548,7 +1652,8 @@ class Searcher:
         radius float64; the scan collects under float32(radius + 2 eps), eps =
         refine_eps, and the candidates are re-scored in float64.  `want` (a
         tagged index; an int or one word per query): only objects with
-        (tag & want) == want answer.
+        (tag & want) == want answer; `avoid` (the same forms; alone it means
+        want = 0): and only objects with (tag & avoid) == 0.
 
         `pair_cap`: candidate slots per (query, probe) of the first scan.  The
         counts are exact whatever it is; if a pair's count exceeds it, one more
@@ -1570,7 +1675,8 @@ class Searcher:
         ValueError before anything is launched on: a radius that is NaN or
         not [nq]; storage "f32x"; an index with float64 rows; float64 queries
         that float32 rounding changes; a sub-cluster layout; a striped index
-        or a Searcher with an exchange group; `want` on an untagged index; in
+        or a Searcher with an exchange group; `want` or `avoid` on an untagged
+        index, or sharing a bit; in
         float64 d > 1024; in either arithmetic d_pad > 1248 (the collect
         scan's query tile would not fit a workgroup's LDS)."""
         import time
@@ -1591,9 +1697,7 @@ class Searcher:
             r64 = np.full(nq, float(r64))
         if r64.shape != (nq,) or np.isnan(r64).any():
             raise ValueError(f"radius must be a number or [{nq}] values, none NaN")
-        want_w = None
-        if want is not None:
-            want_w = want_words(ix, want, nq, 1, "f32")
+        want_w = filter_words(ix, want, avoid, nq, 1, "f32")
         dev = ix.device
         q64 = (isinstance(q_search, torch.Tensor) and q_search.dtype == torch.float64) or \
             (isinstance(q_search, np.ndarray) and q_search.dtype == np.float64)
@@ -1731,7 +1835,7 @@ class Searcher:
                use_threshold: bool = True, classes: Optional[torch.Tensor] = None,
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
-               min_probes: int = 1, want=None):
+               min_probes: int = 1, want=None, avoid=None):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
 
         `want` (a tagged index): filtered search -- only rows with
@@ -1740,9 +1844,12 @@ class Searcher:
         int for the whole batch (its round merge couples the batch's queries)
         and answers as search() on the index built from the eligible rows
         alone: the replay reads every bucket's eligible row count as its size.
-        The filtered scan is never seeded.  ValueError before anything is
-        launched on an untagged index, with dist="f64", storage "f32x", lists
-        of more than 16 entries or a malformed `want`.
+        The filtered scan is never seeded.  `avoid` (the same forms as `want`;
+        alone it means want = 0): and only rows with (tag & avoid) == 0 answer
+        -- "not deleted", "not flagged" (DeviceIndex.edit_tags sets such bits
+        in place).  ValueError before anything is launched on an untagged
+        index, with dist="f64", storage "f32x", lists of more than 16 entries,
+        a malformed `want` or `avoid`, or a query that wants and avoids one bit.
 
         `stop_mass` (None: off): adaptive probing -- R is the cap, and each
         query stops at the first probe before which the router's probability
@@ -1789,9 +1896,9 @@ class Searcher:
             replay_on = "host"  # the device replay holds rows of <= 32 / 64 entries
         dev = self.index.device
         want_w = None
-        if want is not None:
+        if want is not None or avoid is not None:
             nq_w = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-            want_w = want_words(self.index, want, nq_w, k_list, dist, per_query=semantics == "exact")
+            want_w = filter_words(self.index, want, avoid, nq_w, k_list, dist, per_query=semantics == "exact")
         sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
 
         def lap(name, t0):
@@ -1835,7 +1942,7 @@ class Searcher:
         # (filtered: the replay's bucket sizes are the eligible row counts)
         bsize = self.index.bucket_size
         if want_w is not None and semantics == "reference":
-            bsize = self.eligible_bucket_size(int(want))
+            bsize = self.eligible_bucket_size(int(want or 0), int(avoid or 0))
         t0 = tl[0]
         h_st = self._host("st", (2,), torch.int32)
 

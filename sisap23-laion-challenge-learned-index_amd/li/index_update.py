@@ -196,6 +196,69 @@ def _update_inplace(index, new, rows, drop, tables, d_dst, status, slab_rows, di
                         staged_rows=int((staged[:, 1] - staged[:, 0]).sum()), staging_rows=stage_rows))
 
 
+class UnknownIds(KeyError, ValueError):
+    """edit_tags' report of ids the index does not hold: remove's KeyError, and a ValueError like
+    the call's other refusals."""
+
+
+def _edit_words(words, n: int, name: str) -> np.ndarray:
+    """`words` (an int or [n] integers in [0, 2^32)) as uint32 [n]; ValueError otherwise."""
+    w = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+    if w.dtype.kind not in "iu" or isinstance(words, bool) or w.shape not in ((), (n,)):
+        raise ValueError(f"{name} must be an integer or [{n}] integers, one per id")
+    if w.size and (int(w.min()) < 0 or int(w.max()) >= 1 << 32):
+        raise ValueError(f"{name} must lie in [0, 2^32)")
+    return np.array(np.broadcast_to(w.astype(np.uint32), (n,)))   # (a copy: broadcast views are read-only)
+
+
+@torch.no_grad()
+def edit_tags(index, ids, set_bits, clear_bits) -> None:
+    """DeviceIndex.edit_tags: the host table and the device words of `index` itself, one launch of
+    lmi_index_edit_tags in stream order; every refusal before it."""
+    index._check_live()
+    if index.tags_by_pos is None:
+        raise ValueError("edit_tags: this index is untagged (build it with `tags`)")
+    if index.world > 1:
+        raise ValueError("edit_tags: a striped index (world > 1) takes no tag edits: every rank holds the "
+                         "whole host table and its own rows' words")
+    ids = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids)
+    if ids.size and ids.dtype.kind not in "iu":
+        raise ValueError("edit_tags: ids must be integers")
+    ids = ids.astype(np.int64, copy=False).ravel()
+    n = int(ids.size)
+    st, cl = _edit_words(set_bits, n, "set_bits"), _edit_words(clear_bits, n, "clear_bits")
+    uniq = np.unique(ids)
+    if uniq.size != n:
+        raise ValueError("edit_tags: duplicate ids")
+    # positions of the ids (one row each: ids are unique in an index), in the caller's order: a sorted
+    # search of pos_to_id, whose order is worked out on the first edit of an index and kept (the table
+    # never changes in an index's life; a repeated edit, as deletes by tombstone are, then costs log n an id)
+    by_id = index.__dict__.get("_by_id")
+    if by_id is None:
+        by_id = index._by_id = np.argsort(index.pos_to_id, kind="stable")
+    at = np.searchsorted(index.pos_to_id, ids, sorter=by_id)
+    pos = by_id[np.minimum(at, by_id.size - 1)] if by_id.size else np.zeros(n, np.int64)
+    found = (index.pos_to_id[pos] == ids) if by_id.size else np.zeros(n, bool)
+    if not found.all():
+        missing = np.unique(ids[~found])
+        raise UnknownIds(f"ids not in the index: {missing[:8].tolist()}" + (" ..." if missing.size > 8 else ""))
+    if n == 0:
+        return
+    dev = index.device
+    # (world == 1: a row's position is its row of the device arrays, gpos = 0 .. n_rows - 1)
+    d_rows = torch.from_numpy(pos.astype(np.int64)).to(dev)
+    d_clear, d_set = (torch.from_numpy(w.view(np.int32)).to(dev) for w in (cl, st))
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    check("lmi_index_edit_tags", _lib.load().lmi_index_edit_tags(
+        ptr(index.tags), index.n_rows, ptr(d_rows), ptr(d_clear), ptr(d_set), n, ptr(status),
+        _lib.stream_handle(dev)))
+    index.tags_by_pos = index.tags_by_pos.copy()   # (a successor or a caller may share the old table)
+    index.tags_by_pos[pos] = (index.tags_by_pos[pos] & ~cl) | st
+    index.tags_version += 1
+    if int(status.item()):   # (waits for the kernel: its inputs stay alive until here)
+        raise RuntimeError(f"edit_tags: internal status {int(status.item())}")
+
+
 def sorted_by_bucket(lab: torch.Tensor, n_buckets: int):
     """(order, bucket_off) of the device labels `lab` (int32 / int64), both
     int64 on the device: BucketLayout.from_labels' tables.  Up to

@@ -260,15 +260,15 @@ def check_tags(tags, n: int) -> np.ndarray:
     return np.ascontiguousarray(t.astype(np.uint32))
 
 
-def eligible_counts(tags_by_pos, bucket_off, want: int) -> np.ndarray:
-    """int64 [C]: the rows of every bucket with (tag & want) == want -- a
-    segmented count over `bucket_off` ([C+1] positions into `tags_by_pos`),
+def eligible_counts(tags_by_pos, bucket_off, want: int, avoid: int = 0) -> np.ndarray:
+    """int64 [C]: the rows of every bucket with (tag & want) == want and
+    (tag & avoid) == 0 -- a segmented count over `bucket_off` ([C+1] positions into `tags_by_pos`),
     done in torch (imported on the call).  The reference replay of a filtered
     search reads these as its bucket sizes (the < k quirk, the empty-bucket skip)."""
     import torch
-    w = int(want)
+    w, m = int(want), int(want) | int(avoid)
     t = torch.from_numpy(np.ascontiguousarray(tags_by_pos, dtype=np.uint32).astype(np.int64))
-    ok = (t & w) == w
+    ok = (t & m) == w
     cs = torch.zeros(t.numel() + 1, dtype=torch.int64)
     torch.cumsum(ok, 0, out=cs[1:])
     off = torch.from_numpy(np.ascontiguousarray(bucket_off, dtype=np.int64))

@@ -16,7 +16,16 @@ process, after a warm-up of each, --reps rounds alternate
   (d) twice only (it takes seconds): DeviceIndex(host rows, host labels), the
       only way to this index without updates
 
-and profiles/index_update_<tag>.json receives every time with its spread
+With --tag-edits the index is tagged and the rounds alternate instead
+
+  (e) index.edit_tags of --batch ids (one bit set: a tombstone): a host clock
+      from the call to its return, and lmi_index_edit_tags alone by device
+      events on prepared tables
+  (f) index.remove of the same ids, the host clock of (b): what hiding those
+      objects from the next query costs without tag edits
+
+and profiles/index_tag_edit_<tag>.json receives them.  Without it,
+profiles/index_update_<tag>.json receives every time with its spread
 (max - min), the byte model 2 n (2 d_pad + 4) + batch bytes, the move kernel's
 bytes/s, that rate over (c)'s and over profiles/r05l_hbm_peak.txt's copy
 rate, the host-table share of (a), and (d) over (a)."""
@@ -92,6 +101,53 @@ def kernels(index, drop, rows, labels):
     return move, ingest, host_ms
 
 
+def tag_edits(a):
+    """(e), (f): edit_tags against remove on one tagged index."""
+    n, d, m, C = a.n, a.d, a.batch, a.buckets
+    x, _ = synth.torch_mixture(n, d, 400, a.seed, DEV)
+    g = torch.Generator(device=DEV)
+    g.manual_seed(a.seed + 1)
+    labels = torch.randint(0, C, (n,), generator=g, device=DEV)
+    tags = torch.randint(0, 64, (n,), generator=g, device=DEV).cpu().numpy().astype(np.uint32)
+    index = DeviceIndex.empty(d, C, device=DEV, tags=True).add(x, labels, tags=tags)
+    del x
+    rng = np.random.Generator(np.random.PCG64(a.seed))
+    ids = rng.choice(n, m, replace=False).astype(np.int64) + 1           # ids 1..n
+    rows = torch.from_numpy(np.flatnonzero(np.isin(index.pos_to_id, ids)).astype(np.int64)).to(DEV)
+    bit = torch.full((m,), 1 << 29, dtype=torch.int32, device=DEV)
+    zero = torch.zeros((m,), dtype=torch.int32, device=DEV)
+    status = torch.zeros((1,), dtype=torch.int32, device=DEV)
+    lib, s = _lib.load(), _lib.stream_handle(DEV)
+    t = {k: [] for k in ("edit_tags_ms", "edit_kernel_ms", "remove_ms")}
+    for rep in range(-1, a.reps):                    # round -1: the warm-up
+        got = {}
+        _, got["edit_tags_ms"] = wall(lambda: index.edit_tags(ids, set_bits=1 << 29))
+        got["edit_kernel_ms"] = events(lambda: _lib.check("lmi_index_edit_tags", lib.lmi_index_edit_tags(
+            index.tags.data_ptr(), index.n_rows, rows.data_ptr(), bit.data_ptr(), zero.data_ptr(), m,
+            status.data_ptr(), s)))                  # (clears the bit again)
+        _, got["remove_ms"] = wall(lambda: index.remove(ids))
+        if rep >= 0:
+            for k, v in got.items():
+                t[k].append(v)
+    assert int(status.item()) == 0
+    index.edit_tags(ids, set_bits=1 << 29)
+    marked = bool(np.array_equal(np.sort(index.ids_with(want=1 << 29)), np.sort(ids))
+                  and int((index.tags & (1 << 29) != 0).sum().item()) == m)
+    out = {"device": torch.cuda.get_device_name(0), "n": n, "d": d, "buckets": C, "batch": m, "reps": a.reps,
+           "timing": "edit_tags_ms, remove_ms: host clock from the call to its return, the device idle before "
+                     "and after; edit_kernel_ms: device events around lmi_index_edit_tags on prepared tables",
+           "marked_ids_equal_ids_with": marked}
+    for k, v in t.items():
+        out[k] = stats(v)
+    out["remove_over_edit_tags"] = out["remove_ms"]["median_ms"] / out["edit_tags_ms"]["median_ms"]
+    path = a.out or os.path.join(ROOT, "profiles", f"index_tag_edit_{a.tag or n}.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: out[k]["median_ms"] for k in t} | {"remove_over_edit_tags": out["remove_over_edit_tags"],
+                                                             "marked": marked, "out": path}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--n", type=int, default=10_000_000)
@@ -103,9 +159,12 @@ def main():
     ap.add_argument("--tag", default=None)
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tag-edits", action="store_true", help="(e), (f): edit_tags against remove")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("index_update_bench needs a HIP device (no CPU path)")
+    if a.tag_edits:
+        return tag_edits(a)
     n, d, m, C = a.n, a.d, a.batch, a.buckets
     x, _ = synth.torch_mixture(n + m, d, 400, a.seed, DEV)
     g = torch.Generator(device=DEV)

@@ -10,27 +10,38 @@ after a warm-up of each side, --launches timed launches per side by device
 events, the two sides of every comparison alternated launch by launch:
 
   (a) the cost of the predicate: the tagged scan with want = 0 against the
-      untagged scan of the same index (selectivity 1)
+      untagged scan of the same index (selectivity 1), and the same call with
+      avoid = a bit no row carries (the second word of the predicate)
   (b) per want word keeping ~1/2, ~1/8, ~1/64 of the rows: the tagged scan
       against the untagged scan of the index built from the eligible rows
       alone (the per-predicate index a caller would otherwise hold)
   (c) at the same points, recall@10 of "unfiltered k = 10, then post-filter"
       against the tagged lists, computed from the lists
 
-and the JSON receives every mean with its spread (max - min) and all values."""
+and the JSON receives every mean with its spread (max - min) and all values.
+--no-selectivity stops after (a).  --pkg DIR imports the `li` package from DIR
+(another checkout's, for a run against the parent commit: alternate whole
+processes of the two trees and compare their medians of (a))."""
 import argparse
 import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "sisap23-laion-challenge-learned-index_amd"))
+PKG = os.path.join(ROOT, "sisap23-laion-challenge-learned-index_amd")
+if "--pkg" in sys.argv[1:-1]:
+    PKG = os.path.abspath(sys.argv[sys.argv.index("--pkg") + 1])
+sys.path.insert(0, PKG)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from li import synth  # noqa: E402
 from li.index import DeviceIndex, bucket_topk, want_words  # noqa: E402
+try:
+    from li.index import mask_words  # noqa: E402
+except ImportError:      # (--pkg: a tree from before `avoid`)
+    mask_words = None
 
 DEV = "cuda:0"
 
@@ -69,6 +80,8 @@ def main():
     ap.add_argument("--tag", default="10M")
     ap.add_argument("--seed", type=int, default=2023)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--no-selectivity", action="store_true", help="(a) only")
+    ap.add_argument("--pkg", default=None, help="directory that holds the `li` package to measure")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tagged_scan_bench needs a HIP device (no CPU path)")
@@ -84,15 +97,28 @@ def main():
     lab_host = labels.cpu().numpy()
     full = DeviceIndex.empty(d, C, device=DEV, tags=True).add(x, labels, tags=tags)
 
-    def scan(index, want=None):
-        ww = None if want is None else want_words(index, want, nq, k)
+    def scan(index, want=None, avoid=None):
+        if avoid is not None:
+            ww = mask_words(index, want, avoid, nq, k)
+        else:
+            ww = None if want is None else want_words(index, want, nq, k)
         return lambda: bucket_topk(index, q, classes, k, want=ww)
 
-    res = {"n": n, "d": d, "nq": nq, "R": R, "k": k, "buckets": C, "launches": a.launches,
+    res = {"package": os.path.relpath(PKG, ROOT), "n": n, "d": d, "nq": nq, "R": R, "k": k, "buckets": C, "launches": a.launches,
            "warmup": a.warmup, "timing": "device events around each lmi_bucket_topk[_tagged] call, "
            "the two sides of a comparison alternated launch by launch in one process"}
-    t = alternate({"untagged": scan(full), "tagged_want0": scan(full, 0)}, a.launches, a.warmup)
+    sides = {"untagged": scan(full), "tagged_want0": scan(full, 0)}
+    if mask_words is not None:   # (tags are 6 bits wide: no row has bit 20)
+        sides["tagged_want0_avoid_unused_bit"] = scan(full, 0, 1 << 20)
+    t = alternate(sides, a.launches, a.warmup)
     res["predicate_cost"] = {name: stats(v) for name, v in t.items()}
+    if a.no_selectivity:
+        out = a.out or os.path.join(ROOT, "profiles", f"tagged_scan_{a.tag}.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"package": os.path.relpath(PKG, ROOT)} | {name: s["median_ms"] for name, s in res["predicate_cost"].items()}))
+        return
     plain_d, plain_pos, _ = bucket_topk(full, q, classes, k)
     plain_pos = plain_pos.clone()
     res["selectivity"] = []
