@@ -48,12 +48,23 @@ extern "C" {
 /* ---- element types / modes ------------------------------------------ */
 #define LMI_F32 0
 #define LMI_F16 1
+/* 8-bit storage (an addition: LMI_ABI_VERSION does not change): corpus is
+ * [n_rows][d_pad] int8 codes and inv_norm the codes' own 1/sqrt(sum c^2)
+ * (lmi_quantize_rows_i8 writes both).  Lossy: the lists are the exact top-k of
+ * the quantised distances.  Only lmi_bucket_topk and lmi_bucket_topk_masked /
+ * _tagged take it, with qmode LMI_Q_I8, 1 <= k <= LMI_MAX_K and d_pad <= 992. */
+#define LMI_I8 2
 
 #define LMI_ROUTER_TOPR 0   /* softmax + classes sorted by probability (predict_proba) */
 #define LMI_ROUTER_ARGMAX 1 /* argmax of logits (predict)                               */
 
 #define LMI_Q_F16 0 /* queries are fp16-representable: exact fp16 MFMA path        */
 #define LMI_Q_F32 1 /* general queries: exact-fp32 MFMA path (16x the MFMA time)   */
+/* The queries of an LMI_I8 index: quantised inside the call by the rule of
+ * lmi_quantize_rows_i8, int8 x int8 products summed exactly in int32
+ * (v_mfma_i32_32x32x32_i8).  LMI_I8 and LMI_Q_I8 come together: one without the
+ * other is LMI_E_INVALID. */
+#define LMI_Q_I8 2
 /* ABI 6, a flag OR-ed into qmode (lmi_bucket_topk / lmi_bucket_topk_f64*, k <=
  * LMI_MAX_K): the lists of probes r >= 1 are needed only below the pair's
  * round-0 k-th distance -- the reference's thresholded rounds compare every
@@ -733,6 +744,26 @@ int lmi_index_move_rows(const void* src_corpus, const float* src_inv_norm, int64
 int lmi_index_ingest_rows(const void* rows, int32_t dtype, int64_t m, int64_t ld, int32_t d,
                           int32_t d_pad, const int64_t* new_dst, void* dst_corpus,
                           float* dst_inv_norm, int64_t n_new, int32_t* status, void* stream);
+
+/* ---- 8-bit storage: the quantiser (an addition: LMI_ABI_VERSION stays) ------- */
+/* Row i of `rows` (device, `dtype` LMI_F16 or LMI_F32, m rows of d values, row
+ * stride ld elements) becomes the int8 codes of slot dst_rows[i] (device int64
+ * [m]; NULL: slot i) of `codes` ([slots][d_pad] int8), and inv_norm[slot] the
+ * codes' 1/||c||.  With v the row's values as float32 (fp16 converts exactly):
+ *   m = max_j |v_j|; if !(m >= 2^-100) (a zero, tiny or NaN row) every code is 0;
+ *   else s = m / 127.0f and c_j = clamp(rintf(v_j / s), -127, 127) -- both
+ *   divisions IEEE float32, rintf round-half-to-even, nothing contracted;
+ *   columns d..d_pad are 0; ss = sum c_j^2 (an exact integer);
+ *   inv_norm = ss == 0 ? 1.0f : (float)(1.0 / sqrt((double)ss)).
+ * The scale s is not stored (the cosine does not need it).  All d_pad columns
+ * of every slot touched are written; slots are the caller's to keep in range.
+ * lmi_bucket_topk quantises its queries by the same device function.
+ * LMI_E_INVALID before any launch: a dtype other than LMI_F16 / LMI_F32, m < 0,
+ * d < 1, d_pad not d rounded up to a multiple of 32, ld < d, a null pointer
+ * (m > 0), codes not 4-byte aligned. */
+int lmi_quantize_rows_i8(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, int64_t m, int64_t ld,
+                         int32_t d, int32_t d_pad, const int64_t* dst_rows /*nullable*/,
+                         int8_t* codes, float* inv_norm, void* stream);
 
 /* ---- index update in place (K9): add / remove inside one buffer ------------- */
 /* lmi_index_move_rows with source and destination in the SAME store of

@@ -358,6 +358,7 @@ __global__ __launch_bounds__(256) void range_pack_kernel(const uint64_t* __restr
 int range_check(const lmi_index_desc* idx, bool tags, bool want, int32_t nq, int32_t R, int32_t qmode,
                 int32_t pair_cap) {
     LMI_CHECK_ARG(idx != nullptr, "lmi_bucket_range: null index");
+    LMI_TRY(i8_refuse("lmi_bucket_range", idx));
     LMI_CHECK_ARG(tags == want, "lmi_bucket_range: tags and want come together");
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
                   "lmi_bucket_range: the split mode (corpus32 / corpus64) takes no range search");
@@ -504,6 +505,7 @@ extern "C" int lmi_range_pack(const lmi_index_desc* idx, int32_t nq, int32_t R, 
                               int32_t* out_q, void* stream) {
     using namespace lmi;
     LMI_CHECK_ARG(idx != nullptr, "lmi_range_pack: null index");
+    LMI_TRY(i8_refuse("lmi_range_pack", idx));
     LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "lmi_range_pack: bad nq/R");
     LMI_CHECK_ARG(pair_cap >= 1, "lmi_range_pack: pair_cap=%d < 1", pair_cap);
     LMI_CHECK_ARG((d64 != nullptr) == (radius64 != nullptr), "lmi_range_pack: d64 and radius64 come together");

@@ -735,6 +735,7 @@ extern "C" int lmi_range_rescore_f64(const lmi_index_desc* idx, const float* q, 
                                      const uint32_t* count, double* d64, uint32_t* kept, void* stream) {
     using namespace lmi;
     LMI_CHECK_ARG(idx != nullptr, "lmi_range_rescore_f64: null index");
+    LMI_TRY(i8_refuse("lmi_range_rescore_f64", idx));
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
                   "lmi_range_rescore_f64: the split mode (corpus32 / corpus64) takes no range search");
     LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32, "lmi_range_rescore_f64: bad corpus dtype");
@@ -1817,6 +1818,7 @@ extern "C" size_t lmi_scan_f64_workspace_bytes(const lmi_index_desc* idx, int32_
     qmode &= ~LMI_Q_SEED_ROUND0;
     lmi::take_phases(qmode);
     if (!idx || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K_F64) return 0;
+    if (lmi::i8_refuse("lmi_scan_f64_workspace_bytes", idx) != LMI_OK) return 0;
     if (idx->corpus32) return k <= LMI_MAX_K ? lmi::x_ws_bytes(idx, nq, R, k) : 0;
     return lmi::refine_ws(idx, nq, R, k, qmode).total;
 }
@@ -1908,6 +1910,7 @@ int bucket_topk_f64_impl(const lmi_index_desc* idx, const float* q, int32_t nq, 
         do_refine = (phases & kPhaseMerge) != 0;
     }
     LMI_CHECK_ARG(idx != nullptr, "null index");
+    LMI_TRY(i8_refuse(global ? "lmi_bucket_topk_f64g" : "lmi_bucket_topk_f64", idx));
     LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K_F64, "k=%d outside [1, %d]", k, LMI_MAX_K_F64);
     LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "bad nq/R");
     LMI_CHECK_ARG(idx->d >= 1 && idx->d <= 4 * 256, "d=%d outside [1, 1024] for float64 refinement",
@@ -2045,6 +2048,7 @@ extern "C" int lmi_f64_global_band(const lmi_index_desc* idx, int32_t nq, int32_
     using namespace lmi;
     qmode &= ~(LMI_Q_SEED_ROUND0 | LMI_Q_PHASE_REFINE);
     take_phases(qmode);
+    if (i8_refuse("lmi_f64_global_band", idx) != LMI_OK) return 0;  // (a predicate: "no", and the message)
     if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K_F64) return 0;
     return (!refine_ws(idx, nq, R, k, qmode).passes && band_capable(idx, qmode)) ? 1 : 0;
 }
@@ -2054,6 +2058,7 @@ extern "C" int lmi_scan_f64_joinable(const lmi_index_desc* idx, int32_t nq, int3
     using namespace lmi;
     qmode &= ~(LMI_Q_SEED_ROUND0 | LMI_Q_PHASE_REFINE);
     take_phases(qmode);
+    if (i8_refuse("lmi_scan_f64_joinable", idx) != LMI_OK) return 0;  // (a predicate: "no", and the message)
     if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K_F64) return 0;
     return (!refine_ws(idx, nq, R, k, qmode).passes && band_capable(idx, qmode)) ? 1 : 0;
 }
@@ -2065,6 +2070,7 @@ extern "C" int lmi_bucket_topk_f64g(const lmi_index_desc* idx, const float* q, i
                                     int64_t kth_stride, double* out_d, int32_t* out_pos,
                                     int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
     LMI_CHECK_ARG(idx != nullptr && !idx->corpus32, "the global band needs an index without corpus32");
+    LMI_TRY(lmi::i8_refuse("lmi_bucket_topk_f64g", idx));
     return lmi::bucket_topk_f64_impl(idx, q, nq, ldq, q64, ldq64, classes, R, k, qmode, eps, out_d,
                                      out_pos, status, workspace, ws_bytes, stream, true, kth_send,
                                      kth_all, G, kth_stride);
@@ -2075,6 +2081,7 @@ extern "C" int lmi_refine_fallback_count(const void* workspace, const lmi_index_
                                          int32_t* count_out, void* stream) {
     using namespace lmi;
     LMI_CHECK_ARG(workspace && idx && count_out, "null pointer");
+    LMI_TRY(i8_refuse("lmi_refine_fallback_count", idx));
     qmode &= ~LMI_Q_SEED_ROUND0;
     take_phases(qmode);
     const size_t at = idx->corpus32 ? x_nfailed_offset(idx, nq, R, k) : refine_ws(idx, nq, R, k, qmode).nfailed;
@@ -2088,6 +2095,7 @@ extern "C" int lmi_split_sample_fallback_count(const void* workspace, const lmi_
                                                int32_t R, int32_t k, int32_t* count_out, void* stream) {
     using namespace lmi;
     LMI_CHECK_ARG(workspace && idx && count_out, "null pointer");
+    LMI_TRY(i8_refuse("lmi_split_sample_fallback_count", idx));
     LMI_CHECK_ARG(idx->corpus32 != nullptr, "not a split-mode index (corpus32)");
     LMI_CHECK_ARG(nq >= 0 && R >= 1 && k >= 1 && k <= LMI_MAX_K, "bad nq/R/k");
     const size_t at = x_nfailed_offset(idx, nq, R, k) + 8 * sizeof(int32_t);

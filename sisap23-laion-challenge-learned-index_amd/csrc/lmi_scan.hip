@@ -38,6 +38,7 @@
 // width, split parts, workspace offsets) and bucket_topk_impl runs it; k > 16
 // is lmi_scan_wide.hip, the split mode lmi_scan_split.hip.
 #include "lmi_scan_internal.hpp"
+#include "lmi_quant.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -123,6 +124,34 @@ __global__ __launch_bounds__(kThreads) void prep_kernel(const float* __restrict_
         // sklearn _handle_zeros_in_scale: norms < 10*eps are replaced by 1
         invq[row] = (n < 10.0f * 1.1920929e-07f) ? 1.0f : 1.0f / n;
     }
+    for (int e = lane; e < out_per_q; e += 64) {
+        out_d[(size_t)row * out_per_q + e] = __builtin_inff();
+        out_pos[(size_t)row * out_per_q + e] = -1;
+        if (out_row) out_row[(size_t)row * out_per_q + e] = -1;
+    }
+    for (int f = 0; f < fills.n; ++f)
+        for (int e = lane; e < fills.per_q[f]; e += 64)
+            fills.p[f][(size_t)row * fills.per_q[f] + e] = fills.v[f];
+}
+
+// prep_kernel for an LMI_I8 scan: qbuf = the int8 codes [nq][d_pad] of every
+// query and invq = the codes' 1/||c||, by the rows' own device function
+// (quantize_row_i8); the output prefill and the PrepFills as above.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void prep_i8_kernel(const float* __restrict__ q, int32_t nq,
+                                                           int32_t ldq, int32_t d, int32_t d_pad,
+                                                           int8_t* __restrict__ qbuf,
+                                                           float* __restrict__ invq,
+                                                           float* __restrict__ out_d,
+                                                           int32_t* __restrict__ out_pos,
+                                                           int32_t* __restrict__ out_row,
+                                                           int32_t out_per_q, PrepFills fills) {
+    const int row = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= nq) return;  // (wave-uniform; no block-wide barrier below)
+    const float inv = quantize_row_i8<float, VEC>(q + (size_t)row * ldq, d, d_pad, lane,
+                                                  qbuf + (size_t)row * d_pad);
+    if (lane == 0) invq[row] = inv;
     for (int e = lane; e < out_per_q; e += 64) {
         out_d[(size_t)row * out_per_q + e] = __builtin_inff();
         out_pos[(size_t)row * out_per_q + e] = -1;
@@ -851,6 +880,7 @@ int split_parts() {
 ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo, bool tagged) {
     ScanPlan w{};
     w.f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
+    w.i8 = (idx->dtype == LMI_I8) && (qmode == LMI_Q_I8);
     // the rings take an fp16 corpus, fp16-exact queries and d_pad == 768; the
     // diagnostic switches LMI_SCAN_V1 / LMI_SCAN_V2 force the general kernel /
     // the 4-wave ring.  The 8-wave ring has 10- and 15-entry lists; the
@@ -862,7 +892,7 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     w.family = ring8 && w.kl != 16 ? ScanKernel::Ring8
                : ring4 && !lo && !tagged ? ScanKernel::Ring4 : ScanKernel::General;
     const bool v3 = w.family == ScanKernel::Ring8;
-    w.qb = v3 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math ? 64 : 32);
+    w.qb = v3 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
     const size_t P = (size_t)nq * R;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -870,7 +900,7 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
         off = align_up(off + bytes, 256);
         return at;
     };
-    w.qbuf = take((size_t)nq * idx->d_pad * (w.f16math ? 2 : 4));
+    w.qbuf = take((size_t)nq * idx->d_pad * (w.i8 ? 1 : w.f16math ? 2 : 4));
     w.invq = take((size_t)nq * 4);
     w.counts = take((size_t)idx->n_buckets * 4);
     w.pair_q = take(P * 4);
@@ -907,6 +937,30 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     w.seed_pos = take(P * 4);
     w.total = off;
     return w;
+}
+
+int i8_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t qmode) {
+    const int32_t base = qmode & ~(LMI_Q_SEED_ROUND0 | (7 << 9) | LMI_Q_PHASE_SCAN_JOIN | LMI_Q_PHASE_REFINE);
+    const bool i8 = idx != nullptr && idx->dtype == LMI_I8;
+    if (!i8 && base != LMI_Q_I8) return LMI_OK;
+    LMI_CHECK_ARG(i8 && base == LMI_Q_I8,
+                  "%s: LMI_I8 (the 8-bit storage) and LMI_Q_I8 come together (dtype=%d, qmode=0x%x)", fn,
+                  idx ? idx->dtype : -1, qmode);
+    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: LMI_I8 takes k in [1, %d], not %d", fn, LMI_MAX_K, k);
+    LMI_CHECK_ARG(!(qmode & LMI_Q_SEED_ROUND0), "%s: LMI_I8 is never seeded (LMI_Q_SEED_ROUND0)", fn);
+    LMI_CHECK_ARG(!(qmode & LMI_Q_PHASE_SCAN_JOIN), "%s: LMI_I8 takes no join workgroups (LMI_Q_PHASE_SCAN_JOIN)", fn);
+    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
+                  "%s: LMI_I8 with corpus32 / corpus64 (the 8-bit storage keeps the codes alone)", fn);
+    LMI_CHECK_ARG(!idx->chunk_centroid, "%s: LMI_I8 takes no sub-cluster layout (chunk_centroid)", fn);
+    LMI_CHECK_ARG(idx->d_pad >= 32 && idx->d_pad % 32 == 0 && idx->d_pad <= kI8MaxDPad,
+                  "%s: LMI_I8 takes d_pad a multiple of 32 up to %d, not %d", fn, kI8MaxDPad, idx->d_pad);
+    return LMI_OK;
+}
+
+int i8_refuse(const char* fn, const lmi_index_desc* idx) {
+    LMI_CHECK_ARG(idx == nullptr || idx->dtype != LMI_I8,
+                  "%s: LMI_I8 (the 8-bit storage) is served by lmi_bucket_topk and lmi_bucket_topk_masked alone", fn);
+    return LMI_OK;
 }
 
 bool band_capable(const lmi_index_desc* idx, int qmode) {
@@ -1004,6 +1058,13 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     const int kl = p.kl, mode = c.wide ? c.wide->mode : 0;
     const bool lo = c.lo_g != nullptr, band = c.out_bound != nullptr, corpus_f16 = c.idx->dtype == LMI_F16;
     const bool plain = mode == 0 && !lo && !band;
+    if (p.i8) {
+        // the 8-bit scan: plain or tagged lists, nothing else
+        if (!plain) return {nullptr, nullptr};
+        if (c.tags != nullptr)
+            return {nullptr, kl == 10 ? launch_scan_i8<10, true> : launch_scan_i8<16, true>};
+        return {nullptr, kl == 10 ? launch_scan_i8<10, false> : launch_scan_i8<16, false>};
+    }
     if (c.tags != nullptr) {
         // the tagged scan: the 8-wave ring's MODE 4 or the general kernel's TAG
         if (!plain) return {nullptr, nullptr};
@@ -1077,6 +1138,7 @@ size_t lmi::scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t 
 extern "C" size_t lmi_scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R,
                                            int32_t k, int32_t qmode) {
     using namespace lmi;
+    if (i8_gate("lmi_scan_workspace_bytes", idx, k, qmode) != LMI_OK) return 0;
     qmode &= ~LMI_Q_SEED_ROUND0;
     take_phases(qmode);
     if (!idx || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K_PASSES) return 0;
@@ -1098,6 +1160,7 @@ extern "C" int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_
                                size_t ws_bytes, void* stream) {
     using namespace lmi;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    LMI_TRY(i8_gate("lmi_bucket_topk", idx, k, qmode));
     const bool seed = (qmode & LMI_Q_SEED_ROUND0) != 0;
     qmode &= ~LMI_Q_SEED_ROUND0;
     int phases = take_phases(qmode);
@@ -1123,7 +1186,8 @@ extern "C" size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int
     using namespace lmi;
     if (!idx || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
     if (idx->corpus32 || idx->corpus64 || idx->chunk_centroid) return 0;
-    if (qmode != LMI_Q_F16 && qmode != LMI_Q_F32) return 0;
+    if (i8_gate("lmi_scan_tagged_workspace_bytes", idx, k, qmode) != LMI_OK) return 0;
+    if (qmode != LMI_Q_F16 && qmode != LMI_Q_F32 && qmode != LMI_Q_I8) return 0;
     return scan_plan(idx, nq, R, k, qmode, false, true).total;
 }
 
@@ -1138,11 +1202,12 @@ int topk_masked(const char* fn, const lmi_index_desc* idx, const uint32_t* tags,
     // (every refusal comes before any launch and needs no device)
     LMI_CHECK_ARG(idx != nullptr, "null index");
     LMI_CHECK_ARG(tags != nullptr && value != nullptr && mask != nullptr, "%s: null tags or want", fn);
+    LMI_TRY(i8_gate(fn, idx, k, qmode));  // (the 8-bit storage's own refusals, by name)
     LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: k=%d outside [1, %d]", fn, k, LMI_MAX_K);
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64, "%s: the split mode (corpus32 / corpus64) takes no tags", fn);
     LMI_CHECK_ARG(!idx->chunk_centroid, "%s: sub-cluster layouts (chunk_centroid) take no tags", fn);
-    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32,
-                  "%s: qmode 0x%x: LMI_Q_F16 or LMI_Q_F32 alone (no phase, join or seed flag)", fn, qmode);
+    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32 || qmode == LMI_Q_I8,
+                  "%s: qmode 0x%x: LMI_Q_F16, LMI_Q_F32 or LMI_Q_I8 alone (no phase, join or seed flag)", fn, qmode);
     const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
                      .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
                      .workspace = workspace, .ws_bytes = ws_bytes,
@@ -1199,14 +1264,22 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     int32_t *out_pos = c.out_pos, *out_row = c.out_row, *status = c.status;
     hipStream_t s = c.stream;
     LMI_CHECK_ARG(idx != nullptr, "null index");
-    LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32, "bad corpus dtype");
+    LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32 || idx->dtype == LMI_I8, "bad corpus dtype");
+    // (the 8-bit storage: the checks of the entry points again, for the
+    // internal callers -- the wide path, the float64 mode, the range search --
+    // none of which it takes)
+    LMI_TRY(i8_gate("bucket_topk", idx, k, qmode | (c.seed_r0 ? LMI_Q_SEED_ROUND0 : 0)));
+    LMI_CHECK_ARG(idx->dtype != LMI_I8 || (c.lo_g == nullptr && c.wide == nullptr && c.out_bound == nullptr &&
+                                           c.range == nullptr && !(c.phases & kPhaseJoin)),
+                  "LMI_I8 takes plain and tagged lists alone (no lower bounds, wide scans, band lists, range "
+                  "scan or join phase)");
     LMI_CHECK_ARG(idx->d >= 1 && idx->d_pad >= idx->d && idx->d_pad % 32 == 0, "bad d/d_pad");
     LMI_CHECK_ARG(idx->n_buckets >= 1, "n_buckets < 1");
     LMI_CHECK_ARG(idx->chunk_rows >= 32 && idx->chunk_rows % 32 == 0, "chunk_rows must be a multiple of 32");
     LMI_CHECK_ARG(idx->n_rows >= 0 && idx->n_rows < (int64_t)UINT32_MAX, "n_rows out of range");
     LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "bad nq/R");
     LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "k=%d outside [1, %d]", k, LMI_MAX_K);
-    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32, "bad qmode");
+    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32 || qmode == LMI_Q_I8, "bad qmode");
     LMI_CHECK_ARG(ldq >= idx->d, "ldq < d");
     if (nq == 0) return LMI_OK;
     LMI_CHECK_ARG(c.q && classes && out_d && out_pos && status && c.workspace, "null pointer");
@@ -1273,7 +1346,14 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         add(ws + w.split_mask, 0u, R);
         if (ring) add(ws + w.thr_g, 0xffffffffu, 2 * R);
     }
-    if (do_plan) {
+    if (do_plan && w.i8) {
+        const dim3 pg((nq + kThreads / 64 - 1) / (kThreads / 64));
+        const bool vec = ((uintptr_t)c.q % 16 == 0) && (ldq % 4 == 0);
+        hipLaunchKernelGGL(vec ? prep_i8_kernel<true> : prep_i8_kernel<false>, pg, dim3(kThreads), 0, s, c.q, nq,
+                           ldq, idx->d, idx->d_pad, (int8_t*)(ws + w.qbuf), (float*)(ws + w.invq), out_d, out_pos,
+                           out_row, c.prefill ? R * ldo : 0, fills);
+        LMI_LAUNCH_CHECK("prep_i8_kernel");
+    } else if (do_plan) {
         const dim3 pg((nq + kThreads / 64 - 1) / (kThreads / 64));
         const bool vec = ((uintptr_t)c.q % 16 == 0) && (ldq % 4 == 0);
         auto* kp = w.f16math ? (vec ? prep_kernel<true, true> : prep_kernel<true, false>)
@@ -1500,6 +1580,7 @@ extern "C" int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t 
     using namespace lmi;
     qmode &= ~LMI_Q_SEED_ROUND0;
     take_phases(qmode);
+    if (i8_refuse("lmi_scan_joinable", idx) != LMI_OK) return 0;  // (a predicate: "no", and the message)
     if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
     return scan_plan(idx, nq, R, k, qmode).family == ScanKernel::Ring8 ? 1 : 0;
 }

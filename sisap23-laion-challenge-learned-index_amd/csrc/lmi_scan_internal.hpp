@@ -214,6 +214,11 @@ template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
 int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s);
 template <int KL>
 int launch_scan2(const Scan2Args& b, hipStream_t s);
+// scan_i8_kernel (8-bit storage: int8 corpus, int8 qbuf; KL 10 / 16, plain or TAG)
+template <int KL, bool TAG>
+int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s);
+// the widest row of the 8-bit scan
+constexpr int kI8MaxDPad = 992;
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the
@@ -231,7 +236,10 @@ struct ScanPlan {
     // fp16 corpus and fp16-exact queries; the nearest-chunk-first plan (8-wave
     // ring, chunk centroids)
     bool f16math, nearest_first;
-    int32_t split_s;      // row parts of a tail-split chunk (1: the tail split is off)
+    // the 8-bit storage (LMI_I8 with LMI_Q_I8): the general family on
+    // scan_i8_kernel, qbuf holds int8 rows
+    bool i8;
+    int32_t split_s;     // row parts of a tail-split chunk (1: the tail split is off)
     int32_t list_stride;  // partial-list slots per pair: split_s * max(max_chunks, 1)
     int32_t max_tiles;
     // offsets into the workspace (pair_pos, seed_pos: LMI_Q_SEED_ROUND0, the
@@ -243,6 +251,13 @@ struct ScanPlan {
 // 4-wave ring's and the 8-wave ring's 15-entry shapes go to the general kernel
 ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false,
                    bool tagged = false);
+// The 8-bit storage's refusals, before any launch and with no device.
+// i8_gate: a call of lmi_bucket_topk / _masked with `qmode` as the caller gave
+// it (flags included) -- LMI_OK off the 8-bit storage, else LMI_I8 and LMI_Q_I8
+// together, k <= LMI_MAX_K, no seed, no join phase, no corpus32 / corpus64 /
+// chunk_centroid, d_pad <= kI8MaxDPad.  i8_refuse: every other entry point.
+int i8_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t qmode);
+int i8_refuse(const char* fn, const lmi_index_desc* idx);
 // the 8-wave ring serves this index and query class (the float64 mode's band lists)
 bool band_capable(const lmi_index_desc* idx, int qmode);
 size_t scan_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,

@@ -8,6 +8,8 @@
 //                from HBM straight into MFMA A fragments
 //   scan2_kernel (v2, round 2)  fp16 / d_pad == 768, queries in registers,
 //                rows through an LDS-DMA ring (LMI_SCAN_V=2)
+//   scan_i8_kernel  scan_kernel on the int8 codes of the 8-bit storage (LMI_I8),
+//                any d_pad <= 992; shares scan_kernel's tile_epilogue
 // Both replace the same reference code as v3 (see lmi_scan.hip's header).
 #include "lmi_scan_internal.hpp"
 
@@ -268,6 +270,193 @@ __global__ __launch_bounds__(kThreads, 1) void scan_kernel(ScanArgs a) {
                 const int qslot = 32 * f + col;
                 tile_epilogue<KL, LO, TAG>(acc[f], L[f], &thr_s[qslot], invq_s[qslot], a.inv_norm,
                                            row_base, valid_rows, queue, lane, lo[f], a.gpos, a.tags, want[f], tmask[f]);
+            }
+        }
+        __syncthreads();  // all waves done with Qs -> reuse as merge buffer
+
+        // ---- merge the 2*kWaves partial lists of every query --------------
+        // list index of (wave, half) = 2*wave + h; layout [qslot][list][KL]
+#pragma unroll
+        for (int f = 0; f < NQF; ++f) {
+            uint64_t* dst = mergebuf + ((size_t)(32 * f + col) * (2 * kWaves) + 2 * wave + h) * KL;
+#pragma unroll
+            for (int i = 0; i < KL; ++i) dst[i] = L[f][i];
+        }
+        __syncthreads();
+        if (tid < tile.np) {
+            const uint64_t* src = mergebuf + (size_t)tid * (2 * kWaves) * KL;
+            uint64_t M[KL];
+#pragma unroll
+            for (int i = 0; i < KL; ++i) M[i] = src[i];
+            for (int l = 1; l < 2 * kWaves; ++l) {
+                for (int i = 0; i < KL; ++i) {
+                    const uint64_t key = src[l * KL + i];
+                    if (key >= M[KL - 1]) break;
+                    list_insert<KL>(M, key);
+                }
+            }
+            uint64_t* out = a.partial + ((size_t)(tile.pp0 + tid) * a.max_chunks + tile.chunk) * KL;
+#pragma unroll
+            for (int i = 0; i < KL; ++i) out[i] = M[i];
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------
+// scan, 8-bit storage (LMI_I8 / LMI_Q_I8)
+// ---------------------------------------------------------------------------
+// scan_kernel's structure -- tile queue, four waves, per-lane candidate queues,
+// the merge of the 2 * kWaves partial lists, the `partial` layout -- on int8
+// rows and int8 queries: v_mfma_i32_32x32x32_i8 sums the products exactly in
+// int32 (|acc| <= 992 * 127^2 < 2^24), so (float)acc is exact and the lists do
+// not depend on the order of k.  64 queries per tile, int8 rows in LDS with a
+// 16-byte pad; a lane streams 64 contiguous bytes of its row per 128-wide k
+// block (four MFMAs), the blocks double-buffered; what is left of d_pad (a
+// multiple of 32) goes in 32-wide blocks of one MFMA.
+using i32x4 = int __attribute__((ext_vector_type(4)));
+using i32x16 = int __attribute__((ext_vector_type(16)));
+
+constexpr int kI8QB = 64;     // queries per tile
+constexpr int kI8NQF = 2;     // 32-query MFMA fragments per wave
+constexpr int kI8QPad = 16;   // LDS row pad (bytes)
+
+template <int KL>
+size_t scan_i8_lds_bytes(int d_pad) {
+    const size_t qs = (size_t)kI8QB * (d_pad + kI8QPad);
+    const size_t merge = (size_t)kI8QB * 2 * kWaves * KL * sizeof(uint64_t);
+    const size_t queue = (size_t)kWaves * kQCap * 64 * sizeof(uint64_t);
+    return std::max(qs, merge) + queue + kI8QB * (sizeof(uint64_t) + sizeof(float)) + 16;
+}
+
+template <int KL, bool TAG>
+__global__ __launch_bounds__(kThreads, 1) void scan_i8_kernel(ScanArgs a) {
+    constexpr int QB = kI8QB, NQF = kI8NQF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    const int d_pad = a.d_pad;
+    const int ldq = d_pad + kI8QPad;  // bytes
+    const size_t qs_bytes = std::max((size_t)QB * ldq, (size_t)QB * 2 * kWaves * KL * sizeof(uint64_t));
+    int8_t* Qs = reinterpret_cast<int8_t*>(smem);
+    uint64_t* mergebuf = reinterpret_cast<uint64_t*>(smem);  // aliases Qs after the scan
+    uint64_t* queue_all = reinterpret_cast<uint64_t*>(smem + qs_bytes);
+    uint64_t* thr_s = queue_all + kWaves * kQCap * 64;
+    float* invq_s = reinterpret_cast<float*>(thr_s + QB);
+    // (no static __shared__: see scan_kernel's s_tile)
+    int& s_tile = *reinterpret_cast<int*>(invq_s + QB);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int h = lane >> 5;
+    const int col = lane & 31;
+    uint64_t* queue = queue_all + wave * kQCap * 64 + lane;
+
+    const int8_t* __restrict__ corpus = reinterpret_cast<const int8_t*>(a.corpus);
+    const int8_t* __restrict__ qbuf = reinterpret_cast<const int8_t*>(a.qbuf);
+    const int ntiles = a.meta[2 * kGroups];
+
+    for (;;) {
+        if (tid == 0) s_tile = atomicAdd(&a.work[kGroups], 1);
+        __syncthreads();
+        const int t = s_tile;
+        if (t >= ntiles) break;
+        const Tile tile = a.tiles[t];
+        const int64_t bstart = a.bucket_off[tile.c];
+        const int64_t bend = a.bucket_off[tile.c + 1];
+        const int64_t row0 = bstart + (int64_t)tile.chunk * a.chunk_rows;
+        const int nrows = (int)std::min<int64_t>(a.chunk_rows, bend - row0);
+
+        // ---- stage the tile's queries (16 B per lane per step) ----------
+        {
+            const int vpr = d_pad / 16;
+            for (int e = tid; e < QB * vpr; e += kThreads) {
+                const int r = e / vpr, v = e - r * vpr;
+                uint4 val = make_uint4(0, 0, 0, 0);
+                if (r < tile.np) {
+                    const int q = a.pair_q[tile.pp0 + r] / a.R;
+                    val = *reinterpret_cast<const uint4*>(qbuf + (size_t)q * d_pad + v * 16);
+                }
+                *reinterpret_cast<uint4*>(Qs + r * ldq + v * 16) = val;
+            }
+            for (int r = tid; r < QB; r += kThreads) {
+                const bool live = r < tile.np;
+                invq_s[r] = live ? a.invq[a.pair_q[tile.pp0 + r] / a.R] : 0.0f;
+                thr_s[r] = live ? kEmptyKey : 0ull;  // dead slots reject everything
+            }
+        }
+        __syncthreads();
+
+        uint64_t L[NQF][KL];
+        uint32_t want[NQF], tmask[NQF];  // (TAG: the value and mask words, a.want's triples)
+#pragma unroll
+        for (int f = 0; f < NQF; ++f) {
+            list_clear<KL>(L[f]);
+            const int r = 32 * f + col;
+            const size_t wq = (TAG && r < tile.np) ? 3 * (size_t)(a.pair_q[tile.pp0 + r] / a.R) : 0;
+            want[f] = (TAG && r < tile.np) ? a.want[wq + 1] : 0u;
+            tmask[f] = (TAG && r < tile.np) ? a.want[wq + 2] : 0u;
+        }
+
+        const int nsub = (nrows + 31) / 32;
+        for (int st = wave; st < nsub; st += kWaves) {
+            const int sub0 = st * 32;
+            const int myrow = std::min(sub0 + col, nrows - 1);
+            const int8_t* yrow = corpus + (size_t)(row0 + myrow) * d_pad;
+            i32x16 acc[NQF];
+#pragma unroll
+            for (int f = 0; f < NQF; ++f)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[f][i] = 0;
+
+            // 128-wide k block: lane half h covers k = kb*128 + 64h + [0, 64);
+            // MFMA step s (0..3), byte j  <->  k = kb*128 + 64h + 16s + j.
+            // A and B use the same permutation of k, and the sum is exact.
+            const i32x4* ysrc = reinterpret_cast<const i32x4*>(yrow) + 4 * h;
+            i32x4 acur[4], anext[4];
+            const int nkb = d_pad / 128;
+            if (nkb > 0) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acur[s] = ysrc[s];
+            }
+            for (int kb = 0; kb < nkb; ++kb) {
+                if (kb + 1 < nkb) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) anext[s] = ysrc[(kb + 1) * 8 + s];
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                    for (int f = 0; f < NQF; ++f) {
+                        const i32x4 b = *reinterpret_cast<const i32x4*>(
+                            Qs + (32 * f + col) * ldq + kb * 128 + 64 * h + 16 * s);
+                        acc[f] = __builtin_amdgcn_mfma_i32_32x32x32_i8(acur[s], b, acc[f], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acur[s] = anext[s];
+            }
+            // the rest of d_pad (0..3 blocks of 32): lane half h covers
+            // k = k0 + 16h + [0, 16), one MFMA each
+            for (int k0 = nkb * 128; k0 < d_pad; k0 += 32) {
+                const i32x4 av = *reinterpret_cast<const i32x4*>(yrow + k0 + 16 * h);
+#pragma unroll
+                for (int f = 0; f < NQF; ++f) {
+                    const i32x4 b = *reinterpret_cast<const i32x4*>(Qs + (32 * f + col) * ldq + k0 + 16 * h);
+                    acc[f] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, b, acc[f], 0, 0, 0);
+                }
+            }
+
+            const uint32_t row_base = (uint32_t)(row0 + sub0);
+            const int valid_rows = nrows - sub0;
+#pragma unroll
+            for (int f = 0; f < NQF; ++f) {
+                const int qslot = 32 * f + col;
+                f32x16 accf;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) accf[i] = (float)acc[f][i];
+                tile_epilogue<KL, false, TAG>(accf, L[f], &thr_s[qslot], invq_s[qslot], a.inv_norm, row_base,
+                                              valid_rows, queue, lane, 0ull, a.gpos, a.tags, want[f], tmask[f]);
             }
         }
         __syncthreads();  // all waves done with Qs -> reuse as merge buffer
@@ -609,6 +798,32 @@ int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s) {
     return LMI_OK;
 }
 
+template <int KL, bool TAG>
+int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s) {
+    const size_t lds = scan_i8_lds_bytes<KL>(d_pad);
+    if (d_pad > kI8MaxDPad || lds > 160 * 1024) {
+        set_error("LMI_I8: d_pad=%d above %d", d_pad, kI8MaxDPad);
+        return LMI_E_UNSUPPORTED;
+    }
+    static std::once_flag once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(once, [] {
+        attr_err = hipFuncSetAttribute((const void*)scan_i8_kernel<KL, TAG>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    LMI_HIP_TRY(attr_err);
+    const bool timed = timing().on;
+    std::pair<hipEvent_t, hipEvent_t> ev{};
+    if (timed) {
+        const int rc = timing_record(s, true, ev);
+        if (rc != LMI_OK) return rc;
+    }
+    hipLaunchKernelGGL((scan_i8_kernel<KL, TAG>), dim3(num_cus()), dim3(kThreads), lds, s, a);
+    LMI_LAUNCH_CHECK("scan_i8_kernel");
+    if (timed) return timing_record(s, false, ev);
+    return LMI_OK;
+}
+
 namespace {
 template <int KL, int ABL>
 int launch_scan2_v(const Scan2Args& b, hipStream_t s) {
@@ -656,6 +871,10 @@ template int launch_scan<10, false, _Float16, false, true>(const ScanArgs&, int,
 template int launch_scan<16, false, _Float16, false, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan<10, false, float, false, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan<16, false, float, false, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan_i8<10, false>(const ScanArgs&, int, hipStream_t);
+template int launch_scan_i8<16, false>(const ScanArgs&, int, hipStream_t);
+template int launch_scan_i8<10, true>(const ScanArgs&, int, hipStream_t);
+template int launch_scan_i8<16, true>(const ScanArgs&, int, hipStream_t);
 template int launch_scan2<10>(const Scan2Args&, hipStream_t);
 template int launch_scan2<16>(const Scan2Args&, hipStream_t);
 

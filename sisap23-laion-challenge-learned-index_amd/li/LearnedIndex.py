@@ -200,7 +200,7 @@ class LearnedIndex(Logger):
         return (refs[0] is data_search and refs[1] is labels and refs[2] is data_navigation.index
                 and t[0] == self._identity(data_navigation, data_search, labels))
 
-    def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None):
+    def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None, storage=None):
         """Build the HBM index of data_search (rows in data_navigation's id
         order, bucket labels `pred_categories`) now, outside any timed call,
         and trust these objects: later search / search_single calls that pass
@@ -212,10 +212,14 @@ class LearnedIndex(Logger):
         `capacity`), so that insert / delete with inplace=True can update it
         inside its own store.  `tags` (an addition; default none): one 32-bit
         tag word per object, in data_navigation's order (DeviceIndex's
-        `tags`), for filtered search: search(..., want=...)."""
+        `tags`), for filtered search: search(..., want=...).  `storage` (an
+        addition; default None: DeviceIndex's "auto"): the index's storage,
+        e.g. "i8" for the lossy 8-bit one -- search then answers from float32
+        lists of the quantised distances whatever the inputs' dtypes."""
         self._trusted = None
         self._cat_written = None
-        self._device_index(data_navigation, data_search, pred_categories, capacity=capacity, tags=tags)
+        self._device_index(data_navigation, data_search, pred_categories, capacity=capacity, tags=tags,
+                           storage=storage)
         # strong references to the trusted objects: while they are held, their
         # id()s and buffers cannot be reused by new objects (ADVICE r3)
         self._trusted = (self._identity(data_navigation, data_search, pred_categories),
@@ -228,12 +232,14 @@ class LearnedIndex(Logger):
         self._trusted = None
         self._cat_written = None
 
-    def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None):
+    def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None, storage=None):
         """DeviceIndex of data_search rows in data_navigation order (with a
         store of at least `capacity` rows when given; with `tags` a tagged
         one -- a call without `tags` reuses the cached index, tagged or not)."""
         from .index import DeviceIndex, check_tags
-        fits = lambda ix: capacity is None or ix.capacity >= int(capacity)
+        # (a call without `storage` reuses the cached index whatever its storage)
+        fits = lambda ix: (capacity is None or ix.capacity >= int(capacity)) and \
+            (storage is None or storage == "auto" or ix.storage == storage)
         if self._is_attached(data_navigation, data_search, labels) and fits(self._index):
             return self._index
         labels = np.asarray(labels).astype(np.int64)
@@ -263,6 +269,8 @@ class LearnedIndex(Logger):
         self._searcher = None
         pg = self._proc_group()
         shard = {} if pg is None else dict(rank=pg[1], world=pg[2], chunk_rows=pg[3])
+        if storage is not None:
+            shard["storage"] = storage
         self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, tags=tags, **shard)
         self._cache_key = key
         return self._index
@@ -314,10 +322,12 @@ class LearnedIndex(Logger):
         self._set_category(data_navigation, pred_categories)   # :67 (caller-visible side effect)
         index = self._device_index(data_navigation, data_search, pred_categories)
         q_nav = data_X_to_torch(queries_navigation).to(index.device)
+        # (the 8-bit storage answers float32 lists whatever the inputs' dtypes)
         return self._get_searcher(index).search(q_nav, _upload_queries(queries_search, index.device),
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
-                                                dist=dist_dtype(data_search, queries_search),
+                                                dist="f32" if index.storage == "i8" else
+                                                dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
                                                 timings=timings, want=want, avoid=avoid)
 

@@ -34,11 +34,13 @@ LMI_STATUS_BAD_PERM = 32   # K10 (lmi_perm_involutions): src_pos is no permutati
 
 LMI_F32 = 0
 LMI_F16 = 1
+LMI_I8 = 2    # 8-bit storage: int8 codes (lmi_quantize_rows_i8), with LMI_Q_I8
 LMI_ROUTER_TOPR = 0
 LMI_ROUTER_ARGMAX = 1
 LMI_PROBE_NONE = -1
 LMI_Q_F16 = 0
 LMI_Q_F32 = 1
+LMI_Q_I8 = 2
 LMI_Q_SEED_ROUND0 = 0x100
 LMI_Q_PHASE_PLAN = 0x200
 LMI_Q_PHASE_SCAN = 0x400
@@ -111,6 +113,7 @@ EXPORTS = (
     "lmi_mlp_train_steps",
     "lmi_index_move_rows",
     "lmi_index_ingest_rows",
+    "lmi_quantize_rows_i8",
     "lmi_index_move_rows_inplace",
     "lmi_bucket_sort_labels_ws_bytes",
     "lmi_bucket_sort_labels",
@@ -258,6 +261,7 @@ _SIGNATURES = {
     "lmi_index_move_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P,
                                       _P]),
     "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "lmi_quantize_rows_i8": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
     "lmi_index_move_rows_inplace": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P,
                                               _I32, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),

@@ -146,6 +146,60 @@ def _as_i32_bits(a: np.ndarray) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32))
 
 
+I8_MAX_D_PAD = 992  # the 8-bit scan's widest row (its query tile in LDS)
+
+
+def _check_i8_build(capacity, subcluster: bool, world: int, d: int) -> None:
+    """What an index of storage "i8" refuses at construction, before anything
+    is allocated."""
+    if capacity is not None:
+        raise ValueError("storage 'i8': no reserved capacity (an 8-bit index takes no updates)")
+    if subcluster:
+        raise ValueError("storage 'i8' takes no sub-cluster layout (subcluster=True)")
+    if world > 1:
+        raise ValueError("storage 'i8' is offered on one GPU (world == 1), not on a striped index")
+    if (int(d) + 31) // 32 * 32 > I8_MAX_D_PAD:
+        raise ValueError(f"storage 'i8' takes rows of at most {I8_MAX_D_PAD} values, not {int(d)}")
+
+
+def check_i8(index, what: str) -> None:
+    """ValueError when `index` is of storage "i8" and `what` (the feature's
+    name in the message) is not offered on it; before anything is launched."""
+    if getattr(index, "storage", None) == "i8":
+        raise ValueError(f"{what} is not offered on storage 'i8' (the 8-bit storage answers float32 lists of "
+                         f"at most {_lib.LMI_MAX_K} entries on one GPU)")
+
+
+def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm: torch.Tensor,
+                  dst_rows: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lmi_quantize_rows_i8: the device rows [m, d] (fp16 or float32, unit
+    stride along a row, any row stride) as int8 codes in `codes` [slots, d_pad]
+    and the codes' 1/||c|| in `inv_norm` [slots] -- row i in slot dst_rows[i]
+    (device int64 [m]) or, without dst_rows, slot i.  Every slot named must
+    exist: the kernel does not check."""
+    if rows.dtype not in (torch.float16, torch.float32):
+        rows = rows.float()
+    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        rows = rows.contiguous()
+    m, d = int(rows.shape[0]), int(rows.shape[1])
+    if codes.dtype != torch.int8 or codes.dim() != 2 or codes.shape[1] != d_pad or not codes.is_contiguous() \
+            or inv_norm.dtype != torch.float32 or inv_norm.shape != (codes.shape[0],) \
+            or not inv_norm.is_contiguous():
+        raise ValueError("quantize_rows: codes must be int8 [slots, d_pad] and inv_norm float32 [slots], contiguous")
+    if dst_rows is None:
+        if codes.shape[0] < m:
+            raise ValueError("quantize_rows: fewer slots than rows")
+    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
+        raise ValueError("quantize_rows: dst_rows must be a contiguous int64 [m] device tensor")
+    if m == 0:
+        return
+    ld = max(int(rows.stride(0)), d)  # (a single row may report any stride)
+    s = stream if stream is not None else _lib.stream_handle(codes.device)
+    check("lmi_quantize_rows_i8", _lib.load().lmi_quantize_rows_i8(
+        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
+        ptr(dst_rows), ptr(codes), ptr(inv_norm), s))
+
+
 # ---------------------------------------------------------------------------
 # device index
 # ---------------------------------------------------------------------------
@@ -173,7 +227,16 @@ class DeviceIndex:
     scan runs on each row L2-normalised and rounded to fp16, `corpus`, and the
     rows within its rounding bound of every pair's k-th distance are re-scored
     exactly from the float32 rows, `corpus32`; d_pad 768), or "f32" (the
-    general exact-fp32 MFMA scan).  "auto" picks the first that applies."""
+    general exact-fp32 MFMA scan).  "auto" picks the first that applies.
+
+    "i8" (opt-in, never picked by "auto"): the lossy 8-bit storage -- every row
+    quantised on the device to int8 codes with one scale per row
+    (lmi_quantize_rows_i8; the scale is not kept, the cosine does not need
+    it), `corpus` [n_rows, d_pad] int8 and `inv_norm` the codes' 1/||c||.  The
+    queries are quantised inside the call by the same rule, and every list is
+    the exact top-k of the quantised distances.  One byte a component; one GPU,
+    d_pad <= 992, lists of at most 16 entries, float32 lists; no capacity, no
+    sub-cluster layout, no updates, no range search (each a ValueError)."""
 
     corpus64 = None  # float64 rows (float64 input that float32 rounding changes)
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
@@ -231,6 +294,9 @@ class DeviceIndex:
 
         gpos, loc_off = self.layout.shard(rank, world)
         self._capacity = None
+        if storage == "i8":
+            _check_i8_build(capacity, subcluster, world, int(np.shape(data)[1]) if not hasattr(data, "shape")
+                            else int(data.shape[1]))
         if capacity is not None:
             if world > 1 or subcluster:
                 raise ValueError("capacity: only an index that add / remove support can reserve rows "
@@ -239,7 +305,7 @@ class DeviceIndex:
                 raise ValueError(f"capacity {int(capacity)} is below the {n} rows of the index")
             self._capacity = int(capacity)
         if isinstance(data, RowSource):
-            self._fill_from_source(data, gpos)
+            self._fill_from_source(data, gpos, storage)
         else:
             self._fill(data, gpos, storage)
         self.gpos = torch.from_numpy(gpos.astype(np.int32)).to(self.device)
@@ -556,7 +622,9 @@ class DeviceIndex:
         if src.dim() != 2 or src.shape[0] != n:
             raise ValueError("data must be [n, d] with one row per label")
         src64 = None
-        if src.dtype == torch.float64:
+        if src.dtype == torch.float64 and storage == "i8":
+            src = src.float()  # (the codes come from the float32 values; no corpus64)
+        elif src.dtype == torch.float64:
             # float64 rows (a float64 data_search): the scan reads them rounded
             # to float32; the float64 mode recomputes from the float64 values
             # when rounding changed any (lmi_index_desc.corpus64)
@@ -582,8 +650,8 @@ class DeviceIndex:
             storage = "f16" if src.dtype == torch.float16 or all(
                 fp16_exact(src[a:a + step].to(self.device)) for a in range(0, n, step)) else \
                 ("f32x" if self.d_pad == SPLIT_D_PAD else "f32")
-        if storage not in ("f16", "f32", "f32x"):
-            raise ValueError("storage must be 'auto', 'f16', 'f32' or 'f32x'")
+        if storage not in ("f16", "f32", "f32x", "i8"):
+            raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x' or 'i8'")
         if storage == "f32x" and self.d_pad != SPLIT_D_PAD:
             raise ValueError(f"storage='f32x' needs d_pad {SPLIT_D_PAD}")
         self.storage = storage
@@ -593,6 +661,16 @@ class DeviceIndex:
             raise ValueError("capacity: only an index that add / remove support can reserve rows "
                              f"(storage 'f16' without float64 rows; this one is {storage!r}"
                              + (" with corpus64)" if src64 is not None else ")"))
+        if storage == "i8":
+            # every block quantised on the device into its slots of the int8
+            # store: the codes plus one uploaded block at the peak
+            self._alloc_store(n_rows, torch.int8)
+            for a in range(0, n_rows, step):
+                blk = src.index_select(0, rows[a:a + step].to(src.device)).to(self.device)
+                quantize_rows(blk, self.d_pad, self.corpus[a:a + step], self.inv_norm[a:a + step])
+                del blk
+            torch.cuda.current_stream(self.device).synchronize()
+            return
         self._alloc_store(n_rows, tdt, zero=True)
         if storage == "f32x":
             self.corpus32 = torch.zeros((n_rows, self.d_pad), dtype=torch.float32, device=self.device)
@@ -630,17 +708,24 @@ class DeviceIndex:
                 _lib.stream_handle(self.device)))
 
     @torch.no_grad()
-    def _fill_from_source(self, src: "RowSource", gpos):
+    def _fill_from_source(self, src: "RowSource", gpos, storage="auto"):
         """Scatter every generated chunk into this shard's bucket-sorted slots
-        (fp16 storage; 1/||y|| as sklearn's normalize, zero norms -> 1)."""
+        (fp16 storage; 1/||y|| as sklearn's normalize, zero norms -> 1).
+        storage "i8": every chunk quantised straight into its slots
+        (lmi_quantize_rows_i8's dst_rows), so no fp16 copy of the corpus exists."""
         n = self.n_total
         if src.n != n:
             raise ValueError("RowSource must have one row per label")
+        if storage not in ("auto", "f16", "i8"):
+            raise ValueError("a RowSource builds storage 'f16' ('auto') or 'i8'")
         self.d = src.d
         self.d_pad = (self.d + 31) // 32 * 32
-        self.storage = "f16"
+        self.storage = "i8" if storage == "i8" else "f16"
         n_rows = int(gpos.size)
-        self._alloc_store(n_rows, torch.float16, zero=True)
+        if self.storage == "i8":
+            self._alloc_store(n_rows, torch.int8)
+        else:
+            self._alloc_store(n_rows, torch.float16, zero=True)
         slot = torch.full((n,), -1, dtype=torch.int64, device=self.device)
         slot[torch.from_numpy(self.layout.order[gpos]).to(self.device)] = torch.arange(
             n_rows, dtype=torch.int64, device=self.device)
@@ -651,10 +736,17 @@ class DeviceIndex:
             m = sl >= 0
             dst = sl[m]
             x = blk[m]
+            if self.storage == "i8":
+                quantize_rows(x, self.d_pad, self.corpus, self.inv_norm, dst_rows=dst)
+                del blk, x
+                continue
             self.corpus[dst, : self.d] = x
             self.inv_norm[dst] = _inv_norm(x)
             del blk, x
         del slot
+        if self.storage == "i8":
+            torch.cuda.current_stream(self.device).synchronize()
+            return
         self._set_inv_norm64()
 
     @torch.no_grad()
@@ -731,6 +823,31 @@ class DeviceIndex:
                 cent[int(cf[c]) + j, :d] = v / v.norm().clamp(min=1e-30)
         self.chunk_centroid = cent
 
+    @torch.no_grad()
+    def quantized(self) -> "DeviceIndex":
+        """A NEW index of storage "i8" with this one's rows quantised on the
+        device (lmi_quantize_rows_i8 over the stored rows): the same layout,
+        ids, tags and chunk tables, and bitwise the index
+        DeviceIndex(rows, ..., storage="i8") builds from the same rows.  This
+        index is not touched.  For a live one-GPU index of storage "f16" or
+        "f32" without a sub-cluster layout (ValueError otherwise); float64
+        rows kept beside a float32 store (corpus64) are not carried over."""
+        self._check_live()
+        if self.storage not in ("f16", "f32"):
+            raise ValueError(f"quantized: storage {self.storage!r} is not supported (only 'f16' and 'f32')")
+        if self.world > 1:
+            raise ValueError("quantized: storage 'i8' is offered on one GPU (world == 1), not on a stripe")
+        if self.chunk_centroid is not None:
+            raise ValueError("quantized: storage 'i8' takes no sub-cluster layout (chunk_centroid)")
+        _check_i8_build(None, False, 1, self.d)
+        new = self._successor(self.layout, self.pos_to_id, self.tags_by_pos)
+        new.storage = "i8"
+        new._adopt_store(torch.empty((self.n_rows, self.d_pad), dtype=torch.int8, device=self.device),
+                         torch.empty((self.n_rows,), dtype=torch.float32, device=self.device), self.n_rows)
+        quantize_rows(self.corpus[:, : self.d], self.d_pad, new.corpus, new.inv_norm)
+        torch.cuda.current_stream(self.device).synchronize()
+        return new
+
     @property
     def desc(self) -> _lib.IndexDesc:
         self._check_live()
@@ -769,7 +886,8 @@ class IndexDescHolder:
     def __init__(self, ix: DeviceIndex, general32: bool = False, inv_norm=None):
         d = _lib.IndexDesc()
         d.corpus = ptr(ix.corpus32 if general32 else ix.corpus)
-        d.dtype = _lib.LMI_F32 if (general32 or ix.storage == "f32") else _lib.LMI_F16
+        d.dtype = _lib.LMI_F32 if (general32 or ix.storage == "f32") else \
+            _lib.LMI_I8 if ix.storage == "i8" else _lib.LMI_F16
         d.d = ix.d
         d.d_pad = ix.d_pad
         d.n_rows = ix.n_rows
@@ -957,6 +1075,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     nq, R = classes.shape
     if q.shape[0] != nq or q.shape[1] != index.d:
         raise ValueError("query shape does not match the index")
+    if index.storage == "i8":
+        if k > _lib.LMI_MAX_K:
+            raise ValueError(f"storage 'i8' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
+        # (the one query class of the 8-bit storage; its scan is never seeded)
+        qmode, seed_round0 = _lib.LMI_Q_I8, False
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     if want is not None or avoid is not None:
@@ -1124,6 +1247,7 @@ def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
     (lmi_range_workspace_bytes answers 0: d_pad > 1248)."""
     if index.storage == "f32x":
         raise ValueError("range search is not offered on storage 'f32x' (the split mode)")
+    check_i8(index, "range search")
     if index.corpus64 is not None:
         raise ValueError("range search is not offered on an index that keeps float64 rows (corpus64)")
     if index.chunk_centroid is not None:
@@ -1243,6 +1367,7 @@ def bucket_topk_f64(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, 
     band decided over G ranks (lmi_bucket_topk_f64g, ABI 10; kth_send f32
     [nq*R*k] written by the MERGE phase, kth_all f32 [G, nq*R*k] read by the
     REFINE phase, LMI_Q_PHASE_REFINE in `phases`)."""
+    check_i8(index, "bucket_topk_f64 (float64 lists)")
     lib = _lib.load()
     q64 = None
     if isinstance(q, torch.Tensor) and q.dtype == torch.float64 or \
@@ -1470,6 +1595,8 @@ class Searcher:
         grouped = tdist.is_available() and tdist.is_initialized()
         if exchange is None:
             exchange = grouped and (index.world > 1 or force_exchange())
+        if exchange:
+            check_i8(index, "the list exchange over a process group")
         if exchange and not grouped:
             raise ValueError("the list exchange needs an initialised process group")
         if exchange and index.world == 1 and tdist.get_world_size(group) > 1:
@@ -1502,6 +1629,8 @@ class Searcher:
         check is one device reduction, run once per query batch (cached by the
         tensor's storage, shape and version counter); every rank holds the same
         batch, so every rank decides the same."""
+        if self.index.storage == "i8":
+            return _lib.LMI_Q_I8  # (the queries are quantised inside the call)
         if self.index.storage != "f16":
             return _lib.LMI_Q_F32
         import weakref
@@ -1585,6 +1714,7 @@ class Searcher:
         ValueError, like every refusal of `want`, before anything is launched."""
         check_stop(stop_mass, min_probes)
         self.index._check_live()
+        self._check_i8_lists(k_list, dist)
         if want is not None or avoid is not None:
             nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
             want = filter_words(self.index, want, avoid, nq, k_list, dist)
@@ -1594,6 +1724,15 @@ class Searcher:
         d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
                                     want=want)
         return classes, d, pos, status
+
+    def _check_i8_lists(self, k_list: int, dist: str) -> None:
+        """The lists an index of storage "i8" answers: float32, at most
+        LMI_MAX_K entries; ValueError otherwise, before anything is launched."""
+        if self.index.storage == "i8":
+            if dist != "f32":
+                check_i8(self.index, "dist='f64' (float64 lists)")
+            if k_list > _lib.LMI_MAX_K:
+                check_i8(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
 
     def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
         """K1 classes [nq, R]; with G > 1 ranks each routes nq/G queries and
@@ -1821,6 +1960,7 @@ class Searcher:
     def streamed(self, q_nav, q_search, R: int, k: int = 10, **kw) -> "StreamedSearch":
         """The step as a four-stage pipeline of captured graphs over a stream
         of batches (StreamedSearch); answers equal search(...) per batch."""
+        check_i8(self.index, "streamed() (the batch stream)")
         from .stream import StreamedSearch
         return StreamedSearch(self, q_nav, q_search, R, k, **kw)
 
@@ -1828,6 +1968,7 @@ class Searcher:
         """The step captured as a HIP graph (GraphedSearch), from the batch in
         host memory to the answer in host memory: same results as
         search(..., semantics="reference", replay_on="device")."""
+        check_i8(self.index, "graph() (the captured step)")
         from .graphed import GraphedSearch
         return GraphedSearch(self, q_nav, q_search, R, k, **kw)
 
@@ -1888,6 +2029,7 @@ class Searcher:
         if dist not in ("f32", "f64"):
             raise ValueError("dist must be 'f32' or 'f64'")
         k_list = k_round if semantics == "reference" else max(k_round, k)
+        self._check_i8_lists(k_list, dist)
         f64 = dist == "f64"
         kmax = _lib.LMI_MAX_K_F64 if f64 else _lib.LMI_MAX_K_PASSES
         if k_list > kmax:
