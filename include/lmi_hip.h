@@ -962,6 +962,16 @@ int32_t lmi_scan_set_join_workgroups(int32_t j);
 /* 1 when lmi_bucket_topk (lmi_scan_joinable) or lmi_bucket_topk_f64* (the
  * _f64 form) of these arguments runs a scan that takes j > 0, else 0. */
 int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, int32_t qmode);
+/* The kernel family that lmi_bucket_topk (tagged != 0: lmi_bucket_topk_tagged /
+ * _masked) of these arguments scans with, read from the plan the launch itself
+ * uses: 0 the general kernel (on LMI_I8: scan_i8_kernel), 1 the 4-wave ring,
+ * 2 the 8-wave ring, 3 the 8-wave ring of the 8-bit storage (LMI_I8 with
+ * LMI_Q_I8 at d_pad == 768 and k <= 10).  The diagnostic switches LMI_SCAN_V1 /
+ * LMI_SCAN_V2 show in the answer (after lmi_config_reload).  A combination the
+ * scan refuses -- LMI_I8 without LMI_Q_I8 or with LMI_Q_SEED_ROUND0, k outside
+ * [1, LMI_MAX_K], a qmode that is no query class -- is a negative LMI_E_* code
+ * (lmi_last_error says which).  Host only: no launch, no device. */
+int32_t lmi_scan_family(const lmi_index_desc* idx, int32_t k, int32_t qmode, int32_t tagged);
 int lmi_scan_f64_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k,
                           int32_t qmode);
 

@@ -889,10 +889,15 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     const bool ring4 = w.f16math && idx->d_pad == v2::D && !env_config().scan_v1;
     const bool ring8 = ring4 && !env_config().scan_v2;
     w.kl = k <= 10 ? 10 : (k <= 15 && ring8 && !tagged) ? 15 : 16;
-    w.family = ring8 && w.kl != 16 ? ScanKernel::Ring8
+    // (the 8-bit storage has a ring of its own at the same width, 10-entry
+    // lists, plain and tagged; LMI_SCAN_V1 forces scan_i8_kernel, LMI_SCAN_V2
+    // does nothing there)
+    const bool ring8i8 = w.i8 && idx->d_pad == v3::D && w.kl == 10 && !env_config().scan_v1;
+    w.family = ring8i8 ? ScanKernel::Ring8I8
+               : ring8 && w.kl != 16 ? ScanKernel::Ring8
                : ring4 && !lo && !tagged ? ScanKernel::Ring4 : ScanKernel::General;
     const bool v3 = w.family == ScanKernel::Ring8;
-    w.qb = v3 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
+    w.qb = v3 || ring8i8 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
     const size_t P = (size_t)nq * R;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -1061,6 +1066,8 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     if (p.i8) {
         // the 8-bit scan: plain or tagged lists, nothing else
         if (!plain) return {nullptr, nullptr};
+        if (p.family == ScanKernel::Ring8I8)
+            return {c.tags != nullptr ? launch_scan3_i8<true> : launch_scan3_i8<false>, nullptr};
         if (c.tags != nullptr)
             return {nullptr, kl == 10 ? launch_scan_i8<10, true> : launch_scan_i8<16, true>};
         return {nullptr, kl == 10 ? launch_scan_i8<10, false> : launch_scan_i8<16, false>};
@@ -1583,6 +1590,22 @@ extern "C" int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t 
     if (i8_refuse("lmi_scan_joinable", idx) != LMI_OK) return 0;  // (a predicate: "no", and the message)
     if (!idx || idx->corpus32 || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
     return scan_plan(idx, nq, R, k, qmode).family == ScanKernel::Ring8 ? 1 : 0;
+}
+
+extern "C" int32_t lmi_scan_family(const lmi_index_desc* idx, int32_t k, int32_t qmode, int32_t tagged) {
+    using namespace lmi;
+    if (!idx) {
+        set_error("lmi_scan_family: null index");
+        return -LMI_E_INVALID;
+    }
+    if (const int rc = i8_gate("lmi_scan_family", idx, k, qmode); rc != LMI_OK) return -rc;
+    qmode &= ~LMI_Q_SEED_ROUND0;
+    take_phases(qmode);
+    if (k < 1 || k > LMI_MAX_K || (qmode != LMI_Q_F16 && qmode != LMI_Q_F32 && qmode != LMI_Q_I8)) {
+        set_error("lmi_scan_family: k=%d outside [1, %d] or qmode 0x%x not a query class", k, LMI_MAX_K, qmode);
+        return -LMI_E_INVALID;
+    }
+    return (int32_t)scan_plan(idx, 0, 1, k, qmode, false, tagged != 0).family;
 }
 
 extern "C" int lmi_timing_enable(int32_t on) {

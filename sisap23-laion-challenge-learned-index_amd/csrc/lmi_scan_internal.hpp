@@ -219,6 +219,10 @@ template <int KL, bool TAG>
 int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s);
 // the widest row of the 8-bit scan
 constexpr int kI8MaxDPad = 992;
+// scan3_i8_kernel (lmi_scan_ring_i8.hip: the 8-wave ring on the 8-bit storage,
+// d_pad == 768, 10-entry lists, plain or TAG)
+template <bool TAG>
+int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the
@@ -226,8 +230,11 @@ constexpr int kI8MaxDPad = 992;
 // where each array lies in the caller's workspace.  bucket_topk_impl reads it;
 // so do the workspace sizes and the drivers that look into a scan's region
 // afterwards (the grouped pairs, the partial lists).  lo: a lower-bound pass.
-// General: scan_kernel; Ring4: scan2_kernel (4 waves); Ring8: scan3_kernel
-enum class ScanKernel { General, Ring4, Ring8 };
+// General: scan_kernel (8-bit storage: scan_i8_kernel); Ring4: scan2_kernel
+// (4 waves); Ring8: scan3_kernel; Ring8I8: scan3_i8_kernel (the 8-bit storage at
+// d_pad == 768 and k <= 10: the 8-wave ring's tiles, one part, none of its
+// other paths).  The values are lmi_scan_family's.
+enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3 };
 struct ScanPlan {
     ScanKernel family;
     // list length of the scan: 10 (k <= 10), 15 (k <= 15 on the 8-wave ring:
@@ -236,8 +243,8 @@ struct ScanPlan {
     // fp16 corpus and fp16-exact queries; the nearest-chunk-first plan (8-wave
     // ring, chunk centroids)
     bool f16math, nearest_first;
-    // the 8-bit storage (LMI_I8 with LMI_Q_I8): the general family on
-    // scan_i8_kernel, qbuf holds int8 rows
+    // the 8-bit storage (LMI_I8 with LMI_Q_I8): scan_i8_kernel of the general
+    // family or the Ring8I8 family, qbuf holds int8 rows
     bool i8;
     int32_t split_s;     // row parts of a tail-split chunk (1: the tail split is off)
     int32_t list_stride;  // partial-list slots per pair: split_s * max(max_chunks, 1)

@@ -130,6 +130,7 @@ EXPORTS = (
     "lmi_scan_set_join_workgroups",
     "lmi_scan_joinable",
     "lmi_scan_f64_joinable",
+    "lmi_scan_family",
     "lmi_host_hash64",
     "lmi_host_stage_f16",
     "lmi_host_copy",
@@ -278,6 +279,7 @@ _SIGNATURES = {
     "lmi_scan_set_workgroups": (C.c_int32, [_I32]),
     "lmi_scan_set_join_workgroups": (C.c_int32, [_I32]),
     "lmi_scan_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
+    "lmi_scan_family": (C.c_int32, [C.POINTER(IndexDesc), _I32, _I32, _I32]),
     "lmi_scan_f64_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_host_hash64": (C.c_uint64, [_P, C.c_uint64, _I32]),
     "lmi_host_stage_f16": (C.c_int32, [_P, C.c_uint64, _P, _I32]),

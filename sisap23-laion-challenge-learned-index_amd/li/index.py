@@ -1105,6 +1105,24 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     return out_d, out_pos, status
 
 
+SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8")
+
+
+def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None) -> str:
+    """The kernel family bucket_topk (tagged: with want / avoid) of this index
+    and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" -- as
+    lmi_scan_family reads it from the plan the launch uses (the diagnostic
+    switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk."""
+    if index.storage == "i8":
+        qmode = _lib.LMI_Q_I8
+    elif qmode is None:
+        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    fam = _lib.load().lmi_scan_family(C.byref(index.desc_for(k)), k, qmode, 1 if tagged else 0)
+    if fam < 0:
+        check("lmi_scan_family", -fam)
+    return SCAN_FAMILIES[fam]
+
+
 def want_words(index: DeviceIndex, want, nq: int, k_list: int, dist: str = "f32",
                per_query: bool = True) -> torch.Tensor:
     """The want words of a filtered scan as a device int32 [nq] tensor (the
