@@ -417,6 +417,29 @@ int lmi_range_pack(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t pai
                    const double* d64, const double* radius64, double* out_d, int32_t* out_pos,
                    int32_t* out_q, void* stream);
 
+/* ---- re-rank of short candidate lists from kept fp16 rows -------------------- */
+/* The 8-bit storage's lists are approximate.  A caller that also
+ * holds the index's fp16 rows scans longer lists (k_in entries a (query,
+ * probe)) and re-scores them here: for every pair, the k smallest of its live
+ * candidates by (d64, position), padded with (+inf, -1); d64 = the float64
+ * distance of (query, row) in the arithmetic and with the bits of
+ * lmi_bucket_topk_f64, computed from the stored fp16 row.
+ *   rows   : the descriptor of the fp16 rows (LMI_F16) in the plain bucket
+ *            layout of one GPU: position == row (gpos is the identity), no
+ *            corpus32 / corpus64 / chunk_centroid, d <= 1024; only corpus, d,
+ *            d_pad and n_rows are read
+ *   q      : device float32 [nq][ldq], the queries as given
+ *   in_pos : device int32 [nq][R][k_in] positions, -1 = empty, anywhere in a list
+ *   out_d  : device float64 [nq][R][k]; out_pos: device int32 [nq][R][k]
+ * 1 <= k <= k_in <= LMI_MAX_K.  A position >= n_rows is skipped and raises
+ * LMI_STATUS_INTERNAL in *status (device int32, OR-ed into).  A position listed
+ * twice in a pair is scored and written twice: nothing is de-duplicated.
+ * LMI_E_INVALID, before any launch, for what the above excludes.  nq == 0 is a
+ * no-op.  Additions: LMI_ABI_VERSION does not change. */
+int lmi_rerank_f64(const lmi_index_desc* rows, const float* q, int32_t nq, int32_t ldq, int32_t R,
+                   const int32_t* in_pos, int32_t k_in, int32_t k, double* out_d, int32_t* out_pos,
+                   int32_t* status, void* stream);
+
 /* Merge G per-shard lists of the same rows (K3): in
  * device [G][rows][k] (d f32, pos int32, -1 = empty), out device [rows][k] =
  * the k smallest by (d, pos).  Used after the RCCL all-gather of a G-GPU index.
@@ -959,6 +982,17 @@ int32_t lmi_scan_set_workgroups(int32_t wgs);
  * launches nothing.  Thread-local, read at launch like the grid; results
  * never depend on it.  Returns the previous setting. */
 int32_t lmi_scan_set_join_workgroups(int32_t j);
+/* The 8-bit storage's 16-entry lists on its ring (an addition: LMI_ABI_VERSION
+ * does not change).  By default lmi_bucket_topk[_masked] on LMI_I8 at d_pad ==
+ * 768 runs k = 11..16 on scan_i8_kernel, as it always has.  With on != 0 the
+ * plan of this thread sends them to the 8-wave ring (scan3_i8_kernel with
+ * 16-entry lists: the over-fetch that lmi_rerank_f64 re-scores), about a fifth
+ * of the time.  The lists are the same bits either way; the workspace layout
+ * differs, so size the workspace (lmi_scan_workspace_bytes /
+ * lmi_scan_tagged_workspace_bytes) and ask lmi_scan_family under the setting the
+ * call runs with.  Thread-local, read when the plan is made (every call).
+ * LMI_SCAN_V1 still forces scan_i8_kernel.  Returns the previous setting. */
+int32_t lmi_scan_set_i8_lists16(int32_t on);
 /* 1 when lmi_bucket_topk (lmi_scan_joinable) or lmi_bucket_topk_f64* (the
  * _f64 form) of these arguments runs a scan that takes j > 0, else 0. */
 int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, int32_t qmode);
@@ -966,7 +1000,8 @@ int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t 
  * _masked) of these arguments scans with, read from the plan the launch itself
  * uses: 0 the general kernel (on LMI_I8: scan_i8_kernel), 1 the 4-wave ring,
  * 2 the 8-wave ring, 3 the 8-wave ring of the 8-bit storage (LMI_I8 with
- * LMI_Q_I8 at d_pad == 768 and k <= 10).  The diagnostic switches LMI_SCAN_V1 /
+ * LMI_Q_I8 at d_pad == 768: k <= 10, and k = 11..16 on a thread that set
+ * lmi_scan_set_i8_lists16).  The diagnostic switches LMI_SCAN_V1 /
  * LMI_SCAN_V2 show in the answer (after lmi_config_reload).  A combination the
  * scan refuses -- LMI_I8 without LMI_Q_I8 or with LMI_Q_SEED_ROUND0, k outside
  * [1, LMI_MAX_K], a qmode that is no query class -- is a negative LMI_E_* code

@@ -871,6 +871,7 @@ __global__ __launch_bounds__(256) void want_pack_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+thread_local int t_i8_lists16 = 0;  // lmi_scan_set_i8_lists16 (0: k = 11..16 stay on scan_i8_kernel)
 }  // namespace
 
 int split_parts() {
@@ -889,10 +890,13 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     const bool ring4 = w.f16math && idx->d_pad == v2::D && !env_config().scan_v1;
     const bool ring8 = ring4 && !env_config().scan_v2;
     w.kl = k <= 10 ? 10 : (k <= 15 && ring8 && !tagged) ? 15 : 16;
-    // (the 8-bit storage has a ring of its own at the same width, 10-entry
-    // lists, plain and tagged; LMI_SCAN_V1 forces scan_i8_kernel, LMI_SCAN_V2
-    // does nothing there)
-    const bool ring8i8 = w.i8 && idx->d_pad == v3::D && w.kl == 10 && !env_config().scan_v1;
+    // (the 8-bit storage has a ring of its own at the same width, plain and
+    // tagged: 10-entry lists, and 16-entry ones for the threads that asked
+    // for them -- lmi_scan_set_i8_lists16, the over-fetch of a re-rank; by
+    // default k = 11..16 keep the plan they had, scan_i8_kernel's.
+    // LMI_SCAN_V1 forces scan_i8_kernel, LMI_SCAN_V2 does nothing there)
+    const bool ring8i8 = w.i8 && idx->d_pad == v3::D && (w.kl == 10 || (w.kl == 16 && t_i8_lists16 != 0)) &&
+                         !env_config().scan_v1;
     w.family = ring8i8 ? ScanKernel::Ring8I8
                : ring8 && w.kl != 16 ? ScanKernel::Ring8
                : ring4 && !lo && !tagged ? ScanKernel::Ring4 : ScanKernel::General;
@@ -1067,7 +1071,9 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
         // the 8-bit scan: plain or tagged lists, nothing else
         if (!plain) return {nullptr, nullptr};
         if (p.family == ScanKernel::Ring8I8)
-            return {c.tags != nullptr ? launch_scan3_i8<true> : launch_scan3_i8<false>, nullptr};
+            return {c.tags != nullptr ? (kl == 10 ? launch_scan3_i8<10, true> : launch_scan3_i8<16, true>)
+                                      : (kl == 10 ? launch_scan3_i8<10, false> : launch_scan3_i8<16, false>),
+                    nullptr};
         if (c.tags != nullptr)
             return {nullptr, kl == 10 ? launch_scan_i8<10, true> : launch_scan_i8<16, true>};
         return {nullptr, kl == 10 ? launch_scan_i8<10, false> : launch_scan_i8<16, false>};
@@ -1580,6 +1586,12 @@ extern "C" int32_t lmi_scan_set_workgroups(int32_t wgs) {
 extern "C" int32_t lmi_scan_set_join_workgroups(int32_t j) {
     const int prev = lmi::t_join_wgs;
     lmi::t_join_wgs = j > 0 ? j : 0;
+    return prev;
+}
+
+extern "C" int32_t lmi_scan_set_i8_lists16(int32_t on) {
+    const int prev = lmi::t_i8_lists16;
+    lmi::t_i8_lists16 = on != 0 ? 1 : 0;
     return prev;
 }
 

@@ -163,7 +163,7 @@ __device__ __forceinline__ void list_store(uint32_t addr, const uint64_t (&L)[KL
 // round 1, 8: one lane's entries contiguous)
 template <int KL, int OFF = 0, int ES = 512>
 __device__ __forceinline__ void list_load(uint32_t addr, uint64_t (&L)[KL]) {
-    static_assert(KL == 10 || KL == 15, "one asm block of 10 or 15 reads");
+    static_assert(KL == 10 || KL == 15 || KL == 16, "one asm block of 10, 15 or 16 reads");
     // all reads in flight, one wait (a wait per read would serialise the LDS
     // round trips); one asm statement so no use can slip before the wait
     if constexpr (KL == 10) {
@@ -184,6 +184,34 @@ __device__ __forceinline__ void list_load(uint32_t addr, uint64_t (&L)[KL]) {
             : "v"(addr), "i"(OFF), "i"(OFF + ES), "i"(OFF + 2 * ES), "i"(OFF + 3 * ES),
               "i"(OFF + 4 * ES), "i"(OFF + 5 * ES), "i"(OFF + 6 * ES), "i"(OFF + 7 * ES),
               "i"(OFF + 8 * ES), "i"(OFF + 9 * ES)
+            : "memory");
+    } else if constexpr (KL == 16) {
+        // (scan3_i8_kernel's 16-entry lists)
+        asm volatile(
+            "ds_read_b64 %0, %16 offset:%17\n\t"
+            "ds_read_b64 %1, %16 offset:%18\n\t"
+            "ds_read_b64 %2, %16 offset:%19\n\t"
+            "ds_read_b64 %3, %16 offset:%20\n\t"
+            "ds_read_b64 %4, %16 offset:%21\n\t"
+            "ds_read_b64 %5, %16 offset:%22\n\t"
+            "ds_read_b64 %6, %16 offset:%23\n\t"
+            "ds_read_b64 %7, %16 offset:%24\n\t"
+            "ds_read_b64 %8, %16 offset:%25\n\t"
+            "ds_read_b64 %9, %16 offset:%26\n\t"
+            "ds_read_b64 %10, %16 offset:%27\n\t"
+            "ds_read_b64 %11, %16 offset:%28\n\t"
+            "ds_read_b64 %12, %16 offset:%29\n\t"
+            "ds_read_b64 %13, %16 offset:%30\n\t"
+            "ds_read_b64 %14, %16 offset:%31\n\t"
+            "ds_read_b64 %15, %16 offset:%32\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(L[0]), "=&v"(L[1]), "=&v"(L[2]), "=&v"(L[3]), "=&v"(L[4]), "=&v"(L[5]),
+              "=&v"(L[6]), "=&v"(L[7]), "=&v"(L[8]), "=&v"(L[9]), "=&v"(L[10]), "=&v"(L[11]),
+              "=&v"(L[12]), "=&v"(L[13]), "=&v"(L[14]), "=&v"(L[15])
+            : "v"(addr), "i"(OFF), "i"(OFF + ES), "i"(OFF + 2 * ES), "i"(OFF + 3 * ES),
+              "i"(OFF + 4 * ES), "i"(OFF + 5 * ES), "i"(OFF + 6 * ES), "i"(OFF + 7 * ES),
+              "i"(OFF + 8 * ES), "i"(OFF + 9 * ES), "i"(OFF + 10 * ES), "i"(OFF + 11 * ES),
+              "i"(OFF + 12 * ES), "i"(OFF + 13 * ES), "i"(OFF + 14 * ES), "i"(OFF + 15 * ES)
             : "memory");
     } else {
         asm volatile(

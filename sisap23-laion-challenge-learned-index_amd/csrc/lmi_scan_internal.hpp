@@ -220,8 +220,8 @@ int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s);
 // the widest row of the 8-bit scan
 constexpr int kI8MaxDPad = 992;
 // scan3_i8_kernel (lmi_scan_ring_i8.hip: the 8-wave ring on the 8-bit storage,
-// d_pad == 768, 10-entry lists, plain or TAG)
-template <bool TAG>
+// d_pad == 768, lists of KL = 10 or 16 entries, plain or TAG)
+template <int KL, bool TAG>
 int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
@@ -232,7 +232,7 @@ int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
 // afterwards (the grouped pairs, the partial lists).  lo: a lower-bound pass.
 // General: scan_kernel (8-bit storage: scan_i8_kernel); Ring4: scan2_kernel
 // (4 waves); Ring8: scan3_kernel; Ring8I8: scan3_i8_kernel (the 8-bit storage at
-// d_pad == 768 and k <= 10: the 8-wave ring's tiles, one part, none of its
+// d_pad == 768 and k <= 16: the 8-wave ring's tiles, one part, none of its
 // other paths).  The values are lmi_scan_family's.
 enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3 };
 struct ScanPlan {

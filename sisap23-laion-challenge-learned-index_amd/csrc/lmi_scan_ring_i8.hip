@@ -1,9 +1,10 @@
 // scan3_i8_kernel: the 8-wave ring (scan3_kernel, lmi_scan3.hpp) on the int8
-// codes of the 8-bit storage (LMI_I8 / LMI_Q_I8), d_pad == 768, k <= 10, plain
-// and tagged.  The family ScanKernel::Ring8I8 of the scan's plan; every other
-// 8-bit shape stays on scan_i8_kernel (lmi_scan_v12.hip), which LMI_SCAN_V1=1
-// also forces here.  The lists are scan_i8_kernel's bit for bit: the integer
-// sums are exact and the distance expression is the same one.
+// codes of the 8-bit storage (LMI_I8 / LMI_Q_I8), d_pad == 768, k <= 16 (lists
+// of 10 or 16 entries), plain and tagged.  The family ScanKernel::Ring8I8 of
+// the scan's plan; every other 8-bit shape stays on scan_i8_kernel
+// (lmi_scan_v12.hip), which LMI_SCAN_V1=1 also forces here.  The lists are
+// scan_i8_kernel's bit for bit: the integer sums are exact and the distance
+// expression is the same one.
 #include "lmi_scan3.hpp"
 
 #include <algorithm>
@@ -31,7 +32,8 @@ using i32x16 = int __attribute__((ext_vector_type(16)));
 //              stage is 8 pieces (one 1-KiB DMA each) of four rows, wave w
 //              brings piece w of every stage (rows 4w .. 4w+3 whole), their 4
 //              norms and, tagged, their 4 tag words; one s_barrier per block
-//   lists    : 10 entries a lane in LDS, lane-interleaved, as in the fp16 ring;
+//   lists    : KL = 10 or 16 entries a lane in LDS (k <= 10, k = 11..16: the
+//              over-fetch of a re-rank), lane-interleaved, as in the fp16 ring;
 //              the tagged form keeps the pair's value and mask words in
 //              registers (there is room here) and reads the row's tag from LDS
 //   not here : seeds, join workgroups, the tail split, nearest-chunk-first,
@@ -59,21 +61,24 @@ constexpr int LIST_OFF = TAG_OFF + 3 * 128;
 constexpr int NW = 8;
 constexpr int QB = NW * 32;
 constexpr int NQF = D / 32;            // B fragments (and MFMAs per block)
-constexpr int KL = 10;
+// KL entries a lane: 94 016 bytes for KL = 10, 118 592 for KL = 16 (one
+// 512-thread workgroup a CU either way)
+template <int KL>
 constexpr size_t kLds = (size_t)LIST_OFF + (size_t)NW * 64 * KL * 8 + 64;
-static_assert(kLds <= 160 * 1024, "LDS budget");
+static_assert(kLds<16> <= 160 * 1024, "LDS budget");
 static_assert(QB == v3::QB, "the plan's tile width");
 }  // namespace r8
 
 // TAG (lmi_bucket_topk_tagged / _masked): MODE 4's rule -- a row is a candidate
 // of a pair only if (tag & mask) == value; invq holds (1/|q|, value, mask)
 // triples; the test runs before the list is touched.
-template <bool TAG>
+template <int KL, bool TAG>
 __global__ __launch_bounds__(512, 1) void scan3_i8_kernel(Scan2Args a) {
+    static_assert(KL == 10 || KL == 16, "10- or 16-entry lists");
     using namespace r8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* ring = smem;
-    // entry i of lane l of wave w at LIST_OFF + w * 5120 + i * 512 + l * 8
+    // entry i of lane l of wave w at LIST_OFF + w * 512 KL + i * 512 + l * 8
     uint64_t* lists = reinterpret_cast<uint64_t*>(smem + LIST_OFF);
     int* wtab = reinterpret_cast<int*>(lists + NW * 64 * KL);  // [NW] SIMD ids, [NW] tile
     int& s_tile = wtab[NW];
@@ -357,13 +362,13 @@ __global__ __launch_bounds__(512, 1) void scan3_i8_kernel(Scan2Args a) {
 
 // one launch of the persistent grid (one workgroup per CU, dynamic LDS); HIP
 // events around it while lmi_timing_enable is on
-template <bool TAG>
+template <int KL, bool TAG>
 int launch_scan3_i8(const Scan2Args& b, hipStream_t s) {
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan3_i8_kernel<TAG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)r8::kLds);
+        attr_err = hipFuncSetAttribute((const void*)scan3_i8_kernel<KL, TAG>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)r8::kLds<KL>);
     });
     LMI_HIP_TRY(attr_err);
     const bool timed = timing().on;
@@ -372,13 +377,15 @@ int launch_scan3_i8(const Scan2Args& b, hipStream_t s) {
         const int rc = timing_record(s, true, ev);
         if (rc != LMI_OK) return rc;
     }
-    hipLaunchKernelGGL((scan3_i8_kernel<TAG>), dim3(scan_grid()), dim3(r8::NW * 64), r8::kLds, s, b);
+    hipLaunchKernelGGL((scan3_i8_kernel<KL, TAG>), dim3(scan_grid()), dim3(r8::NW * 64), r8::kLds<KL>, s, b);
     LMI_LAUNCH_CHECK("scan3_i8_kernel");
     if (timed) return timing_record(s, false, ev);
     return LMI_OK;
 }
 
-template int launch_scan3_i8<false>(const Scan2Args&, hipStream_t);
-template int launch_scan3_i8<true>(const Scan2Args&, hipStream_t);
+template int launch_scan3_i8<10, false>(const Scan2Args&, hipStream_t);
+template int launch_scan3_i8<10, true>(const Scan2Args&, hipStream_t);
+template int launch_scan3_i8<16, false>(const Scan2Args&, hipStream_t);
+template int launch_scan3_i8<16, true>(const Scan2Args&, hipStream_t);
 
 }  // namespace lmi

@@ -138,7 +138,8 @@ class LearnedIndex(Logger):
     _searcher = None
     _attached_labels = None
     _cat_written = None
-    _pg = None        # process-group mode: (group, rank, world, chunk_rows)
+    _rerank = None    # attach(..., rerank=k2): search re-ranks k2-entry 8-bit lists
+    _pg = None       # process-group mode: (group, rank, world, chunk_rows)
 
     def __init__(self):
         self.model = None
@@ -200,7 +201,8 @@ class LearnedIndex(Logger):
         return (refs[0] is data_search and refs[1] is labels and refs[2] is data_navigation.index
                 and t[0] == self._identity(data_navigation, data_search, labels))
 
-    def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None, storage=None):
+    def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None, storage=None,
+               keep_rows=False, rerank=None):
         """Build the HBM index of data_search (rows in data_navigation's id
         order, bucket labels `pred_categories`) now, outside any timed call,
         and trust these objects: later search / search_single calls that pass
@@ -215,11 +217,28 @@ class LearnedIndex(Logger):
         `tags`), for filtered search: search(..., want=...).  `storage` (an
         addition; default None: DeviceIndex's "auto"): the index's storage,
         e.g. "i8" for the lossy 8-bit one -- search then answers from float32
-        lists of the quantised distances whatever the inputs' dtypes."""
+        lists of the quantised distances whatever the inputs' dtypes.
+        `keep_rows` (an addition; storage "i8" alone): the 8-bit index also
+        keeps the fp16 rows (DeviceIndex's `keep_rows`).  `rerank` = k2 (an
+        addition; needs storage="i8" and keep_rows=True, 10 < k2 <= 16): search
+        then scans k2-entry 8-bit lists and re-ranks each to its 10 entries by
+        the float64 distances of the kept rows (Searcher.search's `rerank`):
+        exact float64 distances on an approximate candidate set.  ValueError
+        before anything is built for a `rerank` without those two, or outside
+        that range."""
+        if rerank is not None:
+            if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
+                raise ValueError("rerank must be an integer")
+            if storage != "i8" or not keep_rows:
+                raise ValueError("rerank needs storage='i8' and keep_rows=True (the rows it re-ranks from)")
+            if not 10 < int(rerank) <= _lib.LMI_MAX_K:
+                raise ValueError(f"rerank = {int(rerank)} must lie in (10, {_lib.LMI_MAX_K}] (search's lists "
+                                 "have 10 entries)")
         self._trusted = None
         self._cat_written = None
         self._device_index(data_navigation, data_search, pred_categories, capacity=capacity, tags=tags,
-                           storage=storage)
+                           storage=storage, keep_rows=keep_rows)
+        self._rerank = None if rerank is None else int(rerank)
         # strong references to the trusted objects: while they are held, their
         # id()s and buffers cannot be reused by new objects (ADVICE r3)
         self._trusted = (self._identity(data_navigation, data_search, pred_categories),
@@ -232,14 +251,16 @@ class LearnedIndex(Logger):
         self._trusted = None
         self._cat_written = None
 
-    def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None, storage=None):
+    def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None, storage=None,
+                      keep_rows=False):
         """DeviceIndex of data_search rows in data_navigation order (with a
         store of at least `capacity` rows when given; with `tags` a tagged
         one -- a call without `tags` reuses the cached index, tagged or not)."""
         from .index import DeviceIndex, check_tags
         # (a call without `storage` reuses the cached index whatever its storage)
         fits = lambda ix: (capacity is None or ix.capacity >= int(capacity)) and \
-            (storage is None or storage == "auto" or ix.storage == storage)
+            (storage is None or storage == "auto" or ix.storage == storage) and \
+            (not keep_rows or ix.rows16 is not None)
         if self._is_attached(data_navigation, data_search, labels) and fits(self._index):
             return self._index
         labels = np.asarray(labels).astype(np.int64)
@@ -271,6 +292,8 @@ class LearnedIndex(Logger):
         shard = {} if pg is None else dict(rank=pg[1], world=pg[2], chunk_rows=pg[3])
         if storage is not None:
             shard["storage"] = storage
+        if keep_rows:
+            shard["keep_rows"] = True
         self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, tags=tags, **shard)
         self._cache_key = key
         return self._index
@@ -322,14 +345,17 @@ class LearnedIndex(Logger):
         self._set_category(data_navigation, pred_categories)   # :67 (caller-visible side effect)
         index = self._device_index(data_navigation, data_search, pred_categories)
         q_nav = data_X_to_torch(queries_navigation).to(index.device)
-        # (the 8-bit storage answers float32 lists whatever the inputs' dtypes)
+        # (the 8-bit storage answers float32 lists whatever the inputs' dtypes,
+        # or -- attach(..., rerank=k2) -- float64 ones re-ranked from its fp16 rows)
+        rerank = self._rerank if index.storage == "i8" and index.rows16 is not None else None
         return self._get_searcher(index).search(q_nav, _upload_queries(queries_search, index.device),
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
-                                                dist="f32" if index.storage == "i8" else
+                                                dist="f64" if rerank is not None else
+                                                "f32" if index.storage == "i8" else
                                                 dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
-                                                timings=timings, want=want, avoid=avoid)
+                                                timings=timings, want=want, avoid=avoid, rerank=rerank)
 
     def range_search(self, data_navigation, queries_navigation, data_search, queries_search,
                      pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None,

@@ -87,6 +87,7 @@ EXPORTS = (
     "lmi_bucket_range",
     "lmi_range_rescore_f64",
     "lmi_range_pack",
+    "lmi_rerank_f64",
     "lmi_merge_topk",
     "lmi_scan_f64_workspace_bytes",
     "lmi_bucket_topk_f64",
@@ -128,6 +129,7 @@ EXPORTS = (
     "lmi_config_reload",
     "lmi_scan_set_workgroups",
     "lmi_scan_set_join_workgroups",
+    "lmi_scan_set_i8_lists16",
     "lmi_scan_joinable",
     "lmi_scan_f64_joinable",
     "lmi_scan_family",
@@ -223,6 +225,7 @@ _SIGNATURES = {
                                         _P, _P]),
     "lmi_range_pack": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P]),
+    "lmi_rerank_f64": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P]),
     "lmi_merge_topk": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P]),
     "lmi_scan_f64_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_f64": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,
@@ -278,6 +281,7 @@ _SIGNATURES = {
     "lmi_config_reload": (C.c_int, []),
     "lmi_scan_set_workgroups": (C.c_int32, [_I32]),
     "lmi_scan_set_join_workgroups": (C.c_int32, [_I32]),
+    "lmi_scan_set_i8_lists16": (C.c_int32, [_I32]),
     "lmi_scan_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_scan_family": (C.c_int32, [C.POINTER(IndexDesc), _I32, _I32, _I32]),
     "lmi_scan_f64_joinable": (C.c_int, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),

@@ -236,8 +236,21 @@ class DeviceIndex:
     queries are quantised inside the call by the same rule, and every list is
     the exact top-k of the quantised distances.  One byte a component; one GPU,
     d_pad <= 992, lists of at most 16 entries, float32 lists; no capacity, no
-    sub-cluster layout, no updates, no range search (each a ValueError)."""
+    sub-cluster layout, no updates, no range search (each a ValueError).
 
+    keep_rows=True (storage "i8" alone): the index also holds `rows16`, the
+    bucket-sorted fp16 rows [n_rows, d_pad] (zero past d; row r of `rows16` is
+    row r of `corpus`, so a list's position indexes both).  Searcher.lists /
+    search(..., dist="f64", rerank=k2) then scan k2-entry 8-bit lists and
+    re-score them from these rows in float64 (rerank_f64): exact distances on
+    an approximate candidate set.  Built from host rows, every value must be
+    fp16-representable (the rule of storage "f16"); not with a RowSource,
+    whose point is that no fp16 copy exists.  quantized(keep_rows=True) of an
+    index of storage "f16" shares that index's corpus tensor (no copy): the
+    source must then not be updated in place while this index is in use."""
+
+    rows16 = None  # the fp16 rows kept beside the int8 codes (storage "i8", keep_rows=True)
+    _rows_desc = None  # the descriptor over rows16 (rows_desc)
     corpus64 = None  # float64 rows (float64 input that float32 rounding changes)
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
     corpus32n = None  # corpus32 normalised as sklearn does in float32 (ABI 11)
@@ -258,8 +271,13 @@ class DeviceIndex:
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
                  storage: str = "auto", chunk_rows: Optional[int] = None,
                  rank: int = 0, world: int = 1, subcluster: bool = False,
-                 capacity: Optional[int] = None, tags=None):
-        """`tags` (None: an untagged index): one 32-bit tag word per input row,
+                 capacity: Optional[int] = None, tags=None, keep_rows: bool = False):
+        """`keep_rows` (storage "i8" alone, see the class): keep the fp16 rows
+        beside the codes, for Searcher's `rerank`.  ValueError, before anything
+        is allocated, with another storage, with a RowSource, or for rows that
+        are not fp16-representable.
+
+        `tags` (None: an untagged index): one 32-bit tag word per input row,
         any integer array with values in [0, 2^32), for filtered search
         (Searcher.lists / search with `want`: a row is eligible for a query iff
         (tag & want) == want).  Not with subcluster=True (ValueError).
@@ -273,6 +291,12 @@ class DeviceIndex:
         sub-cluster layout): ValueError otherwise, or when below the row
         count."""
         _lib.load()
+        if keep_rows:
+            if storage != "i8":
+                raise ValueError(f"keep_rows: the fp16 rows are kept beside storage 'i8' alone, not {storage!r}")
+            if isinstance(data, RowSource):
+                raise ValueError("keep_rows: a RowSource builds storage 'i8' so that no fp16 copy exists")
+        self._keep_rows = bool(keep_rows)
         self.device = torch.device(device if device is not None else "cuda")
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
         self.layout = BucketLayout.from_labels(lab, n_buckets)
@@ -664,10 +688,18 @@ class DeviceIndex:
         if storage == "i8":
             # every block quantised on the device into its slots of the int8
             # store: the codes plus one uploaded block at the peak
+            keep = getattr(self, "_keep_rows", False)
+            if keep and src.dtype != torch.float16 and not all(
+                    fp16_exact(src[a:a + step]) for a in range(0, n, step)):
+                raise ValueError("keep_rows needs fp16-representable data (the rule of storage='f16')")
             self._alloc_store(n_rows, torch.int8)
+            if keep:
+                self.rows16 = torch.zeros((n_rows, self.d_pad), dtype=torch.float16, device=self.device)
             for a in range(0, n_rows, step):
                 blk = src.index_select(0, rows[a:a + step].to(src.device)).to(self.device)
                 quantize_rows(blk, self.d_pad, self.corpus[a:a + step], self.inv_norm[a:a + step])
+                if keep:
+                    self.rows16[a:a + step, : self.d] = blk.half()
                 del blk
             torch.cuda.current_stream(self.device).synchronize()
             return
@@ -824,17 +856,22 @@ class DeviceIndex:
         self.chunk_centroid = cent
 
     @torch.no_grad()
-    def quantized(self) -> "DeviceIndex":
+    def quantized(self, keep_rows: bool = False) -> "DeviceIndex":
         """A NEW index of storage "i8" with this one's rows quantised on the
         device (lmi_quantize_rows_i8 over the stored rows): the same layout,
         ids, tags and chunk tables, and bitwise the index
         DeviceIndex(rows, ..., storage="i8") builds from the same rows.  This
         index is not touched.  For a live one-GPU index of storage "f16" or
         "f32" without a sub-cluster layout (ValueError otherwise); float64
-        rows kept beside a float32 store (corpus64) are not carried over."""
+        rows kept beside a float32 store (corpus64) are not carried over.
+        keep_rows=True (storage "f16" alone, else ValueError): the new index's
+        `rows16` is this index's corpus tensor itself -- no copy; do not update
+        this index in place while the new one is in use."""
         self._check_live()
         if self.storage not in ("f16", "f32"):
             raise ValueError(f"quantized: storage {self.storage!r} is not supported (only 'f16' and 'f32')")
+        if keep_rows and self.storage != "f16":
+            raise ValueError(f"quantized(keep_rows=True): the kept rows are fp16 (storage 'f16'), not {self.storage!r}")
         if self.world > 1:
             raise ValueError("quantized: storage 'i8' is offered on one GPU (world == 1), not on a stripe")
         if self.chunk_centroid is not None:
@@ -845,8 +882,26 @@ class DeviceIndex:
         new._adopt_store(torch.empty((self.n_rows, self.d_pad), dtype=torch.int8, device=self.device),
                          torch.empty((self.n_rows,), dtype=torch.float32, device=self.device), self.n_rows)
         quantize_rows(self.corpus[:, : self.d], self.d_pad, new.corpus, new.inv_norm)
+        if keep_rows:
+            new.rows16 = self.corpus
         torch.cuda.current_stream(self.device).synchronize()
         return new
+
+    @property
+    def rows_desc(self) -> _lib.IndexDesc:
+        """The descriptor of the kept fp16 rows (`rows16`) that lmi_rerank_f64
+        takes: the rows, their width and count; nothing else is read."""
+        self._check_live()
+        if self.rows16 is None:
+            raise ValueError("this index keeps no fp16 rows (build it with storage='i8', keep_rows=True)")
+        if self._rows_desc is None:
+            d = _lib.IndexDesc()
+            d.corpus = ptr(self.rows16)
+            d.dtype = _lib.LMI_F16
+            d.d, d.d_pad, d.n_rows = self.d, self.d_pad, self.n_rows
+            d.n_buckets = self.n_buckets
+            self._rows_desc = d
+        return self._rows_desc
 
     @property
     def desc(self) -> _lib.IndexDesc:
@@ -1052,9 +1107,25 @@ def _workspace(ws, need: int, what: str) -> torch.Tensor:
     return ws
 
 
+class i8_lists16:
+    """Inside this context the calling thread's scans of an index of storage
+    "i8" at d_pad 768 run k = 11..16 on the 8-bit ring's 16-entry lists
+    (lmi_scan_set_i8_lists16) instead of scan_i8_kernel: the same lists bit for
+    bit, about a fifth of the time.  Off by default, so that every call keeps
+    the plan (kernel family, workspace size) it had; bucket_topk(...,
+    lists16=True) and the re-rank of Searcher turn it on for their own scan."""
+
+    def __enter__(self):
+        self.prev = _lib.load().lmi_scan_set_i8_lists16(1)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.load().lmi_scan_set_i8_lists16(self.prev)
+
+
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                 qmode: Optional[int] = None, stream=None, out=None, ws=None,
-                seed_round0: bool = False, phases: int = 0, want=None, avoid=None):
+                seed_round0: bool = False, phases: int = 0, want=None, avoid=None, lists16: bool = False):
     """K2 on one shard.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
     `out` = such a triple to write into (the status word zeroed by the caller);
     `ws` = a caller-owned uint8 workspace (default: the index's cached one,
@@ -1068,7 +1139,13 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     (tag & want) == want are listed; never seeded, no phases.  `avoid` (the
     same form; alone it means want = 0): and only rows with (tag & avoid) == 0.
     At this level the words are on the device: that no query wants and avoids
-    one bit is the caller's check (mask_words makes it on the host)."""
+    one bit is the caller's check (mask_words makes it on the host).
+    `lists16`: the call runs inside i8_lists16() (storage "i8" at d_pad 768:
+    k = 11..16 on the ring's 16-entry lists; the workspace is sized there too)."""
+    if lists16:
+        with i8_lists16():
+            return bucket_topk(index, q, classes, k, qmode=qmode, stream=stream, out=out, ws=ws,
+                               seed_round0=seed_round0, phases=phases, want=want, avoid=avoid)
     lib = _lib.load()
     q = _rows_f32(q, index.device)
     classes = _as_torch(classes, index.device, torch.int32)
@@ -1108,11 +1185,16 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
 SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8")
 
 
-def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None) -> str:
+def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None,
+                lists16: bool = False) -> str:
     """The kernel family bucket_topk (tagged: with want / avoid) of this index
     and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" -- as
     lmi_scan_family reads it from the plan the launch uses (the diagnostic
-    switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk."""
+    switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk;
+    `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan."""
+    if lists16:
+        with i8_lists16():
+            return scan_family(index, k, tagged, qmode)
     if index.storage == "i8":
         qmode = _lib.LMI_Q_I8
     elif qmode is None:
@@ -1357,6 +1439,62 @@ def range_rescore_f64(index: DeviceIndex, q: torch.Tensor, radius64: torch.Tenso
         C.byref(index.desc_for(1, f64=True)), ptr(q), nq, q.stride(0), R, ptr(radius64), cap, ptr(cand),
         ptr(count), ptr(d64), ptr(kept), s))
     return d64, kept
+
+
+RERANK_MAX = _lib.LMI_MAX_K  # the longest list a re-rank takes (the 8-bit scan's longest)
+
+
+def check_rerank(index: DeviceIndex, rerank, k_list: int, dist: str) -> None:
+    """What Searcher.lists / search(..., rerank=k2) refuse, as a ValueError
+    before anything is launched: an index that is not of storage "i8" or keeps
+    no fp16 rows, dist="f32" (the re-ranked distances are float64), and k2
+    outside (k_list, 16]."""
+    if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
+        raise ValueError("rerank must be an integer (the entries of the 8-bit lists to re-rank)")
+    if getattr(index, "storage", None) != "i8":
+        raise ValueError(f"rerank: re-ranking is for storage 'i8', not {getattr(index, 'storage', None)!r}")
+    if getattr(index, "rows16", None) is None:
+        raise ValueError("rerank: this index keeps no fp16 rows (build it with keep_rows=True)")
+    if dist != "f64":
+        raise ValueError("rerank: the re-ranked distances are float64 (dist='f64'), not dist='f32'")
+    if not k_list < int(rerank) <= RERANK_MAX:
+        raise ValueError(f"rerank = {int(rerank)} must lie in (k_list, {RERANK_MAX}] = ({k_list}, {RERANK_MAX}]")
+
+
+def rerank_f64(index: DeviceIndex, q: torch.Tensor, pos: torch.Tensor, k: int, stream=None, out=None):
+    """Exact float64 distances for short candidate lists (lmi_rerank_f64): for
+    every (query, probe) the k smallest of pos's live candidates by (d64,
+    position), padded (+inf, -1); d64 from the index's kept fp16 rows (`rows16`;
+    an index of storage "f16" serves from its corpus), with the bits
+    lmi_bucket_topk_f64 gives that (query, row).  q: the float32 queries [nq, d];
+    pos: device int32 [nq, R, k_in] positions (bucket_topk's), -1 = empty
+    anywhere, 1 <= k <= k_in <= 16.  Returns (d float64 [nq, R, k], pos int32
+    [nq, R, k], status int32 tensor); `out`: such a triple to write into (the
+    status word is OR-ed into).  A position past the index's rows is skipped
+    and raises LMI_STATUS_INTERNAL in the status."""
+    lib = _lib.load()
+    if index.storage == "f16" and index.world == 1 and index.chunk_centroid is None:
+        desc = index.desc
+    else:
+        desc = index.rows_desc
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or pos.dim() != 3:
+        raise ValueError("rerank_f64: pos must be an int32 tensor [nq, R, k_in]")
+    nq, R, k_in = (int(v) for v in pos.shape)
+    if not 1 <= int(k) <= k_in <= RERANK_MAX:
+        raise ValueError(f"rerank_f64: need 1 <= k <= k_in <= {RERANK_MAX}, not k={k}, k_in={k_in}")
+    q = _rows_f32(q, index.device)  # (float64 queries are rounded, as the 8-bit scan rounds them)
+    if q.shape[0] != nq or q.shape[1] != index.d:
+        raise ValueError("rerank_f64: query shape does not match the lists or the index")
+    pos = pos.to(index.device).contiguous()
+    if out is None:
+        out = (torch.empty((nq, R, int(k)), dtype=torch.float64, device=index.device),
+               torch.empty((nq, R, int(k)), dtype=torch.int32, device=index.device),
+               torch.zeros((1,), dtype=torch.int32, device=index.device))
+    out_d, out_pos, status = out
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_rerank_f64", lib.lmi_rerank_f64(C.byref(desc), ptr(q), nq, q.stride(0), R, ptr(pos), k_in, int(k),
+                                               ptr(out_d), ptr(out_pos), ptr(status), s))
+    return out_d, out_pos, status
 
 
 def range_pack(index: DeviceIndex, count: torch.Tensor, cand: torch.Tensor, off: torch.Tensor, out,
@@ -1664,13 +1802,32 @@ class Searcher:
         return mode
 
     def _scan(self, q_search, classes, k_list: int, qmode: int, f64: bool, lap=None,
-              status_out=None, ws=None, seed_round0: bool = False, want=None):
+              status_out=None, ws=None, seed_round0: bool = False, want=None, rerank=None):
         """K2 on this shard (+ all-gather and K3 for G > 1 ranks, the status
         words riding along so every rank sees every rank's bits).  `lap`
         (measurement only) is called after the scan and after the exchange.
         `status_out` (a zeroed device int32 word): the status lands there.
         `ws`: a caller-owned scan workspace (GraphedSearch's).  `want`: the
-        want words of a filtered scan (want_words; float32 lists only)."""
+        want words of a filtered scan (want_words; float32 lists only).
+        `rerank` (checked by check_rerank; f64, one GPU): the 8-bit scan keeps
+        `rerank` entries a pair and rerank_f64 cuts them to k_list float64 ones."""
+        if rerank is not None:
+            st = status_out if status_out is not None else torch.zeros((1,), dtype=torch.int32,
+                                                                       device=self.index.device)
+            nq, R = classes.shape
+            scan_out = (torch.empty((nq, R, rerank), dtype=torch.float32, device=self.index.device),
+                        torch.empty((nq, R, rerank), dtype=torch.int32, device=self.index.device), st)
+            # (the over-fetch runs on the ring's 16-entry lists where the plan has them)
+            _, pos2, _ = bucket_topk(self.index, q_search, classes, rerank, qmode=qmode, out=scan_out, ws=ws,
+                                     want=want, lists16=True)
+            if lap:
+                lap("scan")
+            d, pos, status = rerank_f64(self.index, q_search, pos2, k_list, out=(
+                torch.empty((nq, R, k_list), dtype=torch.float64, device=self.index.device),
+                torch.empty((nq, R, k_list), dtype=torch.int32, device=self.index.device), st))
+            if lap:
+                lap("rerank")
+            return d, pos, status
         out = None
         if not self.exchange and status_out is not None:
             nq, R = classes.shape
@@ -1720,8 +1877,14 @@ class Searcher:
 
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
-              min_probes: int = 1, want=None, avoid=None):
+              min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
+        `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64",
+        k_list < k2 <= 16): the 8-bit scan keeps k2 entries a pair and their
+        float64 distances from the kept fp16 rows decide the k_list returned
+        (rerank_f64) -- exact distances on an approximate candidate set; with
+        `want` / `avoid` the k2 candidates are eligible rows.  ValueError
+        (check_rerank) before anything is launched otherwise.
         `stop_mass`, `min_probes`: the router's stop rule (DeviceRouter.topr);
         a dropped probe's list is (+inf, -1).  `want` (a tagged index; an int
         or an integer array [nq], words in [0, 2^32)): filtered lists -- each
@@ -1732,20 +1895,27 @@ class Searcher:
         ValueError, like every refusal of `want`, before anything is launched."""
         check_stop(stop_mass, min_probes)
         self.index._check_live()
-        self._check_i8_lists(k_list, dist)
+        self._check_i8_lists(k_list, dist, rerank)
         if want is not None or avoid is not None:
             nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-            want = filter_words(self.index, want, avoid, nq, k_list, dist)
+            # (re-ranked: the filtered scan is the float32 one of `rerank` entries)
+            want = filter_words(self.index, want, avoid, nq, *((k_list, dist) if rerank is None else
+                                                               (int(rerank), "f32")))
         if classes is None:
             classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
         d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
-                                    want=want)
+                                    want=want, rerank=None if rerank is None else int(rerank))
         return classes, d, pos, status
 
-    def _check_i8_lists(self, k_list: int, dist: str) -> None:
+    def _check_i8_lists(self, k_list: int, dist: str, rerank=None) -> None:
         """The lists an index of storage "i8" answers: float32, at most
-        LMI_MAX_K entries; ValueError otherwise, before anything is launched."""
+        LMI_MAX_K entries -- or, with `rerank`, float64 ones re-ranked from its
+        kept fp16 rows (check_rerank, on any index); ValueError otherwise,
+        before anything is launched."""
+        if rerank is not None:
+            check_rerank(self.index, rerank, k_list, dist)
+            return
         if self.index.storage == "i8":
             if dist != "f32":
                 check_i8(self.index, "dist='f64' (float64 lists)")
@@ -1994,8 +2164,13 @@ class Searcher:
                use_threshold: bool = True, classes: Optional[torch.Tensor] = None,
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
-               min_probes: int = 1, want=None, avoid=None):
+               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64"; as
+        in lists): the lists the merge or the replay reads are the k2-entry
+        8-bit lists re-ranked to float64 from the kept fp16 rows; everything
+        downstream runs as on float64 lists.  The scan is never seeded.
 
         `want` (a tagged index): filtered search -- only rows with
         (tag & want) == want answer.  semantics="exact" takes an int or an
@@ -2047,7 +2222,8 @@ class Searcher:
         if dist not in ("f32", "f64"):
             raise ValueError("dist must be 'f32' or 'f64'")
         k_list = k_round if semantics == "reference" else max(k_round, k)
-        self._check_i8_lists(k_list, dist)
+        self._check_i8_lists(k_list, dist, rerank)
+        rerank = None if rerank is None else int(rerank)
         f64 = dist == "f64"
         kmax = _lib.LMI_MAX_K_F64 if f64 else _lib.LMI_MAX_K_PASSES
         if k_list > kmax:
@@ -2058,7 +2234,9 @@ class Searcher:
         want_w = None
         if want is not None or avoid is not None:
             nq_w = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-            want_w = filter_words(self.index, want, avoid, nq_w, k_list, dist, per_query=semantics == "exact")
+            want_w = filter_words(self.index, want, avoid, nq_w, *((k_list, dist) if rerank is None else
+                                                                   (rerank, "f32")),
+                                  per_query=semantics == "exact")
         sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
 
         def lap(name, t0):
@@ -2098,7 +2276,7 @@ class Searcher:
                 and want_w is None)
         d, pos, status = self._scan(q_search, classes, k_list, qmode, f64, lap_at if sync else None,
                                     status_out=None if ans is None else ans[3][0:1],
-                                    seed_round0=seed, want=want_w)
+                                    seed_round0=seed, want=want_w, rerank=rerank)
         # (filtered: the replay's bucket sizes are the eligible row counts)
         bsize = self.index.bucket_size
         if want_w is not None and semantics == "reference":
@@ -2137,7 +2315,8 @@ class Searcher:
             t0 = lap("d2h", t0)
             if check_status(int(h_st[0])):
                 # the cached fp16 check was stale: redo with exact fp32 MFMA
-                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64, want=want_w)
+                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64, want=want_w,
+                                            rerank=rerank)
                 rd, ra = exact(d, pos)
                 h_d.copy_(rd)
                 h_a.copy_(ra)
@@ -2168,7 +2347,8 @@ class Searcher:
             if check_status(st0, st1):
                 ans = answer_buffer(nq, w_ans, dev)
                 d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                            status_out=ans[3][0:1], seed_round0=seed, want=want_w)
+                                            status_out=ans[3][0:1], seed_round0=seed, want=want_w,
+                                            rerank=rerank)
                 h = run_replay(d, pos, ans)
                 torch.cuda.current_stream(dev).synchronize()
                 hd, ha, st0, st1 = answer_views(h, nq, w_ans)
@@ -2185,7 +2365,7 @@ class Searcher:
         t0 = lap("d2h", t0)
         if check_status(int(h_st[0])):
             d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                        seed_round0=seed, want=want_w)
+                                        seed_round0=seed, want=want_w, rerank=rerank)
             h_d.copy_(d)
             h_pos.copy_(pos)
             h_st[0:1].copy_(status)
