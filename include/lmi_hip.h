@@ -281,6 +281,55 @@ int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_t nq, int32
                     float* out_d, int32_t* out_pos, int32_t* status,
                     void* workspace, size_t ws_bytes, void* stream);
 
+/* K2 by another metric: lmi_bucket_topk with the distance of every (query, row)
+ * pair taken from the same accumulator acc = sum_j q_j y_j by another rule.
+ *   LMI_METRIC_COSINE  d = 1 - acc / (|q| |y|): lmi_bucket_topk itself, every bit.
+ *   LMI_METRIC_IP      d = -acc (largest inner products first: smaller is
+ *                      better, so the lists stay ascending).  No per-row word:
+ *                      idx->inv_norm may be null.
+ *   LMI_METRIC_L2      d = fmaf(-2, acc, qq + yy), the squared Euclidean
+ *                      distance.  yy = |y|^2 of every stored row, accumulated in
+ *                      float64 over the stored values and rounded once to
+ *                      float32 (lmi_row_sqnorms): idx->inv_norm names that array.
+ *                      qq = |q|^2 the same way, inside the call, by the same
+ *                      device function.  qq + yy is one float32 addition.  The
+ *                      value may come out slightly negative for a row equal to
+ *                      the query and is not clamped: the (distance, position)
+ *                      order is a function of the expression alone.
+ * Queries are not normalised.  Arguments, outputs, status bits and the
+ * PLAN / SCAN / MERGE phase flags are lmi_bucket_topk's; the workspace is
+ * lmi_scan_metric_workspace_bytes, which equals lmi_scan_workspace_bytes
+ * wherever both plans pick the same kernel family -- every shape but d_pad ==
+ * 768 with an fp16 corpus, LMI_Q_F16 and k = 11..16, which the cosine plan
+ * gives to the rings' 15- and 16-entry lists and this one to the general
+ * kernel.  The kernels are scan3_kernel MODE 5 / 6 (d_pad == 768, fp16 corpus,
+ * LMI_Q_F16, k <= 10) and scan_kernel_metric (everything else).
+ * LMI_E_INVALID (lmi_last_error names the metric) before any launch, device or
+ * no device, for what a metric other than cosine does not offer: an unknown
+ * metric; LMI_I8 / LMI_Q_I8; idx->corpus32 or corpus64; idx->chunk_centroid;
+ * k outside [1, LMI_MAX_K]; LMI_Q_SEED_ROUND0, LMI_Q_PHASE_SCAN_JOIN or
+ * LMI_Q_PHASE_REFINE; d_pad > 992.  The tagged, range, float64 and re-rank
+ * entries take cosine indexes alone. */
+#define LMI_METRIC_COSINE 0
+#define LMI_METRIC_L2 1
+#define LMI_METRIC_IP 2
+size_t lmi_scan_metric_workspace_bytes(const lmi_index_desc* idx, int32_t metric, int32_t nq, int32_t R,
+                                       int32_t k, int32_t qmode);
+int lmi_bucket_topk_metric(const lmi_index_desc* idx, int32_t metric, const float* q, int32_t nq,
+                           int32_t ldq, const int32_t* classes, int32_t R, int32_t k, int32_t qmode,
+                           float* out_d, int32_t* out_pos, int32_t* status, void* workspace,
+                           size_t ws_bytes, void* stream);
+
+/* The per-row word of LMI_METRIC_L2: sqnorm[t] = sum_j rows[i][j]^2 over j < d,
+ * accumulated in float64 and rounded once to float32, t = dst_rows ? dst_rows[i]
+ * : i (an index build scatters each block into its bucket-sorted slots).  One
+ * wave a row, 16-byte loads where every row starts on a 16-byte boundary.
+ *   rows  device [m][ld] fp16 or float32 (dtype LMI_F16 / LMI_F32), ld >= d
+ * Slots are the caller's to keep in range.  LMI_E_INVALID before any launch: a
+ * dtype other than LMI_F16 / LMI_F32, m < 0, d < 1, ld < d, a null pointer (m > 0). */
+int lmi_row_sqnorms(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, int64_t m, int64_t ld, int32_t d,
+                    const int64_t* dst_rows /*nullable*/, float* sqnorm, void* stream);
+
 /* K2 tagged: lmi_bucket_topk with a predicate tested inside the scan.  Every
  * stored row carries a 32-bit tag word, every query a 32-bit want word; a row
  * is eligible for a query iff (tag & want) == want (all-of; want == 0 accepts

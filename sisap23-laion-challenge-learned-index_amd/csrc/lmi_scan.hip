@@ -878,7 +878,7 @@ int split_parts() {
     return std::max(2, std::min(kSplitMaxParts, env_config().scan_split_parts));
 }
 
-ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo, bool tagged) {
+ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo, bool tagged, int metric) {
     ScanPlan w{};
     w.f16math = (idx->dtype == LMI_F16) && (qmode == LMI_Q_F16);
     w.i8 = (idx->dtype == LMI_I8) && (qmode == LMI_Q_I8);
@@ -889,7 +889,9 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     // (tagged: the 8-wave ring's 10-entry lists or the general kernel)
     const bool ring4 = w.f16math && idx->d_pad == v2::D && !env_config().scan_v1;
     const bool ring8 = ring4 && !env_config().scan_v2;
-    w.kl = k <= 10 ? 10 : (k <= 15 && ring8 && !tagged) ? 15 : 16;
+    // (a metric other than cosine has the 8-wave ring's 10-entry lists alone:
+    // its k = 11..16 at d_pad 768 go to the general kernel's 16-entry lists)
+    w.kl = k <= 10 ? 10 : (k <= 15 && ring8 && !tagged && metric == LMI_METRIC_COSINE) ? 15 : 16;
     // (the 8-bit storage has a ring of its own at the same width, plain and
     // tagged: 10-entry lists, and 16-entry ones for the threads that asked
     // for them -- lmi_scan_set_i8_lists16, the over-fetch of a re-rank; by
@@ -899,7 +901,7 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
                          !env_config().scan_v1;
     w.family = ring8i8 ? ScanKernel::Ring8I8
                : ring8 && w.kl != 16 ? ScanKernel::Ring8
-               : ring4 && !lo && !tagged ? ScanKernel::Ring4 : ScanKernel::General;
+               : ring4 && !lo && !tagged && metric == LMI_METRIC_COSINE ? ScanKernel::Ring4 : ScanKernel::General;
     const bool v3 = w.family == ScanKernel::Ring8;
     w.qb = v3 || ring8i8 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
     const size_t P = (size_t)nq * R;
@@ -963,6 +965,31 @@ int i8_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t qmode)
     LMI_CHECK_ARG(!idx->chunk_centroid, "%s: LMI_I8 takes no sub-cluster layout (chunk_centroid)", fn);
     LMI_CHECK_ARG(idx->d_pad >= 32 && idx->d_pad % 32 == 0 && idx->d_pad <= kI8MaxDPad,
                   "%s: LMI_I8 takes d_pad a multiple of 32 up to %d, not %d", fn, kI8MaxDPad, idx->d_pad);
+    return LMI_OK;
+}
+
+const char* metric_name(int32_t metric) {
+    return metric == LMI_METRIC_COSINE ? "cosine" : metric == LMI_METRIC_L2 ? "l2" : metric == LMI_METRIC_IP ? "ip" : "?";
+}
+
+int metric_gate(const char* fn, const lmi_index_desc* idx, int32_t metric, int32_t k, int32_t qmode) {
+    LMI_CHECK_ARG(metric == LMI_METRIC_COSINE || metric == LMI_METRIC_L2 || metric == LMI_METRIC_IP,
+                  "%s: unknown metric %d (LMI_METRIC_COSINE, LMI_METRIC_L2 or LMI_METRIC_IP)", fn, metric);
+    if (metric == LMI_METRIC_COSINE) return LMI_OK;
+    const char* m = metric_name(metric);
+    LMI_CHECK_ARG(idx != nullptr, "%s: metric %s: null index", fn, m);
+    const int32_t base = qmode & ~(LMI_Q_SEED_ROUND0 | (7 << 9) | LMI_Q_PHASE_SCAN_JOIN | LMI_Q_PHASE_REFINE);
+    LMI_CHECK_ARG(idx->dtype != LMI_I8 && base != LMI_Q_I8,
+                  "%s: metric %s is not offered on the 8-bit storage (LMI_I8 / LMI_Q_I8)", fn, m);
+    LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
+                  "%s: metric %s takes no split mode and no float64 rows (corpus32 / corpus64)", fn, m);
+    LMI_CHECK_ARG(!idx->chunk_centroid, "%s: metric %s takes no sub-cluster layout (chunk_centroid)", fn, m);
+    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: metric %s takes k in [1, %d], not %d", fn, m, LMI_MAX_K, k);
+    LMI_CHECK_ARG(!(qmode & LMI_Q_SEED_ROUND0), "%s: metric %s is never seeded (LMI_Q_SEED_ROUND0)", fn, m);
+    LMI_CHECK_ARG(!(qmode & (LMI_Q_PHASE_SCAN_JOIN | LMI_Q_PHASE_REFINE)),
+                  "%s: metric %s takes no join workgroups and no refine phase (LMI_Q_PHASE_SCAN_JOIN / _REFINE)", fn, m);
+    LMI_CHECK_ARG(idx->d_pad >= 32 && idx->d_pad % 32 == 0 && idx->d_pad <= kMetricMaxDPad,
+                  "%s: metric %s takes d_pad a multiple of 32 up to %d, not %d", fn, m, kMetricMaxDPad, idx->d_pad);
     return LMI_OK;
 }
 
@@ -1067,6 +1094,25 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     const int kl = p.kl, mode = c.wide ? c.wide->mode : 0;
     const bool lo = c.lo_g != nullptr, band = c.out_bound != nullptr, corpus_f16 = c.idx->dtype == LMI_F16;
     const bool plain = mode == 0 && !lo && !band;
+    if (c.metric != LMI_METRIC_COSINE) {
+        // plain lists alone: the 8-wave ring's 10-entry lists, the
+        // general kernel's 10 and 16 in the three (math, corpus) classes
+        if (!plain || p.i8 || c.tags != nullptr || c.range != nullptr) return {nullptr, nullptr};
+        const bool l2 = c.metric == LMI_METRIC_L2;
+#define LMI_PICK_M(...) (l2 ? __VA_ARGS__, LMI_METRIC_L2> : __VA_ARGS__, LMI_METRIC_IP>)
+        if (p.family == ScanKernel::Ring8)
+            return {kl == 10 ? LMI_PICK_M(launch_scan3_metric<10) : nullptr, nullptr};
+        if (p.family != ScanKernel::General) return {nullptr, nullptr};
+        if (p.f16math)
+            return {nullptr, kl == 10 ? LMI_PICK_M(launch_scan_metric<10, true, _Float16)
+                                      : LMI_PICK_M(launch_scan_metric<16, true, _Float16)};
+        if (corpus_f16)
+            return {nullptr, kl == 10 ? LMI_PICK_M(launch_scan_metric<10, false, _Float16)
+                                      : LMI_PICK_M(launch_scan_metric<16, false, _Float16)};
+        return {nullptr, kl == 10 ? LMI_PICK_M(launch_scan_metric<10, false, float)
+                                  : LMI_PICK_M(launch_scan_metric<16, false, float)};
+#undef LMI_PICK_M
+    }
     if (p.i8) {
         // the 8-bit scan: plain or tagged lists, nothing else
         if (!plain) return {nullptr, nullptr};
@@ -1194,6 +1240,36 @@ extern "C" int lmi_bucket_topk(const lmi_index_desc* idx, const float* q, int32_
     return k <= LMI_MAX_K ? bucket_topk_impl(c) : bucket_topk_wide_k(c);
 }
 
+extern "C" size_t lmi_scan_metric_workspace_bytes(const lmi_index_desc* idx, int32_t metric, int32_t nq,
+                                                  int32_t R, int32_t k, int32_t qmode) {
+    using namespace lmi;
+    if (metric == LMI_METRIC_COSINE) return lmi_scan_workspace_bytes(idx, nq, R, k, qmode);
+    if (metric_gate("lmi_scan_metric_workspace_bytes", idx, metric, k, qmode) != LMI_OK) return 0;
+    take_phases(qmode);
+    if (nq < 0 || R < 1 || (qmode != LMI_Q_F16 && qmode != LMI_Q_F32)) return 0;
+    return scan_plan(idx, nq, R, k, qmode, false, false, metric).total;
+}
+
+extern "C" int lmi_bucket_topk_metric(const lmi_index_desc* idx, int32_t metric, const float* q, int32_t nq,
+                                      int32_t ldq, const int32_t* classes, int32_t R, int32_t k, int32_t qmode,
+                                      float* out_d, int32_t* out_pos, int32_t* status, void* workspace,
+                                      size_t ws_bytes, void* stream) {
+    using namespace lmi;
+    // (every refusal comes before any launch and needs no device)
+    LMI_TRY(metric_gate("lmi_bucket_topk_metric", idx, metric, k, qmode));
+    if (metric == LMI_METRIC_COSINE)
+        return lmi_bucket_topk(idx, q, nq, ldq, classes, R, k, qmode, out_d, out_pos, status, workspace, ws_bytes,
+                               stream);
+    const int phases = take_phases(qmode);
+    const ScanCall c{.idx = idx, .q = q, .nq = nq, .ldq = ldq, .classes = classes, .R = R, .k = k,
+                     .qmode = qmode, .out_d = out_d, .out_pos = out_pos, .status = status,
+                     .workspace = workspace, .ws_bytes = ws_bytes,
+                     .stream = reinterpret_cast<hipStream_t>(stream), .phases = phases, .metric = metric};
+    // (with join workgroups set on this thread bucket_topk_impl refuses a scan
+    // phase: the metric scans run in one launch)
+    return bucket_topk_impl(c);
+}
+
 extern "C" size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R,
                                                   int32_t k, int32_t qmode) {
     using namespace lmi;
@@ -1286,6 +1362,13 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
                                            c.range == nullptr && !(c.phases & kPhaseJoin)),
                   "LMI_I8 takes plain and tagged lists alone (no lower bounds, wide scans, band lists, range "
                   "scan or join phase)");
+    // (a metric other than cosine: the entry's checks again, and plain lists alone)
+    LMI_TRY(metric_gate("bucket_topk", idx, c.metric, k, qmode | (c.seed_r0 ? LMI_Q_SEED_ROUND0 : 0)));
+    const bool metric = c.metric != LMI_METRIC_COSINE;
+    LMI_CHECK_ARG(!metric || (c.lo_g == nullptr && c.wide == nullptr && c.out_bound == nullptr &&
+                              c.range == nullptr && c.tags == nullptr && !(c.phases & kPhaseJoin)),
+                  "metric %s takes plain lists alone (no tags, lower bounds, wide scans, band lists, range scan "
+                  "or join phase)", metric_name(c.metric));
     LMI_CHECK_ARG(idx->d >= 1 && idx->d_pad >= idx->d && idx->d_pad % 32 == 0, "bad d/d_pad");
     LMI_CHECK_ARG(idx->n_buckets >= 1, "n_buckets < 1");
     LMI_CHECK_ARG(idx->chunk_rows >= 32 && idx->chunk_rows % 32 == 0, "chunk_rows must be a multiple of 32");
@@ -1296,12 +1379,15 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     LMI_CHECK_ARG(ldq >= idx->d, "ldq < d");
     if (nq == 0) return LMI_OK;
     LMI_CHECK_ARG(c.q && classes && out_d && out_pos && status && c.workspace, "null pointer");
-    LMI_CHECK_ARG(idx->n_rows == 0 || (idx->corpus && idx->inv_norm && idx->gpos), "null corpus arrays");
+    // (metric ip reads no per-row word)
+    LMI_CHECK_ARG(idx->n_rows == 0 || (idx->corpus && (idx->inv_norm || c.metric == LMI_METRIC_IP) && idx->gpos),
+                  "null corpus arrays");
     LMI_CHECK_ARG(idx->bucket_off && idx->chunk_first, "null bucket tables");
 
     LMI_CHECK_ARG((c.tags != nullptr) == (c.want != nullptr) && (c.tags != nullptr) == (c.mask != nullptr),
                   "tags, value and mask come together");
-    const ScanPlan w = c.plan ? *c.plan : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr, c.tags != nullptr);
+    const ScanPlan w = c.plan ? *c.plan
+                              : scan_plan(idx, nq, R, k, qmode, lo_g != nullptr, c.tags != nullptr, c.metric);
     if (c.ws_bytes < w.total) {
         set_error("workspace %zu B < required %zu B", c.ws_bytes, w.total);
         return LMI_E_WORKSPACE;
@@ -1326,7 +1412,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     int phases = c.phases;
     {
         bool done;
-        LMI_TRY(join_gate(phases, v3 && wide == nullptr && lo_g == nullptr && c.tags == nullptr, &done));
+        LMI_TRY(join_gate(phases, v3 && wide == nullptr && lo_g == nullptr && c.tags == nullptr && !metric, &done));
         if (done) return LMI_OK;
     }
     const bool do_plan = phases & kPhasePlan, do_scan = phases & kPhaseScan, do_merge = phases & kPhaseMerge;
@@ -1366,6 +1452,19 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
                            ldq, idx->d, idx->d_pad, (int8_t*)(ws + w.qbuf), (float*)(ws + w.invq), out_d, out_pos,
                            out_row, c.prefill ? R * ldo : 0, fills);
         LMI_LAUNCH_CHECK("prep_i8_kernel");
+    } else if (do_plan && metric) {
+        // (prep_kernel's PrepFills stays this unit's own type: it is part of
+        // the existing prep kernels' symbols)
+        WordFills wf{};
+        wf.n = fills.n;
+        for (int f = 0; f < fills.n; ++f) {
+            wf.p[f] = fills.p[f];
+            wf.v[f] = fills.v[f];
+            wf.per_q[f] = fills.per_q[f];
+        }
+        LMI_TRY(launch_prep_metric(w.f16math, c.q, nq, ldq, idx->d, idx->d_pad, c.metric, ws + w.qbuf,
+                                   (float*)(ws + w.invq), status, out_d, out_pos, out_row,
+                                   c.prefill ? R * ldo : 0, wf, s));
     } else if (do_plan) {
         const dim3 pg((nq + kThreads / 64 - 1) / (kThreads / 64));
         const bool vec = ((uintptr_t)c.q % 16 == 0) && (ldq % 4 == 0);

@@ -4,6 +4,7 @@
 // DESIGN.md §3 / §5 measure).  Each includer gets its own internal copy.
 #pragma once
 #include "lmi_scan_internal.hpp"
+#include "lmi_metric.hpp"
 
 namespace lmi {
 namespace {
@@ -367,10 +368,23 @@ __device__ __forceinline__ uint32_t opaque_u(uint32_t x) {
 // into `ok` -- spilled a query fragment into the stream).
 // Bounds, the thr_g atomicMin, the 32-block bound exchange, the tail handling
 // and the lists are MODE 0's; never seeded; invq holds (1/|q|, value, mask) triples.
+//
+// MODE 5 / 6 (lmi_bucket_topk_metric, instantiated in lmi_scan_metric.hip): MODE
+// 0, the product scan, with the distance of LMI_METRIC_L2 / LMI_METRIC_IP taken from the same accumulators, one
+// fma per register as for the cosine.  l2: the row-word area the ring brings
+// beside each 32-row block carries |y|^2 (idx->inv_norm names it), the pair's
+// word is |q|^2, d = fmaf(-2, acc, qq + yy).  ip: d = -acc needs neither word,
+// so that instantiation issues no row-word DMA at all (every wait in the block
+// loop is a vmcnt(0), so dropping the pieces needs no count changed) and reads
+// no word area in the filter or the walk.  Distances may be negative: the
+// keys' order-preserving image (f2ord) and the dead slots' bound (-inf) hold
+// for them.  The walk, the bound exchange, the lists and `partial` are MODE 0's.
 template <int KL, int ABL = 0, bool LO = false, int MODE = 0>
 __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     using namespace v3;
-    static_assert(MODE == 0 || (ABL == 0 && !LO), "the wide modes are product variants");
+    constexpr int METRIC = MODE == 5 ? LMI_METRIC_L2 : MODE == 6 ? LMI_METRIC_IP : LMI_METRIC_COSINE;
+    constexpr bool kPlain = MODE == 0 || MODE == 5 || MODE == 6;  // plain lists (MODE 0's paths)
+    static_assert(MODE == 0 || (ABL == 0 && !LO), "the wide modes and the metric scans are product variants");
     static_assert(MODE != 3 || KL == 10, "band lists are built from 10-entry lane lists");
     static_assert(MODE != 4 || KL == 10, "the tagged scan has 10-entry lists");
     // diagnostic builds only (results wrong for ABL != 0): 1 no insertion,
@@ -392,7 +406,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
     constexpr bool kNoIns = ABL == 1 || ABL == 4;
     constexpr bool kNoBar = ABL == 6 || ABL == 66 || ABL == 21 || ABL == 69 || ABL == 70;
     // bound exchange period in blocks (diagnostic: 40 none, 41 every 4, 42 every 8, 43 every 16)
-    constexpr int kXch = (ABL == 40 || (MODE != 0 && MODE != 4)) ? 0 : ABL == 41 ? 4 : ABL == 42 ? 8 : ABL == 43 ? 16 : 32;
+    constexpr int kXch = (ABL == 40 || (!kPlain && MODE != 4)) ? 0 : ABL == 41 ? 4 : ABL == 42 ? 8 : ABL == 43 ? 16 : 32;
     // (ABL 53, round 1's placement: an LDS-DMA issue holds its wave for ~45-60
     // cycles, so the two waves of a SIMD issued theirs at different MFMAs)
     constexpr int kDmaTT = 2, kDmaLate = 10;
@@ -545,7 +559,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                                                              4, vo, b * 128, 0, 0);
                 }
             } else
-            if (j == NST - 1 && lane < 4)
+            if (METRIC != LMI_METRIC_IP && j == NST - 1 && lane < 4)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rn, (lds_t)(ring + nb_area * STAGE + NORM_OFF + 16 * w),
                                                          4, (uint32_t)((4 * w + opaque(lane)) * 4), b * 128, 0, 0);
         };
@@ -606,7 +620,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                 my_invq = live ? __uint_as_float(iw[0]) : 0.0f;
                 const uint64_t vm = live ? ((uint64_t)iw[2] << 32) | iw[1] : 0ull;
                 lds_put_u64_at<0>((uint32_t)(uintptr_t)(tag_area + TAG_AREA + wave * 256) + (uint32_t)col * 8u, vm);
-            } else
+            } else if constexpr (METRIC != LMI_METRIC_IP)  // (cosine: 1/|q|; l2: |q|^2)
             my_invq = live ? a.invq[q] : 0.0f;
             if constexpr (MODE == 1) {
                 // (no bound until every bin holds a finished list's 15th)
@@ -659,11 +673,12 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
             auto filter = [&]<bool TAIL>() {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const f32x4 n4 = *reinterpret_cast<const f32x4*>(nb + 32 * g);
+                    f32x4 n4 = {};
+                    if constexpr (METRIC != LMI_METRIC_IP) n4 = *reinterpret_cast<const f32x4*>(nb + 32 * g);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int reg = 4 * g + e;
-                        const float d = fmaf(-acc[reg], my_invq * n4[e], 1.0f);
+                        const float d = metric_dist<METRIC>(acc[reg], my_invq, n4[e]);
             
                         // (LO: lo_d <= d <= bound as one med3 and one compare)
                         bool ok = LO ? __builtin_amdgcn_fmed3f(d, lo_d, bound) == d : d <= bound;
@@ -751,8 +766,9 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                             m ^= 1u << hb;
                             const int rg = 15 - hb;
                             const int i = (rg & 3) + 8 * (rg >> 2);
-                            const float n1 = *reinterpret_cast<const float*>(nb + i * 4);
-                            const float d = fmaf(-select16(acc, rg), my_invq * n1, 1.0f);
+                            float n1 = 0.0f;
+                            if constexpr (METRIC != LMI_METRIC_IP) n1 = *reinterpret_cast<const float*>(nb + i * 4);
+                            const float d = metric_dist<METRIC>(select16(acc, rg), my_invq, n1);
                             key = make_key(d, rb + (uint32_t)i);
                             // (at or before the pair's lower bound: not this pass's)
                             if (LO && d == lo_d && eb * 32 + 4 * hh + i < lo_row) key = kEmptyKey;
@@ -800,8 +816,9 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
                         m ^= 1u << hb;
                         const int rg = 15 - hb;
                         const int i = (rg & 3) + 8 * (rg >> 2);
-                        const float n1 = *reinterpret_cast<const float*>(nb + i * 4);
-                        const float d = fmaf(-select16(acc, rg), my_invq * n1, 1.0f);
+                        float n1 = 0.0f;
+                        if constexpr (METRIC != LMI_METRIC_IP) n1 = *reinterpret_cast<const float*>(nb + i * 4);
+                        const float d = metric_dist<METRIC>(select16(acc, rg), my_invq, n1);
                         const uint64_t key = make_key(d, rb + (uint32_t)i);
                         // (MODE 4) the candidate's tag word and the pair's value
                         // and mask words, all from LDS at addresses made here from the
@@ -1023,7 +1040,7 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
             uint64_t* out = LMI_KARG(partial) + ((size_t)pp * a.max_chunks + tile.chunk) * KL;
 #pragma unroll
             for (int i = 0; i < KL; ++i) out[i] = L[i];
-            if ((MODE == 0 || MODE == 4) && L[KL - 1] != kEmptyKey) atomicMin(&a.thr_g[pp], (unsigned long long)L[KL - 1]);
+            if ((kPlain || MODE == 4) && L[KL - 1] != kEmptyKey) atomicMin(&a.thr_g[pp], (unsigned long long)L[KL - 1]);
             if (MODE == 1 && L[KL - 1] != kEmptyKey)
                 atomicMin(&a.bins[(size_t)pp * a.nbins + tile.chunk % a.nbins], (uint32_t)(L[KL - 1] >> 32));
         }

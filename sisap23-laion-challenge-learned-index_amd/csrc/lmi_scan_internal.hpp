@@ -214,6 +214,28 @@ template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
 int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s);
 template <int KL>
 int launch_scan2(const Scan2Args& b, hipStream_t s);
+// scan_kernel_metric (LMI_METRIC_L2 / _IP: plain lists, KL 10 / 16, the three
+// (math, corpus) classes of launch_scan); the widest row is the general
+// kernel's at fp16 math (its query tile in LDS)
+template <int KL, bool F16MATH, typename TC, int METRIC>
+int launch_scan_metric(const ScanArgs& a, int d_pad, hipStream_t s);
+constexpr int kMetricMaxDPad = 992;
+// scan3_kernel MODE 5 / 6 (the 8-wave ring's plain 10-entry lists)
+template <int KL, int METRIC>
+int launch_scan3_metric(const Scan2Args& b, hipStream_t s);
+// prep_metric_kernel: the queries rounded to qbuf (f16: fp16, the status bit
+// for a value that is not), invq = |q|^2 (l2) or untouched (ip), the output
+// prefill and bucket_topk_impl's word fills (copied field by field from its
+// PrepFills, a type of lmi_scan.hip's own that names the existing prep kernels)
+struct WordFills {
+    uint32_t* p[5];
+    uint32_t v[5];
+    int32_t per_q[5];
+    int32_t n;
+};
+int launch_prep_metric(bool f16, const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t d_pad, int32_t metric,
+                       void* qbuf, float* invq, int32_t* status, float* out_d, int32_t* out_pos, int32_t* out_row,
+                       int32_t out_per_q, const WordFills& fills, hipStream_t s);
 // scan_i8_kernel (8-bit storage: int8 corpus, int8 qbuf; KL 10 / 16, plain or TAG)
 template <int KL, bool TAG>
 int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s);
@@ -256,8 +278,16 @@ struct ScanPlan {
 };
 // tagged: the plan of lmi_bucket_topk_tagged -- the untagged plan but that the
 // 4-wave ring's and the 8-wave ring's 15-entry shapes go to the general kernel
+// metric (LMI_METRIC_*): the cosine plan of the same call -- the same family,
+// list length and workspace -- but that the 8-wave ring's 15-entry lists and
+// the 4-wave ring's shape (k = 11..16 at d_pad 768, fp16 math) go to the
+// general kernel's 16-entry lists, which have the metric variants
 ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, bool lo = false,
-                   bool tagged = false);
+                   bool tagged = false, int metric = LMI_METRIC_COSINE);
+// The refusals of a metric other than cosine (lmi_bucket_topk_metric), before
+// any launch and with no device; `qmode` as the caller gave it (flags included)
+int metric_gate(const char* fn, const lmi_index_desc* idx, int32_t metric, int32_t k, int32_t qmode);
+const char* metric_name(int32_t metric);
 // The 8-bit storage's refusals, before any launch and with no device.
 // i8_gate: a call of lmi_bucket_topk / _masked with `qmode` as the caller gave
 // it (flags included) -- LMI_OK off the 8-bit storage, else LMI_I8 and LMI_Q_I8
@@ -384,6 +414,9 @@ struct ScanCall {
     // K11 range search: the general kernel's collect form in place of the list
     // scan (a plan of the general family, phases plan + scan, no prefill)
     const RangeScan* range = nullptr;
+    // LMI_METRIC_*: plain lists by squared Euclidean distance or inner product
+    // (idx->inv_norm: |y|^2 / unused); none of the options above but phases
+    int32_t metric = LMI_METRIC_COSINE;
 };
 int bucket_topk_impl(const ScanCall& c);
 // the masked entries' host copies of their words (both or neither; null: not

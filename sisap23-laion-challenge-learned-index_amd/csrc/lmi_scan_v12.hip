@@ -96,7 +96,10 @@ __device__ inline void tile_epilogue(const f32x16& acc, uint64_t (&L)[KL], uint6
                                    (unsigned long long)L[KL - 1]);
 }
 
-// Kept in lock-step: a copy of this kernel's query staging and MFMA loop lives in
+// Kept in lock-step: a second copy of this kernel, whole but for the epilogue
+// and the LO / TAG words, is scan_kernel_metric (lmi_scan_metric.hip: the l2 /
+// ip scans; sharing the body as a device function changed this kernel's
+// code); a copy of this kernel's query staging and MFMA loop lives in
 // range_scan_kernel (lmi_range.hip), the collect form the range search runs,
 // and of tile_epilogue's distance expression in its epilogue.  The range
 // search promises the distance bits of these lists (test_gpu_range.py's

@@ -18,7 +18,14 @@ from .Logger import Logger
 
 
 class Baseline(Logger):
-    def __init__(self):
+    def __init__(self, metric="cosine"):
+        """`metric` (an addition; the reference scores by cosine alone):
+        "l2" answers the squared Euclidean distances, "ip" the negated inner
+        products (DeviceIndex's `metric`), float32 lists of k <= 16."""
+        from .index import METRICS
+        if metric not in METRICS:
+            raise ValueError(f"metric must be 'cosine', 'l2' or 'ip', not {metric!r}")
+        self.metric = metric
         self._index = None
         self._key = None
 
@@ -29,12 +36,12 @@ class Baseline(Logger):
         key = content_key(data)
         if self._index is None or self._key != key:
             n = np.shape(data)[0]
-            self._index = DeviceIndex(data, np.zeros(n, np.int64), 1)
+            self._index = DeviceIndex(data, np.zeros(n, np.int64), 1, metric=self.metric)
             self._key = key
         ix = self._index
         q = _upload_queries(queries, ix.device)
         classes = torch.zeros((q.shape[0], 1), dtype=torch.int32, device=ix.device)
-        dist = dist_dtype(data, queries)
+        dist = dist_dtype(data, queries) if self.metric == "cosine" else "f32"
         _, d, pos, st = Searcher(ix, None, exchange=False).lists(None, q, 1, k, classes=classes, dist=dist)
         if int(st.item()) & _lib.LMI_STATUS_INTERNAL:
             raise RuntimeError(f"Baseline.search: scan status {int(st.item())}")

@@ -202,7 +202,7 @@ class LearnedIndex(Logger):
                 and t[0] == self._identity(data_navigation, data_search, labels))
 
     def attach(self, data_navigation, data_search, pred_categories, capacity=None, tags=None, storage=None,
-               keep_rows=False, rerank=None):
+               keep_rows=False, rerank=None, metric=None):
         """Build the HBM index of data_search (rows in data_navigation's id
         order, bucket labels `pred_categories`) now, outside any timed call,
         and trust these objects: later search / search_single calls that pass
@@ -225,7 +225,24 @@ class LearnedIndex(Logger):
         the float64 distances of the kept rows (Searcher.search's `rerank`):
         exact float64 distances on an approximate candidate set.  ValueError
         before anything is built for a `rerank` without those two, or outside
-        that range."""
+        that range.  `metric` (an addition; default None: DeviceIndex's
+        "cosine", the reference's distance): "l2" or "ip" -- search and
+        search_single then answer float32 squared Euclidean distances or
+        negated inner products of the rows and queries as given (DeviceIndex's
+        `metric`; the router still sees the navigation vectors).  ValueError
+        naming the metric, before anything is built, with `capacity`, `tags`,
+        `keep_rows`, `rerank`, storage "i8" / "f32x" or a process group of
+        several ranks; range_search, insert, delete and rebucket refuse such
+        an index.  The reference replay pads with distance 10000, so
+        semantics="reference" is the reference's while every distance stays
+        below 10000 (always for "ip" rows with |<q, y>| < 10000)."""
+        if metric is not None:
+            from .index import _check_metric_build, check_metric
+            pg = self._proc_group()
+            _check_metric_build(metric, "auto" if storage is None else storage, False, capacity,
+                                1 if pg is None else pg[2], tags, keep_rows)
+            if rerank is not None:
+                check_metric(metric, "rerank")
         if rerank is not None:
             if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
                 raise ValueError("rerank must be an integer")
@@ -237,7 +254,7 @@ class LearnedIndex(Logger):
         self._trusted = None
         self._cat_written = None
         self._device_index(data_navigation, data_search, pred_categories, capacity=capacity, tags=tags,
-                           storage=storage, keep_rows=keep_rows)
+                           storage=storage, keep_rows=keep_rows, metric=metric)
         self._rerank = None if rerank is None else int(rerank)
         # strong references to the trusted objects: while they are held, their
         # id()s and buffers cannot be reused by new objects
@@ -252,7 +269,7 @@ class LearnedIndex(Logger):
         self._cat_written = None
 
     def _device_index(self, data_navigation, data_search, labels, capacity=None, tags=None, storage=None,
-                      keep_rows=False):
+                      keep_rows=False, metric=None):
         """DeviceIndex of data_search rows in data_navigation order (with a
         store of at least `capacity` rows when given; with `tags` a tagged
         one -- a call without `tags` reuses the cached index, tagged or not)."""
@@ -260,7 +277,8 @@ class LearnedIndex(Logger):
         # (a call without `storage` reuses the cached index whatever its storage)
         fits = lambda ix: (capacity is None or ix.capacity >= int(capacity)) and \
             (storage is None or storage == "auto" or ix.storage == storage) and \
-            (not keep_rows or ix.rows16 is not None)
+            (not keep_rows or ix.rows16 is not None) and \
+            (metric is None or ix.metric == metric)  # (a call without `metric` reuses the cached index)
         if self._is_attached(data_navigation, data_search, labels) and fits(self._index):
             return self._index
         labels = np.asarray(labels).astype(np.int64)
@@ -294,6 +312,8 @@ class LearnedIndex(Logger):
             shard["storage"] = storage
         if keep_rows:
             shard["keep_rows"] = True
+        if metric is not None:
+            shard["metric"] = metric
         self._index = DeviceIndex(rows, labels, n_buckets, ids=ids, capacity=capacity, tags=tags, **shard)
         self._cache_key = key
         return self._index
@@ -352,7 +372,7 @@ class LearnedIndex(Logger):
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist="f64" if rerank is not None else
-                                                "f32" if index.storage == "i8" else
+                                                "f32" if index.storage == "i8" or index.metric != "cosine" else
                                                 dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
                                                 timings=timings, want=want, avoid=avoid, rerank=rerank)
@@ -408,7 +428,8 @@ class LearnedIndex(Logger):
         cls = np.asarray(pred_categories).astype(np.int32).reshape(-1, 1)
         classes = torch.from_numpy(cls).to(dev)
         _, d, pos, st = self._get_searcher(index).lists(None, q, 1, k, classes=classes,
-                                                        dist=dist_dtype(data_search, queries_search))
+                                                        dist="f32" if index.metric != "cosine" else
+                                                        dist_dtype(data_search, queries_search))
         if int(st.item()) & _lib.LMI_STATUS_INTERNAL:
             raise RuntimeError(f"search_single: scan status {int(st.item())}")
         if k > _lib.LMI_REPLAY_DEVICE_MAX_KR:

@@ -41,6 +41,9 @@ LMI_PROBE_NONE = -1
 LMI_Q_F16 = 0
 LMI_Q_F32 = 1
 LMI_Q_I8 = 2
+LMI_METRIC_COSINE = 0  # lmi_bucket_topk_metric: 1 - cos, the squared Euclidean distance, -<q, y>
+LMI_METRIC_L2 = 1
+LMI_METRIC_IP = 2
 LMI_Q_SEED_ROUND0 = 0x100
 LMI_Q_PHASE_PLAN = 0x200
 LMI_Q_PHASE_SCAN = 0x400
@@ -78,6 +81,9 @@ EXPORTS = (
     "lmi_plan_chunks",
     "lmi_scan_workspace_bytes",
     "lmi_bucket_topk",
+    "lmi_scan_metric_workspace_bytes",
+    "lmi_bucket_topk_metric",
+    "lmi_row_sqnorms",
     "lmi_scan_tagged_workspace_bytes",
     "lmi_bucket_topk_tagged",
     "lmi_bucket_topk_masked",
@@ -210,6 +216,10 @@ _SIGNATURES = {
     "lmi_scan_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32,
                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_scan_metric_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32, _I32]),
+    "lmi_bucket_topk_metric": (C.c_int, [C.POINTER(IndexDesc), _I32, _P, _I32, _I32, _P, _I32, _I32, _I32,
+                                         _P, _P, _P, _P, C.c_size_t, _P]),
+    "lmi_row_sqnorms": (C.c_int, [_P, _I32, _I64, _I64, _I32, _P, _P, _P]),
     "lmi_scan_tagged_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_tagged": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32,
                                          _I32, _P, _P, _P, _P, C.c_size_t, _P]),

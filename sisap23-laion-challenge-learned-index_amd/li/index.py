@@ -170,6 +170,67 @@ def check_i8(index, what: str) -> None:
                          f"at most {_lib.LMI_MAX_K} entries on one GPU)")
 
 
+METRICS = {"cosine": _lib.LMI_METRIC_COSINE, "l2": _lib.LMI_METRIC_L2, "ip": _lib.LMI_METRIC_IP}
+
+
+def check_metric(index, what: str) -> None:
+    """ValueError when `index` is searched by a metric other than cosine and
+    `what` (the feature's name in the message) is not offered on it; before
+    anything is allocated or launched."""
+    m = index if isinstance(index, str) else getattr(index, "metric", "cosine")
+    if m != "cosine":
+        raise ValueError(f"{what} is not offered with metric {m!r} (an index searched by squared Euclidean "
+                         f"distance or inner product answers float32 lists of at most {_lib.LMI_MAX_K} entries "
+                         "on one GPU)")
+
+
+def _check_metric_build(metric, storage, subcluster: bool, capacity, world: int, tags, keep_rows: bool) -> None:
+    """What DeviceIndex(metric=...) refuses at construction, before anything is allocated."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be 'cosine', 'l2' or 'ip', not {metric!r}")
+    if metric == "cosine":
+        return
+    if storage not in ("auto", "f16", "f32"):
+        check_metric(metric, f"storage {storage!r}")
+    if subcluster:
+        check_metric(metric, "a sub-cluster layout (subcluster=True)")
+    if capacity is not None:
+        check_metric(metric, "reserved capacity (capacity=)")
+    if world > 1:
+        check_metric(metric, "a striped index (world > 1)")
+    if tags is not None:
+        check_metric(metric, "filtered search (tags=)")
+    if keep_rows:
+        check_metric(metric, "keep_rows")
+
+
+def row_sqnorms(rows: torch.Tensor, sqnorm: torch.Tensor, dst_rows: Optional[torch.Tensor] = None,
+                stream=None) -> None:
+    """lmi_row_sqnorms: |y|^2 of the device rows [m, d] (fp16 or float32, unit
+    stride along a row, any row stride), accumulated in float64 and rounded
+    once, into `sqnorm` (float32, contiguous) -- row i at dst_rows[i] (device
+    int64 [m]) or, without dst_rows, at i.  Every slot named must exist."""
+    if rows.dtype not in (torch.float16, torch.float32):
+        rows = rows.float()
+    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        rows = rows.contiguous()
+    m, d = int(rows.shape[0]), int(rows.shape[1])
+    if sqnorm.dtype != torch.float32 or sqnorm.dim() != 1 or not sqnorm.is_contiguous():
+        raise ValueError("row_sqnorms: sqnorm must be a contiguous float32 vector")
+    if dst_rows is None:
+        if sqnorm.shape[0] < m:
+            raise ValueError("row_sqnorms: fewer slots than rows")
+    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
+        raise ValueError("row_sqnorms: dst_rows must be a contiguous int64 [m] device tensor")
+    if m == 0:
+        return
+    ld = max(int(rows.stride(0)), d)
+    s = stream if stream is not None else _lib.stream_handle(sqnorm.device)
+    check("lmi_row_sqnorms", _lib.load().lmi_row_sqnorms(
+        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, ptr(dst_rows),
+        ptr(sqnorm), s))
+
+
 def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm: torch.Tensor,
                   dst_rows: Optional[torch.Tensor] = None, stream=None) -> None:
     """lmi_quantize_rows_i8: the device rows [m, d] (fp16 or float32, unit
@@ -271,8 +332,22 @@ class DeviceIndex:
     def __init__(self, data, labels, n_buckets: int, *, ids=None, device=None,
                  storage: str = "auto", chunk_rows: Optional[int] = None,
                  rank: int = 0, world: int = 1, subcluster: bool = False,
-                 capacity: Optional[int] = None, tags=None, keep_rows: bool = False):
-        """`keep_rows` (storage "i8" alone, see the class): keep the fp16 rows
+                 capacity: Optional[int] = None, tags=None, keep_rows: bool = False,
+                 metric: str = "cosine"):
+        """`metric` ("cosine", today's 1 - cos(q, y); "l2", the squared
+        Euclidean distance fmaf(-2, <q, y>, |q|^2 + |y|^2); "ip", -<q, y>, so
+        the largest inner products come first): a property of the index --
+        `inv_norm` then holds |y|^2 of every stored row (lmi_row_sqnorms; "ip":
+        nothing) -- readable as `ix.metric`.  Rows and queries are not
+        normalised.  storage "auto" keeps its rule (fp16 when every value is
+        fp16-exact) but never picks the split mode: float32 storage runs the
+        exact-fp32 scan.  A metric other than cosine answers float32 lists of
+        at most 16 entries on one GPU: ValueError, before anything is
+        allocated, with storage "i8" / "f32x", subcluster, capacity, world > 1,
+        tags or keep_rows; add / remove / relabel / reserve / quantized,
+        range search, float64 lists, streamed() and graph() refuse such an index.
+
+        `keep_rows` (storage "i8" alone, see the class): keep the fp16 rows
         beside the codes, for Searcher's `rerank`.  ValueError, before anything
         is allocated, with another storage, with a RowSource, or for rows that
         are not fp16-representable.
@@ -291,6 +366,8 @@ class DeviceIndex:
         sub-cluster layout): ValueError otherwise, or when below the row
         count."""
         _lib.load()
+        _check_metric_build(metric, storage, subcluster, capacity, world, tags, keep_rows)
+        self.metric = metric
         if keep_rows:
             if storage != "i8":
                 raise ValueError(f"keep_rows: the fp16 rows are kept beside storage 'i8' alone, not {storage!r}")
@@ -461,11 +538,13 @@ class DeviceIndex:
         new.tags_by_pos = tags_by_pos
         new.tags = None if tags_by_pos is None else _as_i32_bits(tags_by_pos).to(self.device)
         new.chunk_centroid = None
+        new.metric = self.metric
         new._ws = {}
         return new
 
     def _check_updatable(self):
         """What add / remove support, refused before any device work."""
+        check_metric(self, "an index update (add / remove / relabel / reserve)")
         if self.world > 1:
             raise ValueError("index update: a striped index (world > 1) cannot be updated in place of "
                              "a rebuild: stripe boundaries move with the bucket sizes and rows would "
@@ -648,6 +727,8 @@ class DeviceIndex:
         src64 = None
         if src.dtype == torch.float64 and storage == "i8":
             src = src.float()  # (the codes come from the float32 values; no corpus64)
+        elif src.dtype == torch.float64 and self.metric != "cosine":
+            src = src.float()  # (float32 lists alone: no corpus64)
         elif src.dtype == torch.float64:
             # float64 rows (a float64 data_search): the scan reads them rounded
             # to float32; the float64 mode recomputes from the float64 values
@@ -673,7 +754,7 @@ class DeviceIndex:
         if storage == "auto":
             storage = "f16" if src.dtype == torch.float16 or all(
                 fp16_exact(src[a:a + step].to(self.device)) for a in range(0, n, step)) else \
-                ("f32x" if self.d_pad == SPLIT_D_PAD else "f32")
+                ("f32x" if self.d_pad == SPLIT_D_PAD and self.metric == "cosine" else "f32")
         if storage not in ("f16", "f32", "f32x", "i8"):
             raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x' or 'i8'")
         if storage == "f32x" and self.d_pad != SPLIT_D_PAD:
@@ -725,8 +806,14 @@ class DeviceIndex:
                 del blk, f, h, nrm
                 continue
             self.corpus[a:a + step, : self.d] = blk.to(tdt)
-            self.inv_norm[a:a + step] = _inv_norm(blk.to(tdt))
+            if self.metric == "cosine":
+                self.inv_norm[a:a + step] = _inv_norm(blk.to(tdt))
+            elif self.metric == "l2":  # (|y|^2 of the stored values; "ip" reads no row word)
+                row_sqnorms(self.corpus[a:a + step, : self.d], self.inv_norm[a:a + step])
             del blk, f
+        if self.metric != "cosine":
+            torch.cuda.current_stream(self.device).synchronize()
+            return
         if storage != "f32x":
             self._set_inv_norm64()
         if storage == "f32x" and self.d % 16 == 0 and os.environ.get("LMI_SPLIT_NORM32", "1") != "0":
@@ -750,6 +837,8 @@ class DeviceIndex:
             raise ValueError("RowSource must have one row per label")
         if storage not in ("auto", "f16", "i8"):
             raise ValueError("a RowSource builds storage 'f16' ('auto') or 'i8'")
+        if storage == "i8":
+            check_metric(self, "storage 'i8'")
         self.d = src.d
         self.d_pad = (self.d + 31) // 32 * 32
         self.storage = "i8" if storage == "i8" else "f16"
@@ -773,10 +862,13 @@ class DeviceIndex:
                 del blk, x
                 continue
             self.corpus[dst, : self.d] = x
-            self.inv_norm[dst] = _inv_norm(x)
+            if self.metric == "cosine":
+                self.inv_norm[dst] = _inv_norm(x)
+            elif self.metric == "l2":  # (each chunk's |y|^2 straight into its bucket-sorted slots)
+                row_sqnorms(x, self.inv_norm, dst_rows=dst.contiguous())
             del blk, x
         del slot
-        if self.storage == "i8":
+        if self.storage == "i8" or self.metric != "cosine":
             torch.cuda.current_stream(self.device).synchronize()
             return
         self._set_inv_norm64()
@@ -868,6 +960,7 @@ class DeviceIndex:
         `rows16` is this index's corpus tensor itself -- no copy; do not update
         this index in place while the new one is in use."""
         self._check_live()
+        check_metric(self, "quantized() (storage 'i8')")
         if self.storage not in ("f16", "f32"):
             raise ValueError(f"quantized: storage {self.storage!r} is not supported (only 'f16' and 'f32')")
         if keep_rows and self.storage != "f16":
@@ -929,7 +1022,10 @@ class DeviceIndex:
 
     def workspace(self, nq: int, R: int, k: int, qmode: int) -> torch.Tensor:
         lib = _lib.load()
-        need = lib.lmi_scan_workspace_bytes(C.byref(self.desc_for(k)), nq, R, k, qmode)
+        if self.metric != "cosine":
+            need = lib.lmi_scan_metric_workspace_bytes(C.byref(self.desc), METRICS[self.metric], nq, R, k, qmode)
+        else:
+            need = lib.lmi_scan_workspace_bytes(C.byref(self.desc_for(k)), nq, R, k, qmode)
         ws = self._ws.get("buf")
         if ws is None or ws.numel() < need:
             ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
@@ -946,7 +1042,9 @@ class IndexDescHolder:
         d.d = ix.d
         d.d_pad = ix.d_pad
         d.n_rows = ix.n_rows
-        d.inv_norm = ptr(inv_norm if inv_norm is not None else ix.inv_norm32 if general32 else ix.inv_norm)
+        # (metric "l2": |y|^2 of every row; "ip" reads no row word)
+        d.inv_norm = None if ix.metric == "ip" else \
+            ptr(inv_norm if inv_norm is not None else ix.inv_norm32 if general32 else ix.inv_norm)
         d.gpos = ptr(ix.gpos)
         d.n_buckets = ix.n_buckets
         d.bucket_off = ptr(ix.bucket_off_local)
@@ -1146,6 +1244,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
         with i8_lists16():
             return bucket_topk(index, q, classes, k, qmode=qmode, stream=stream, out=out, ws=ws,
                                seed_round0=seed_round0, phases=phases, want=want, avoid=avoid)
+    if index.metric != "cosine":  # (refused before anything is uploaded)
+        if want is not None or avoid is not None:
+            check_metric(index, "filtered search (want / avoid)")
+        if k > _lib.LMI_MAX_K:
+            check_metric(index, f"k = {k} > {_lib.LMI_MAX_K}")
     lib = _lib.load()
     q = _rows_f32(q, index.device)
     classes = _as_torch(classes, index.device, torch.int32)
@@ -1159,6 +1262,23 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
         qmode, seed_round0 = _lib.LMI_Q_I8, False
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    if index.metric != "cosine":
+        # (lmi_bucket_topk_metric: plain float32 lists, never seeded)
+        desc, mcode = index.desc, METRICS[index.metric]
+        if out is None:
+            out = (torch.empty((nq, R, k), dtype=torch.float32, device=index.device),
+                   torch.empty((nq, R, k), dtype=torch.int32, device=index.device),
+                   torch.zeros((1,), dtype=torch.int32, device=index.device))
+        out_d, out_pos, status = out
+        if ws is None:
+            ws = index.workspace(nq, R, k, qmode)
+        else:
+            _workspace(ws, lib.lmi_scan_metric_workspace_bytes(C.byref(desc), mcode, nq, R, k, qmode), "scan")
+        s = stream if stream is not None else _lib.stream_handle(index.device)
+        check("lmi_bucket_topk_metric", lib.lmi_bucket_topk_metric(
+            C.byref(desc), mcode, ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode | phases, ptr(out_d),
+            ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
+        return out_d, out_pos, status
     if want is not None or avoid is not None:
         return _bucket_topk_tagged(index, q, classes, k, qmode, want, avoid, stream, out, ws, phases)
     desc = index.desc_for(k)
@@ -1345,6 +1465,7 @@ def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
     float64 a width the float64 search does not take, and in either
     arithmetic a width whose query tile the collect scan cannot stage
     (lmi_range_workspace_bytes answers 0: d_pad > 1248)."""
+    check_metric(index, "range search (range_search / bucket_range)")
     if index.storage == "f32x":
         raise ValueError("range search is not offered on storage 'f32x' (the split mode)")
     check_i8(index, "range search")
@@ -1524,6 +1645,7 @@ def bucket_topk_f64(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, 
     [nq*R*k] written by the MERGE phase, kth_all f32 [G, nq*R*k] read by the
     REFINE phase, LMI_Q_PHASE_REFINE in `phases`)."""
     check_i8(index, "bucket_topk_f64 (float64 lists)")
+    check_metric(index, "bucket_topk_f64 (float64 lists)")
     lib = _lib.load()
     q64 = None
     if isinstance(q, torch.Tensor) and q.dtype == torch.float64 or \
@@ -1753,6 +1875,7 @@ class Searcher:
             exchange = grouped and (index.world > 1 or force_exchange())
         if exchange:
             check_i8(index, "the list exchange over a process group")
+            check_metric(index, "the list exchange over a process group")
         if exchange and not grouped:
             raise ValueError("the list exchange needs an initialised process group")
         if exchange and index.world == 1 and tdist.get_world_size(group) > 1:
@@ -1897,6 +2020,7 @@ class Searcher:
         self.index._check_live()
         self._check_i8_lists(k_list, dist, rerank)
         if want is not None or avoid is not None:
+            check_metric(self.index, "filtered search (want / avoid)")
             nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
             # (re-ranked: the filtered scan is the float32 one of `rerank` entries)
             want = filter_words(self.index, want, avoid, nq, *((k_list, dist) if rerank is None else
@@ -1913,6 +2037,13 @@ class Searcher:
         LMI_MAX_K entries -- or, with `rerank`, float64 ones re-ranked from its
         kept fp16 rows (check_rerank, on any index); ValueError otherwise,
         before anything is launched."""
+        if self.index.metric != "cosine":
+            if rerank is not None:
+                check_metric(self.index, "rerank")
+            if dist != "f32":
+                check_metric(self.index, "dist='f64' (float64 lists)")
+            if k_list > _lib.LMI_MAX_K:
+                check_metric(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
         if rerank is not None:
             check_rerank(self.index, rerank, k_list, dist)
             return
@@ -2149,6 +2280,7 @@ class Searcher:
         """The step as a four-stage pipeline of captured graphs over a stream
         of batches (StreamedSearch); answers equal search(...) per batch."""
         check_i8(self.index, "streamed() (the batch stream)")
+        check_metric(self.index, "streamed() (the batch stream)")
         from .stream import StreamedSearch
         return StreamedSearch(self, q_nav, q_search, R, k, **kw)
 
@@ -2157,6 +2289,7 @@ class Searcher:
         host memory to the answer in host memory: same results as
         search(..., semantics="reference", replay_on="device")."""
         check_i8(self.index, "graph() (the captured step)")
+        check_metric(self.index, "graph() (the captured step)")
         from .graphed import GraphedSearch
         return GraphedSearch(self, q_nav, q_search, R, k, **kw)
 
@@ -2233,6 +2366,7 @@ class Searcher:
         dev = self.index.device
         want_w = None
         if want is not None or avoid is not None:
+            check_metric(self.index, "filtered search (want / avoid)")
             nq_w = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
             want_w = filter_words(self.index, want, avoid, nq_w, *((k_list, dist) if rerank is None else
                                                                    (rerank, "f32")),
@@ -2273,7 +2407,7 @@ class Searcher:
         # the running threshold then never exceeds round 0's k-th distance;
         # with k > k_round the first merge pads with 10000s)
         seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
-                and want_w is None)
+                and want_w is None and self.index.metric == "cosine")
         d, pos, status = self._scan(q_search, classes, k_list, qmode, f64, lap_at if sync else None,
                                     status_out=None if ans is None else ans[3][0:1],
                                     seed_round0=seed, want=want_w, rerank=rerank)
