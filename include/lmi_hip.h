@@ -54,6 +54,16 @@ extern "C" {
  * the quantised distances.  Only lmi_bucket_topk and lmi_bucket_topk_masked /
  * _tagged take it, with qmode LMI_Q_I8, 1 <= k <= LMI_MAX_K and d_pad <= 992. */
 #define LMI_I8 2
+/* 4-bit storage (an addition: LMI_ABI_VERSION does not change): MXFP4 rows,
+ * "the MXFP4 format" at lmi_quantize_rows_mx4 below.  corpus holds the codes,
+ * [n_rows][d_pad / 2] bytes, and behind them, LMI_MX4_SCALE_OFFSET(n_rows,
+ * d_pad) bytes from corpus, the scale bytes [n_rows][d_pad / 32]; inv_norm is
+ * the codes' own 1/n.  Lossy.  Only lmi_bucket_topk takes it, with qmode
+ * LMI_Q_MX4, d_pad == 768, no tags, the cosine alone, k <= 10 -- and k = 11..16
+ * on a thread that set lmi_scan_set_i8_lists16. */
+#define LMI_MX4 3
+#define LMI_MX4_SCALE_OFFSET(n_rows, d_pad) \
+    ((((size_t)(n_rows) * (size_t)((d_pad) / 2)) + 255) / 256 * 256)
 
 #define LMI_ROUTER_TOPR 0   /* softmax + classes sorted by probability (predict_proba) */
 #define LMI_ROUTER_ARGMAX 1 /* argmax of logits (predict)                               */
@@ -65,6 +75,11 @@ extern "C" {
  * (v_mfma_i32_32x32x32_i8).  LMI_I8 and LMI_Q_I8 come together: one without the
  * other is LMI_E_INVALID. */
 #define LMI_Q_I8 2
+/* The queries of an LMI_MX4 index: quantised inside the call by the rule of
+ * lmi_quantize_rows_mx4; E2M1 x E2M1 products with both operands' block scales
+ * on v_mfma_scale_f32_32x32x64_f8f6f4, summed in float32.  LMI_MX4 and
+ * LMI_Q_MX4 come together: one without the other is LMI_E_INVALID. */
+#define LMI_Q_MX4 3
 /* ABI 6, a flag OR-ed into qmode (lmi_bucket_topk / lmi_bucket_topk_f64*, k <=
  * LMI_MAX_K): the lists of probes r >= 1 are needed only below the pair's
  * round-0 k-th distance -- the reference's thresholded rounds compare every
@@ -837,6 +852,40 @@ int lmi_quantize_rows_i8(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, in
                          int32_t d, int32_t d_pad, const int64_t* dst_rows /*nullable*/,
                          int8_t* codes, float* inv_norm, void* stream);
 
+/* ---- 4-bit storage: the MXFP4 format and its quantiser (an addition) --------- */
+/* Row i of `rows` (as for lmi_quantize_rows_i8) becomes the codes, scale bytes
+ * and 1/n of slot dst_rows[i] (NULL: slot i): codes [slots][d_pad / 2] bytes,
+ * scales [slots][d_pad / 32] bytes, inv_norm [slots].  d_pad is a multiple of 64.
+ * The MXFP4 format.  v is the row as float32 (fp16 converts exactly), zero past
+ * d up to d_pad, cut into blocks of 32 consecutive columns.  For block b:
+ *   m_b = max_j |v_j|.  If !(m_b >= 2^-100) (zero, tiny, or a NaN anywhere in
+ *   the block) every code of the block is +0 and its scale byte is 127.
+ *   Else e_b = floor(log2 m_b) - 2, read from the exponent field of m_b; the
+ *   scale byte is e_b + 127, an E8M0 exponent (255 is never written);
+ *   t_j = v_j * 2^-e_b (exact, |t_j| < 8); the code is the E2M1 value nearest
+ *   |t_j| of {0, 0.5, 1, 1.5, 2, 3, 4, 6} (code bits 0..7 in that order), ties
+ *   to the even mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2,
+ *   3.5 -> 4, 5 -> 4), saturating (|t| > 5 gives 6); bit 3 is the sign, set for
+ *   t_j < 0 unless the code is zero (there is no -0).
+ * Nibble order: the code of column 2 i is the LOW nibble of code byte i, that
+ * of column 2 i + 1 the high nibble -- the order in which the scaled MFMA reads
+ * a register's eight codes, lowest bits first.
+ * Scale order: with H = d_pad / 64, the byte of block b is at (b & 1) * H +
+ * (b >> 1): even blocks first, then odd ones (a lane of the scan multiplies
+ * every second block; its bytes are then H consecutive ones).
+ * The norm, from integers so that no reduction order enters: S_b = sum_j
+ * (2 c_j)^2 over the block (c_j the code's value; S_b <= 4608), n^2 = sum_b
+ * S_b * 2^(2 e_b - 2) in float64 in block order b = 0, 1, ...;
+ * inv_norm = n^2 == 0 ? 1.0f : (float)(1.0 / sqrt(n^2)).
+ * The distance of a scan is fmaf(-acc, invq * invy, 1), acc the float32 sum of
+ * the scaled MFMAs over the blocks.  Magnitudes fp16 holds are in scope;
+ * float32 rows whose scaled products overflow float32 are not.
+ * LMI_E_INVALID before any launch: as for lmi_quantize_rows_i8, and d_pad not
+ * a multiple of 64. */
+int lmi_quantize_rows_mx4(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, int64_t m, int64_t ld,
+                          int32_t d, int32_t d_pad, const int64_t* dst_rows /*nullable*/,
+                          uint8_t* codes, uint8_t* scales, float* inv_norm, void* stream);
+
 /* ---- index update in place (K9): add / remove inside one buffer ------------- */
 /* lmi_index_move_rows with source and destination in the SAME store of
  * `capacity` rows (li.index.DeviceIndex.add / remove with inplace=True): an add
@@ -1040,7 +1089,10 @@ int32_t lmi_scan_set_join_workgroups(int32_t j);
  * differs, so size the workspace (lmi_scan_workspace_bytes /
  * lmi_scan_tagged_workspace_bytes) and ask lmi_scan_family under the setting the
  * call runs with.  Thread-local, read when the plan is made (every call).
- * LMI_SCAN_V1 still forces scan_i8_kernel.  Returns the previous setting. */
+ * LMI_SCAN_V1 still forces scan_i8_kernel.  Returns the previous setting.
+ * The 4-bit storage (LMI_MX4) follows the same switch: its ring has 10- and
+ * 16-entry lists and no other kernel, so k = 11..16 is LMI_E_INVALID on a
+ * thread that has not set it. */
 int32_t lmi_scan_set_i8_lists16(int32_t on);
 /* 1 when lmi_bucket_topk (lmi_scan_joinable) or lmi_bucket_topk_f64* (the
  * _f64 form) of these arguments runs a scan that takes j > 0, else 0. */
@@ -1050,7 +1102,8 @@ int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t 
  * uses: 0 the general kernel (on LMI_I8: scan_i8_kernel), 1 the 4-wave ring,
  * 2 the 8-wave ring, 3 the 8-wave ring of the 8-bit storage (LMI_I8 with
  * LMI_Q_I8 at d_pad == 768: k <= 10, and k = 11..16 on a thread that set
- * lmi_scan_set_i8_lists16).  The diagnostic switches LMI_SCAN_V1 /
+ * lmi_scan_set_i8_lists16), 4 the 8-wave ring of the 4-bit storage (LMI_MX4
+ * with LMI_Q_MX4, d_pad == 768, the same k).  The diagnostic switches LMI_SCAN_V1 /
  * LMI_SCAN_V2 show in the answer (after lmi_config_reload).  A combination the
  * scan refuses -- LMI_I8 without LMI_Q_I8 or with LMI_Q_SEED_ROUND0, k outside
  * [1, LMI_MAX_K], a qmode that is no query class -- is a negative LMI_E_* code

@@ -79,4 +79,77 @@ __device__ inline float quantize_row_i8(const T* __restrict__ src, int d, int d_
     return ss == 0 ? 1.0f : (float)(1.0 / sqrt((double)ss));
 }
 
+// 4-bit storage: the one device function that turns a vector into MXFP4 codes
+// (include/lmi_hip.h, "the MXFP4 format"); the row quantiser (lmi_quant.hip) and
+// the query prep of an LMI_MX4 scan (prep_mx4_kernel, lmi_scan_ring_mx4.hip)
+// both call it.
+// One wave quantises one vector: src[0..d) -> codes[0..d_pad/2) (4-byte
+// aligned) and scales[0..d_pad/32), d_pad a multiple of 64; returns the codes'
+// 1/n on every lane.  A pass takes 512 columns: lane l owns the eight
+// consecutive columns 8l.. (one 32-bit word of codes), four lanes own a block.
+//   block b:  m = max |v_j| (a NaN anywhere makes the block zero)
+//             !(m >= 2^-100): codes +0, scale byte 127
+//             else byte = exponent field of m - 2 (e_b + 127), t_j = v_j 2^-e_b
+//             (one exact multiplication), code = E2M1 nearest |t_j|, ties to the
+//             even mantissa, saturating at 6; a zero code carries no sign
+//   scales :  byte of block b at (b & 1) * d_pad/64 + (b >> 1)
+//   n^2    :  sum_b S_b 2^(2 e_b - 2), S_b = sum_j (2 c_j)^2 an integer, summed
+//             in float64 in block order (lane shuffles in a fixed order)
+template <typename T, bool VEC>
+__device__ inline float quantize_row_mx4(const T* __restrict__ src, int d, int d_pad, int lane,
+                                         uint8_t* __restrict__ codes, uint8_t* __restrict__ scales) {
+    const int half_blocks = d_pad >> 6;
+    double n2 = 0.0;
+    for (int base = 0; base < d_pad; base += 512) {
+        const int c0 = base + 8 * lane;
+        float v[2][4] = {};
+        if (c0 < d) {
+            quant_load4<VEC>(src, c0, d, v[0]);
+            quant_load4<VEC>(src, c0 + 4, d, v[1]);
+        }
+        float m = 0.0f;
+        int nan = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = v[e >> 2][e & 3];
+            nan |= (x != x) ? 1 : 0;
+            m = fmaxf(m, fabsf(x));
+        }
+#pragma unroll
+        for (int off = 1; off < 4; off <<= 1) {
+            m = fmaxf(m, __shfl_xor(m, off));
+            nan |= __shfl_xor(nan, off);
+        }
+        const bool zero = nan != 0 || !(m >= 0x1p-100f);
+        const uint32_t ef = zero ? 129u : (__float_as_uint(m) >> 23) & 0xffu;  // e_b = ef - 129
+        const float mul = __uint_as_float((256u - ef) << 23);                  // 2^-e_b
+        uint32_t word = 0u;
+        int ss = 0;
+        if (!zero) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float t = v[e >> 2][e & 3] * mul;
+                const float a = fabsf(t);
+                const uint32_t idx = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) +
+                                     (a >= 3.5f) + (a > 5.0f);
+                const int c2 = (int)((0xC8643210u >> (4 * idx)) & 15u);  // 2 |c|
+                ss += c2 * c2;
+                word |= (idx | ((t < 0.0f && idx != 0u) ? 8u : 0u)) << (4 * e);
+            }
+        }
+        ss += __shfl_xor(ss, 1);
+        ss += __shfl_xor(ss, 2);
+        if (c0 < d_pad) {
+            *reinterpret_cast<uint32_t*>(codes + (c0 >> 1)) = word;
+            const int b = c0 >> 5;
+            if ((lane & 3) == 0) scales[(b & 1) * half_blocks + (b >> 1)] = (uint8_t)(ef - 2u);
+        }
+        // S_b 2^(2 e_b - 2): exact in float64 (S_b <= 4608)
+        const double term = (double)ss * __hiloint2double((int)((1023u + 2u * ef - 260u) << 20), 0);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) n2 += __shfl(term, 4 * j);
+    }
+    return n2 == 0.0 ? 1.0f : (float)(1.0 / sqrt(n2));
+}
+
 }  // namespace lmi

@@ -245,6 +245,24 @@ constexpr int kI8MaxDPad = 992;
 // d_pad == 768, lists of KL = 10 or 16 entries, plain or TAG)
 template <int KL, bool TAG>
 int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
+// scan3_mx4_kernel (lmi_scan_ring_mx4.hip: the 8-wave ring on the 4-bit storage,
+// d_pad == 768, plain lists of KL = 10 or 16 entries).  s.corpus: the rows'
+// MXFP4 codes [n_rows][384]; scales: their scale bytes [n_rows][24]; s.qbuf:
+// the query records prep_mx4_kernel writes (mx4_qbuf_bytes)
+struct ScanMx4Args {
+    Scan2Args s;
+    const uint8_t* scales;
+};
+template <int KL>
+int launch_scan3_mx4(const ScanMx4Args& b, hipStream_t s);
+size_t mx4_qbuf_bytes(int nq);
+// prep_mx4_kernel: every query's codes, scale bytes and 1/n, the output prefill
+// and bucket_topk_impl's word fills
+int launch_prep_mx4(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t d_pad, void* qbuf, float* invq,
+                    float* out_d, int32_t* out_pos, int32_t* out_row, int32_t out_per_q, const WordFills& fills,
+                    hipStream_t s);
+// the one width of the 4-bit storage
+constexpr int kMx4DPad = 768;
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the
@@ -255,8 +273,10 @@ int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
 // General: scan_kernel (8-bit storage: scan_i8_kernel); Ring4: scan2_kernel
 // (4 waves); Ring8: scan3_kernel; Ring8I8: scan3_i8_kernel (the 8-bit storage at
 // d_pad == 768 and k <= 16: the 8-wave ring's tiles, one part, none of its
-// other paths).  The values are lmi_scan_family's.
-enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3 };
+// other paths); Ring8MX4: scan3_mx4_kernel (the 4-bit storage: d_pad == 768, k
+// <= 10, and k = 11..16 on a thread that set lmi_scan_set_i8_lists16; it has no
+// other kernel).  The values are lmi_scan_family's.
+enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3, Ring8MX4 = 4 };
 struct ScanPlan {
     ScanKernel family;
     // list length of the scan: 10 (k <= 10), 15 (k <= 15 on the 8-wave ring:
@@ -268,7 +288,10 @@ struct ScanPlan {
     // the 8-bit storage (LMI_I8 with LMI_Q_I8): scan_i8_kernel of the general
     // family or the Ring8I8 family, qbuf holds int8 rows
     bool i8;
-    int32_t split_s;     // row parts of a tail-split chunk (1: the tail split is off)
+    // the 4-bit storage (LMI_MX4 with LMI_Q_MX4): the Ring8MX4 family, qbuf
+    // holds prep_mx4_kernel's query records
+    bool mx4;
+    int32_t split_s;    // row parts of a tail-split chunk (1: the tail split is off)
     int32_t list_stride;  // partial-list slots per pair: split_s * max(max_chunks, 1)
     int32_t max_tiles;
     // offsets into the workspace (pair_pos, seed_pos: LMI_Q_SEED_ROUND0, the
@@ -293,6 +316,9 @@ const char* metric_name(int32_t metric);
 // it (flags included) -- LMI_OK off the 8-bit storage, else LMI_I8 and LMI_Q_I8
 // together, k <= LMI_MAX_K, no seed, no join phase, no corpus32 / corpus64 /
 // chunk_centroid, d_pad <= kI8MaxDPad.  i8_refuse: every other entry point.
+// Both speak for the 4-bit storage too (LMI_MX4 with LMI_Q_MX4, by that name):
+// i8_gate refuses what it refuses of LMI_I8, and d_pad != kMx4DPad, and k =
+// 11..16 off a thread that set lmi_scan_set_i8_lists16; i8_refuse refuses it.
 int i8_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t qmode);
 int i8_refuse(const char* fn, const lmi_index_desc* idx);
 // the 8-wave ring serves this index and query class (the float64 mode's band lists)

@@ -41,6 +41,8 @@ LMI_PROBE_NONE = -1
 LMI_Q_F16 = 0
 LMI_Q_F32 = 1
 LMI_Q_I8 = 2
+LMI_MX4 = 3   # 4-bit storage: MXFP4 codes and scale bytes (lmi_quantize_rows_mx4), with LMI_Q_MX4
+LMI_Q_MX4 = 3
 LMI_METRIC_COSINE = 0  # lmi_bucket_topk_metric: 1 - cos, the squared Euclidean distance, -<q, y>
 LMI_METRIC_L2 = 1
 LMI_METRIC_IP = 2
@@ -121,6 +123,7 @@ EXPORTS = (
     "lmi_index_move_rows",
     "lmi_index_ingest_rows",
     "lmi_quantize_rows_i8",
+    "lmi_quantize_rows_mx4",
     "lmi_index_move_rows_inplace",
     "lmi_bucket_sort_labels_ws_bytes",
     "lmi_bucket_sort_labels",
@@ -276,6 +279,7 @@ _SIGNATURES = {
                                       _P]),
     "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "lmi_quantize_rows_i8": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "lmi_quantize_rows_mx4": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "lmi_index_move_rows_inplace": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P,
                                               _I32, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 import time
 from typing import Optional, Sequence
 
@@ -149,16 +150,26 @@ def _as_i32_bits(a: np.ndarray) -> torch.Tensor:
 I8_MAX_D_PAD = 992  # the 8-bit scan's widest row (its query tile in LDS)
 
 
-def _check_i8_build(capacity, subcluster: bool, world: int, d: int) -> None:
-    """What an index of storage "i8" refuses at construction, before anything
-    is allocated."""
+MX4_D_PAD = 768     # the 4-bit scan's one width
+QUANTIZED = ("i8", "mx4")  # the lossy storages: codes quantised on the device, float32 lists of <= 16 entries
+
+
+def _check_i8_build(capacity, subcluster: bool, world: int, d: int, storage: str = "i8", tags=None) -> None:
+    """What an index of storage "i8" or "mx4" refuses at construction, before
+    anything is allocated."""
     if capacity is not None:
-        raise ValueError("storage 'i8': no reserved capacity (an 8-bit index takes no updates)")
+        raise ValueError(f"storage {storage!r}: no reserved capacity (a quantised index takes no updates)")
     if subcluster:
-        raise ValueError("storage 'i8' takes no sub-cluster layout (subcluster=True)")
+        raise ValueError(f"storage {storage!r} takes no sub-cluster layout (subcluster=True)")
     if world > 1:
-        raise ValueError("storage 'i8' is offered on one GPU (world == 1), not on a striped index")
-    if (int(d) + 31) // 32 * 32 > I8_MAX_D_PAD:
+        raise ValueError(f"storage {storage!r} is offered on one GPU (world == 1), not on a striped index")
+    if storage == "mx4":
+        if (int(d) + 31) // 32 * 32 != MX4_D_PAD:
+            raise ValueError(f"storage 'mx4' takes rows of {MX4_D_PAD - 31} to {MX4_D_PAD} values (d_pad == "
+                             f"{MX4_D_PAD}), not {int(d)}")
+        if tags is not None:
+            raise ValueError("storage 'mx4' takes no tags (filtered search is not offered on the 4-bit storage)")
+    elif (int(d) + 31) // 32 * 32 > I8_MAX_D_PAD:
         raise ValueError(f"storage 'i8' takes rows of at most {I8_MAX_D_PAD} values, not {int(d)}")
 
 
@@ -168,6 +179,9 @@ def check_i8(index, what: str) -> None:
     if getattr(index, "storage", None) == "i8":
         raise ValueError(f"{what} is not offered on storage 'i8' (the 8-bit storage answers float32 lists of "
                          f"at most {_lib.LMI_MAX_K} entries on one GPU)")
+    if getattr(index, "storage", None) == "mx4":
+        raise ValueError(f"{what} is not offered on storage 'mx4' (the 4-bit storage answers unfiltered float32 "
+                         f"lists of at most {_lib.LMI_MAX_K} entries on one GPU)")
 
 
 METRICS = {"cosine": _lib.LMI_METRIC_COSINE, "l2": _lib.LMI_METRIC_L2, "ip": _lib.LMI_METRIC_IP}
@@ -261,6 +275,50 @@ def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm:
         ptr(dst_rows), ptr(codes), ptr(inv_norm), s))
 
 
+def mx4_views(store: torch.Tensor, n_rows: int, d_pad: int):
+    """(codes uint8 [n_rows, d_pad / 2], scales uint8 [n_rows, d_pad / 32]): the
+    two arrays of an LMI_MX4 store (a flat uint8 tensor of mx4_store_bytes)."""
+    off = (n_rows * (d_pad // 2) + 255) // 256 * 256  # LMI_MX4_SCALE_OFFSET
+    return (store[: n_rows * (d_pad // 2)].view(n_rows, d_pad // 2),
+            store[off: off + n_rows * (d_pad // 32)].view(n_rows, d_pad // 32))
+
+
+def mx4_store_bytes(n_rows: int, d_pad: int) -> int:
+    return (n_rows * (d_pad // 2) + 255) // 256 * 256 + n_rows * (d_pad // 32)
+
+
+def quantize_rows_mx4(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, scales: torch.Tensor,
+                      inv_norm: torch.Tensor, dst_rows: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lmi_quantize_rows_mx4: the device rows [m, d] (fp16 or float32) as MXFP4
+    codes [slots, d_pad / 2], scale bytes [slots, d_pad / 32] (uint8) and the
+    codes' 1/n in `inv_norm` [slots] -- row i in slot dst_rows[i] or, without
+    dst_rows, slot i.  Every slot named must exist: the kernel does not check."""
+    if rows.dtype not in (torch.float16, torch.float32):
+        rows = rows.float()
+    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        rows = rows.contiguous()
+    m, d = int(rows.shape[0]), int(rows.shape[1])
+    slots = int(codes.shape[0])
+    if codes.dtype != torch.uint8 or tuple(codes.shape) != (slots, d_pad // 2) or not codes.is_contiguous() \
+            or scales.dtype != torch.uint8 or tuple(scales.shape) != (slots, d_pad // 32) \
+            or not scales.is_contiguous() or inv_norm.dtype != torch.float32 or inv_norm.shape != (slots,) \
+            or not inv_norm.is_contiguous():
+        raise ValueError("quantize_rows_mx4: codes uint8 [slots, d_pad/2], scales uint8 [slots, d_pad/32] and "
+                         "inv_norm float32 [slots], contiguous")
+    if dst_rows is None:
+        if slots < m:
+            raise ValueError("quantize_rows_mx4: fewer slots than rows")
+    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
+        raise ValueError("quantize_rows_mx4: dst_rows must be a contiguous int64 [m] device tensor")
+    if m == 0:
+        return
+    ld = max(int(rows.stride(0)), d)
+    s = stream if stream is not None else _lib.stream_handle(codes.device)
+    check("lmi_quantize_rows_mx4", _lib.load().lmi_quantize_rows_mx4(
+        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
+        ptr(dst_rows), ptr(codes), ptr(scales), ptr(inv_norm), s))
+
+
 # ---------------------------------------------------------------------------
 # device index
 # ---------------------------------------------------------------------------
@@ -299,7 +357,15 @@ class DeviceIndex:
     d_pad <= 992, lists of at most 16 entries, float32 lists; no capacity, no
     sub-cluster layout, no updates, no range search (each a ValueError).
 
-    keep_rows=True (storage "i8" alone): the index also holds `rows16`, the
+    "mx4" (opt-in, never picked by "auto"): the lossy 4-bit storage -- every
+    row as MXFP4 (lmi_quantize_rows_mx4: E2M1 codes, one E8M0 scale byte per 32
+    columns): `corpus` is one flat uint8 store, `codes` [n_rows, d_pad / 2] and
+    `scales` [n_rows, d_pad / 32] its two arrays, `inv_norm` the codes' 1/n.
+    What "i8" refuses it refuses, and d_pad != 768, tags, and a metric other
+    than cosine; lists of 11..16 entries need lists16=True.  Made for
+    keep_rows + rerank=16: 16 candidates a pair re-scored from the fp16 rows.
+
+    keep_rows=True (storage "i8" or "mx4"): the index also holds `rows16`, the
     bucket-sorted fp16 rows [n_rows, d_pad] (zero past d; row r of `rows16` is
     row r of `corpus`, so a list's position indexes both).  Searcher.lists /
     search(..., dist="f64", rerank=k2) then scan k2-entry 8-bit lists and
@@ -310,7 +376,8 @@ class DeviceIndex:
     index of storage "f16" shares that index's corpus tensor (no copy): the
     source must then not be updated in place while this index is in use."""
 
-    rows16 = None  # the fp16 rows kept beside the int8 codes (storage "i8", keep_rows=True)
+    rows16 = None  # the fp16 rows kept beside the codes (storage "i8" / "mx4", keep_rows=True)
+    codes = scales = None  # storage "mx4": the two arrays of the flat store `corpus` (mx4_views)
     _rows_desc = None  # the descriptor over rows16 (rows_desc)
     corpus64 = None  # float64 rows (float64 input that float32 rounding changes)
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
@@ -369,10 +436,11 @@ class DeviceIndex:
         _check_metric_build(metric, storage, subcluster, capacity, world, tags, keep_rows)
         self.metric = metric
         if keep_rows:
-            if storage != "i8":
-                raise ValueError(f"keep_rows: the fp16 rows are kept beside storage 'i8' alone, not {storage!r}")
+            if storage not in QUANTIZED:
+                raise ValueError("keep_rows: the fp16 rows are kept beside storage 'i8' or 'mx4' alone, not "
+                                 f"{storage!r}")
             if isinstance(data, RowSource):
-                raise ValueError("keep_rows: a RowSource builds storage 'i8' so that no fp16 copy exists")
+                raise ValueError(f"keep_rows: a RowSource builds storage {storage!r} so that no fp16 copy exists")
         self._keep_rows = bool(keep_rows)
         self.device = torch.device(device if device is not None else "cuda")
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
@@ -395,9 +463,9 @@ class DeviceIndex:
 
         gpos, loc_off = self.layout.shard(rank, world)
         self._capacity = None
-        if storage == "i8":
+        if storage in QUANTIZED:
             _check_i8_build(capacity, subcluster, world, int(np.shape(data)[1]) if not hasattr(data, "shape")
-                            else int(data.shape[1]))
+                            else int(data.shape[1]), storage, tags)
         if capacity is not None:
             if world > 1 or subcluster:
                 raise ValueError("capacity: only an index that add / remove support can reserve rows "
@@ -469,6 +537,17 @@ class DeviceIndex:
         make = torch.zeros if zero else torch.empty
         self._adopt_store(make((cap, self.d_pad), dtype=dtype, device=self.device),
                           torch.empty((cap,), dtype=torch.float32, device=self.device), n_rows)
+
+    def _alloc_mx4(self, n_rows: int):
+        """The store of storage "mx4": one flat uint8 tensor (codes, then the
+        scale bytes at LMI_MX4_SCALE_OFFSET) as `corpus`, its two arrays as
+        `codes` / `scales`, and `inv_norm`; nothing is reserved."""
+        self._store = self.corpus = torch.empty((max(mx4_store_bytes(n_rows, self.d_pad), 256),),
+                                                dtype=torch.uint8, device=self.device)
+        self._store_inv = self.inv_norm = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
+        self._capacity = n_rows
+        self.codes, self.scales = mx4_views(self.corpus, n_rows, self.d_pad)
+        self._desc = self._desc32 = self._desc64 = None
 
     def _adopt_store(self, store, store_inv, n_rows: int, inv64: bool = False):
         """Take `store` / `store_inv` (fresh, or a consumed index's): the capacity is its rows, `corpus` /
@@ -648,11 +727,15 @@ class DeviceIndex:
         shard (world > 1), duplicate ids, words outside [0, 2^32); an id the
         index does not hold raises as `remove` reports it (a KeyError that is a
         ValueError too); a consumed index raises as every call on it does."""
+        if self.storage == "mx4":
+            check_i8(self, "edit_tags")
         index_update.edit_tags(self, ids, set_bits, clear_bits)
 
     def set_tags(self, ids, tags) -> None:
         """The tag words of the stored objects `ids` := `tags` (an int or one
         word per id): edit_tags with every bit cleared first."""
+        if self.storage == "mx4":
+            check_i8(self, "set_tags")
         index_update.edit_tags(self, ids, tags, 0xFFFFFFFF)
 
     def ids_with(self, want: int = 0, avoid: int = 0) -> np.ndarray:
@@ -725,7 +808,7 @@ class DeviceIndex:
         if src.dim() != 2 or src.shape[0] != n:
             raise ValueError("data must be [n, d] with one row per label")
         src64 = None
-        if src.dtype == torch.float64 and storage == "i8":
+        if src.dtype == torch.float64 and storage in QUANTIZED:
             src = src.float()  # (the codes come from the float32 values; no corpus64)
         elif src.dtype == torch.float64 and self.metric != "cosine":
             src = src.float()  # (float32 lists alone: no corpus64)
@@ -755,8 +838,8 @@ class DeviceIndex:
             storage = "f16" if src.dtype == torch.float16 or all(
                 fp16_exact(src[a:a + step].to(self.device)) for a in range(0, n, step)) else \
                 ("f32x" if self.d_pad == SPLIT_D_PAD and self.metric == "cosine" else "f32")
-        if storage not in ("f16", "f32", "f32x", "i8"):
-            raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x' or 'i8'")
+        if storage not in ("f16", "f32", "f32x", "i8", "mx4"):
+            raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x', 'i8' or 'mx4'")
         if storage == "f32x" and self.d_pad != SPLIT_D_PAD:
             raise ValueError(f"storage='f32x' needs d_pad {SPLIT_D_PAD}")
         self.storage = storage
@@ -766,19 +849,26 @@ class DeviceIndex:
             raise ValueError("capacity: only an index that add / remove support can reserve rows "
                              f"(storage 'f16' without float64 rows; this one is {storage!r}"
                              + (" with corpus64)" if src64 is not None else ")"))
-        if storage == "i8":
-            # every block quantised on the device into its slots of the int8
+        if storage in QUANTIZED:
+            # every block quantised on the device into its slots of the code
             # store: the codes plus one uploaded block at the peak
             keep = getattr(self, "_keep_rows", False)
             if keep and src.dtype != torch.float16 and not all(
                     fp16_exact(src[a:a + step]) for a in range(0, n, step)):
                 raise ValueError("keep_rows needs fp16-representable data (the rule of storage='f16')")
-            self._alloc_store(n_rows, torch.int8)
+            if storage == "mx4":
+                self._alloc_mx4(n_rows)
+            else:
+                self._alloc_store(n_rows, torch.int8)
             if keep:
                 self.rows16 = torch.zeros((n_rows, self.d_pad), dtype=torch.float16, device=self.device)
             for a in range(0, n_rows, step):
                 blk = src.index_select(0, rows[a:a + step].to(src.device)).to(self.device)
-                quantize_rows(blk, self.d_pad, self.corpus[a:a + step], self.inv_norm[a:a + step])
+                if storage == "mx4":
+                    quantize_rows_mx4(blk, self.d_pad, self.codes[a:a + step], self.scales[a:a + step],
+                                      self.inv_norm[a:a + step])
+                else:
+                    quantize_rows(blk, self.d_pad, self.corpus[a:a + step], self.inv_norm[a:a + step])
                 if keep:
                     self.rows16[a:a + step, : self.d] = blk.half()
                 del blk
@@ -835,15 +925,17 @@ class DeviceIndex:
         n = self.n_total
         if src.n != n:
             raise ValueError("RowSource must have one row per label")
-        if storage not in ("auto", "f16", "i8"):
-            raise ValueError("a RowSource builds storage 'f16' ('auto') or 'i8'")
-        if storage == "i8":
-            check_metric(self, "storage 'i8'")
+        if storage not in ("auto", "f16", "i8", "mx4"):
+            raise ValueError("a RowSource builds storage 'f16' ('auto'), 'i8' or 'mx4'")
+        if storage in QUANTIZED:
+            check_metric(self, f"storage {storage!r}")
         self.d = src.d
         self.d_pad = (self.d + 31) // 32 * 32
-        self.storage = "i8" if storage == "i8" else "f16"
+        self.storage = storage if storage in QUANTIZED else "f16"
         n_rows = int(gpos.size)
-        if self.storage == "i8":
+        if self.storage == "mx4":
+            self._alloc_mx4(n_rows)
+        elif self.storage == "i8":
             self._alloc_store(n_rows, torch.int8)
         else:
             self._alloc_store(n_rows, torch.float16, zero=True)
@@ -857,6 +949,10 @@ class DeviceIndex:
             m = sl >= 0
             dst = sl[m]
             x = blk[m]
+            if self.storage == "mx4":
+                quantize_rows_mx4(x, self.d_pad, self.codes, self.scales, self.inv_norm, dst_rows=dst)
+                del blk, x
+                continue
             if self.storage == "i8":
                 quantize_rows(x, self.d_pad, self.corpus, self.inv_norm, dst_rows=dst)
                 del blk, x
@@ -868,7 +964,7 @@ class DeviceIndex:
                 row_sqnorms(x, self.inv_norm, dst_rows=dst.contiguous())
             del blk, x
         del slot
-        if self.storage == "i8" or self.metric != "cosine":
+        if self.storage in QUANTIZED or self.metric != "cosine":
             torch.cuda.current_stream(self.device).synchronize()
             return
         self._set_inv_norm64()
@@ -948,8 +1044,9 @@ class DeviceIndex:
         self.chunk_centroid = cent
 
     @torch.no_grad()
-    def quantized(self, keep_rows: bool = False) -> "DeviceIndex":
-        """A NEW index of storage "i8" with this one's rows quantised on the
+    def quantized(self, keep_rows: bool = False, storage: str = "i8") -> "DeviceIndex":
+        """A NEW index of storage "i8" (or `storage` = "mx4": lmi_quantize_rows_mx4,
+        d_pad 768, an untagged index) with this one's rows quantised on the
         device (lmi_quantize_rows_i8 over the stored rows): the same layout,
         ids, tags and chunk tables, and bitwise the index
         DeviceIndex(rows, ..., storage="i8") builds from the same rows.  This
@@ -960,21 +1057,27 @@ class DeviceIndex:
         `rows16` is this index's corpus tensor itself -- no copy; do not update
         this index in place while the new one is in use."""
         self._check_live()
-        check_metric(self, "quantized() (storage 'i8')")
+        if storage not in QUANTIZED:
+            raise ValueError(f"quantized: storage must be 'i8' or 'mx4', not {storage!r}")
+        check_metric(self, f"quantized() (storage {storage!r})")
         if self.storage not in ("f16", "f32"):
             raise ValueError(f"quantized: storage {self.storage!r} is not supported (only 'f16' and 'f32')")
         if keep_rows and self.storage != "f16":
             raise ValueError(f"quantized(keep_rows=True): the kept rows are fp16 (storage 'f16'), not {self.storage!r}")
         if self.world > 1:
-            raise ValueError("quantized: storage 'i8' is offered on one GPU (world == 1), not on a stripe")
+            raise ValueError(f"quantized: storage {storage!r} is offered on one GPU (world == 1), not on a stripe")
         if self.chunk_centroid is not None:
-            raise ValueError("quantized: storage 'i8' takes no sub-cluster layout (chunk_centroid)")
-        _check_i8_build(None, False, 1, self.d)
+            raise ValueError(f"quantized: storage {storage!r} takes no sub-cluster layout (chunk_centroid)")
+        _check_i8_build(None, False, 1, self.d, storage, self.tags_by_pos)
         new = self._successor(self.layout, self.pos_to_id, self.tags_by_pos)
-        new.storage = "i8"
-        new._adopt_store(torch.empty((self.n_rows, self.d_pad), dtype=torch.int8, device=self.device),
-                         torch.empty((self.n_rows,), dtype=torch.float32, device=self.device), self.n_rows)
-        quantize_rows(self.corpus[:, : self.d], self.d_pad, new.corpus, new.inv_norm)
+        new.storage = storage
+        if storage == "mx4":
+            new._alloc_mx4(self.n_rows)
+            quantize_rows_mx4(self.corpus[:, : self.d], self.d_pad, new.codes, new.scales, new.inv_norm)
+        else:
+            new._adopt_store(torch.empty((self.n_rows, self.d_pad), dtype=torch.int8, device=self.device),
+                             torch.empty((self.n_rows,), dtype=torch.float32, device=self.device), self.n_rows)
+            quantize_rows(self.corpus[:, : self.d], self.d_pad, new.corpus, new.inv_norm)
         if keep_rows:
             new.rows16 = self.corpus
         torch.cuda.current_stream(self.device).synchronize()
@@ -986,7 +1089,7 @@ class DeviceIndex:
         takes: the rows, their width and count; nothing else is read."""
         self._check_live()
         if self.rows16 is None:
-            raise ValueError("this index keeps no fp16 rows (build it with storage='i8', keep_rows=True)")
+            raise ValueError("this index keeps no fp16 rows (build it with storage='i8' or 'mx4', keep_rows=True)")
         if self._rows_desc is None:
             d = _lib.IndexDesc()
             d.corpus = ptr(self.rows16)
@@ -1038,7 +1141,7 @@ class IndexDescHolder:
         d = _lib.IndexDesc()
         d.corpus = ptr(ix.corpus32 if general32 else ix.corpus)
         d.dtype = _lib.LMI_F32 if (general32 or ix.storage == "f32") else \
-            _lib.LMI_I8 if ix.storage == "i8" else _lib.LMI_F16
+            _lib.LMI_I8 if ix.storage == "i8" else _lib.LMI_MX4 if ix.storage == "mx4" else _lib.LMI_F16
         d.d = ix.d
         d.d_pad = ix.d_pad
         d.n_rows = ix.n_rows
@@ -1213,12 +1316,26 @@ class i8_lists16:
     the plan (kernel family, workspace size) it had; bucket_topk(...,
     lists16=True) and the re-rank of Searcher turn it on for their own scan."""
 
+    on = threading.local()  # .depth > 0: this thread is inside the context
+
     def __enter__(self):
         self.prev = _lib.load().lmi_scan_set_i8_lists16(1)
+        self.on.depth = getattr(self.on, "depth", 0) + 1
         return self
 
     def __exit__(self, *exc):
+        self.on.depth -= 1
         _lib.load().lmi_scan_set_i8_lists16(self.prev)
+
+
+def check_mx4_k(k: int) -> None:
+    """The lists storage "mx4" scans: at most 10 entries, or at most 16 inside
+    i8_lists16() (lists16=True); ValueError otherwise, before anything is launched."""
+    if k > _lib.LMI_MAX_K:
+        raise ValueError(f"storage 'mx4' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
+    if k > 10 and getattr(i8_lists16.on, "depth", 0) == 0:
+        raise ValueError(f"storage 'mx4' takes lists of {k} entries with lists16=True alone (its ring has 10- "
+                         "and 16-entry lists)")
 
 
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
@@ -1260,6 +1377,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
             raise ValueError(f"storage 'i8' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
         # (the one query class of the 8-bit storage; its scan is never seeded)
         qmode, seed_round0 = _lib.LMI_Q_I8, False
+    if index.storage == "mx4":
+        check_mx4_k(k)
+        if want is not None or avoid is not None:
+            check_i8(index, "filtered search (want / avoid)")
+        qmode, seed_round0 = _lib.LMI_Q_MX4, False
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     if index.metric != "cosine":
@@ -1302,13 +1424,13 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     return out_d, out_pos, status
 
 
-SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8")
+SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8", "ring8-mx4")
 
 
 def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None,
                 lists16: bool = False) -> str:
     """The kernel family bucket_topk (tagged: with want / avoid) of this index
-    and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" -- as
+    and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" | "ring8-mx4" -- as
     lmi_scan_family reads it from the plan the launch uses (the diagnostic
     switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk;
     `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan."""
@@ -1317,6 +1439,8 @@ def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optiona
             return scan_family(index, k, tagged, qmode)
     if index.storage == "i8":
         qmode = _lib.LMI_Q_I8
+    elif index.storage == "mx4":
+        qmode = _lib.LMI_Q_MX4
     elif qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     fam = _lib.load().lmi_scan_family(C.byref(index.desc_for(k)), k, qmode, 1 if tagged else 0)
@@ -1572,8 +1696,8 @@ def check_rerank(index: DeviceIndex, rerank, k_list: int, dist: str) -> None:
     outside (k_list, 16]."""
     if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
         raise ValueError("rerank must be an integer (the entries of the 8-bit lists to re-rank)")
-    if getattr(index, "storage", None) != "i8":
-        raise ValueError(f"rerank: re-ranking is for storage 'i8', not {getattr(index, 'storage', None)!r}")
+    if getattr(index, "storage", None) not in QUANTIZED:
+        raise ValueError(f"rerank: re-ranking is for storage 'i8' or 'mx4', not {getattr(index, 'storage', None)!r}")
     if getattr(index, "rows16", None) is None:
         raise ValueError("rerank: this index keeps no fp16 rows (build it with keep_rows=True)")
     if dist != "f64":
@@ -1910,6 +2034,8 @@ class Searcher:
         batch, so every rank decides the same."""
         if self.index.storage == "i8":
             return _lib.LMI_Q_I8  # (the queries are quantised inside the call)
+        if self.index.storage == "mx4":
+            return _lib.LMI_Q_MX4
         if self.index.storage != "f16":
             return _lib.LMI_Q_F32
         import weakref
@@ -2000,8 +2126,11 @@ class Searcher:
 
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
-              min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None):
+              min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
+              lists16: bool = False):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
+        `lists16`: the call runs inside i8_lists16() -- storage "mx4" needs it
+        for k_list = 11..16, storage "i8" takes its ring's 16-entry lists with it.
         `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64",
         k_list < k2 <= 16): the 8-bit scan keeps k2 entries a pair and their
         float64 distances from the kept fp16 rows decide the k_list returned
@@ -2016,9 +2145,15 @@ class Searcher:
         `avoid` (the same forms; alone it means want = 0): and only rows with
         (tag & avoid) == 0.  A query that wants and avoids one bit is a
         ValueError, like every refusal of `want`, before anything is launched."""
+        if lists16:
+            with i8_lists16():
+                return self.lists(q_nav, q_search, R, k_list, classes=classes, dist=dist, stop_mass=stop_mass,
+                                  min_probes=min_probes, want=want, avoid=avoid, rerank=rerank)
         check_stop(stop_mass, min_probes)
         self.index._check_live()
         self._check_i8_lists(k_list, dist, rerank)
+        if self.index.storage == "mx4" and (want is not None or avoid is not None):
+            check_i8(self.index, "filtered search (want / avoid)")
         if want is not None or avoid is not None:
             check_metric(self.index, "filtered search (want / avoid)")
             nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
@@ -2047,11 +2182,13 @@ class Searcher:
         if rerank is not None:
             check_rerank(self.index, rerank, k_list, dist)
             return
-        if self.index.storage == "i8":
+        if self.index.storage in QUANTIZED:
             if dist != "f32":
                 check_i8(self.index, "dist='f64' (float64 lists)")
             if k_list > _lib.LMI_MAX_K:
                 check_i8(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
+        if self.index.storage == "mx4":
+            check_mx4_k(k_list)
 
     def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
         """K1 classes [nq, R]; with G > 1 ranks each routes nq/G queries and
@@ -2297,8 +2434,11 @@ class Searcher:
                use_threshold: bool = True, classes: Optional[torch.Tensor] = None,
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
-               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None):
+               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
+               lists16: bool = False):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `lists16`: as in lists (storage "mx4" with lists of 11..16 entries).
 
         `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64"; as
         in lists): the lists the merge or the replay reads are the k2-entry
@@ -2346,8 +2486,16 @@ class Searcher:
         replay).  `timings` (measurement only) receives per-stage wall times in
         ms; the stages are then separated by stream synchronisations."""
         import time
+        if lists16:
+            with i8_lists16():
+                return self.search(q_nav, q_search, R, k, k_round=k_round, use_threshold=use_threshold,
+                                   classes=classes, timings=timings, replay_on=replay_on, semantics=semantics,
+                                   dist=dist, stop_mass=stop_mass, min_probes=min_probes, want=want, avoid=avoid,
+                                   rerank=rerank)
         check_stop(stop_mass, min_probes)
         self.index._check_live()
+        if self.index.storage == "mx4" and (want is not None or avoid is not None):
+            check_i8(self.index, "filtered search (want / avoid)")
         if replay_on not in ("device", "host"):
             raise ValueError("replay_on must be 'device' or 'host'")
         if semantics not in ("reference", "exact"):
