@@ -64,6 +64,17 @@ extern "C" {
 #define LMI_MX4 3
 #define LMI_MX4_SCALE_OFFSET(n_rows, d_pad) \
     ((((size_t)(n_rows) * (size_t)((d_pad) / 2)) + 255) / 256 * 256)
+/* 6-bit storage (an addition: LMI_ABI_VERSION does not change): MXFP6 rows,
+ * "the MXFP6 format" at lmi_quantize_rows_mx6 below.  corpus holds the codes,
+ * [n_rows][d_pad / 32] fragments of 24 bytes, and behind them,
+ * LMI_MX6_SCALE_OFFSET(n_rows, d_pad) bytes from corpus, the scale bytes
+ * [n_rows][d_pad / 32]; inv_norm is the codes' own 1/n.  Lossy.  Only
+ * lmi_bucket_topk takes it, with qmode LMI_Q_MX6, d_pad == 768, no tags, the
+ * cosine alone, k <= 10 -- and k = 11..16 on a thread that set
+ * lmi_scan_set_i8_lists16. */
+#define LMI_MX6 4
+#define LMI_MX6_SCALE_OFFSET(n_rows, d_pad) \
+    ((((size_t)(n_rows) * (size_t)((d_pad) / 4 * 3)) + 255) / 256 * 256)
 
 #define LMI_ROUTER_TOPR 0   /* softmax + classes sorted by probability (predict_proba) */
 #define LMI_ROUTER_ARGMAX 1 /* argmax of logits (predict)                               */
@@ -80,6 +91,11 @@ extern "C" {
  * on v_mfma_scale_f32_32x32x64_f8f6f4, summed in float32.  LMI_MX4 and
  * LMI_Q_MX4 come together: one without the other is LMI_E_INVALID. */
 #define LMI_Q_MX4 3
+/* The queries of an LMI_MX6 index: quantised inside the call by the rule of
+ * lmi_quantize_rows_mx6; E2M3 x E2M3 products with both operands' block scales
+ * on v_mfma_scale_f32_32x32x64_f8f6f4, summed in float32.  LMI_MX6 and
+ * LMI_Q_MX6 come together: one without the other is LMI_E_INVALID. */
+#define LMI_Q_MX6 4
 /* ABI 6, a flag OR-ed into qmode (lmi_bucket_topk / lmi_bucket_topk_f64*, k <=
  * LMI_MAX_K): the lists of probes r >= 1 are needed only below the pair's
  * round-0 k-th distance -- the reference's thresholded rounds compare every
@@ -886,6 +902,34 @@ int lmi_quantize_rows_mx4(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, i
                           int32_t d, int32_t d_pad, const int64_t* dst_rows /*nullable*/,
                           uint8_t* codes, uint8_t* scales, float* inv_norm, void* stream);
 
+/* ---- 6-bit storage: the MXFP6 format and its quantiser (an addition) --------- */
+/* As lmi_quantize_rows_mx4, with codes [slots][d_pad / 32] fragments of 24 bytes
+ * (d_pad * 3 / 4 bytes a slot), scales [slots][d_pad / 32] bytes, inv_norm [slots].
+ * The MXFP6 format.  Blocks, m_b, the zero rule, e_b, the scale byte and t_j
+ * are the MXFP4 format's, unchanged.  The code is the E2M3 value nearest |t_j|:
+ * bit 5 the sign, bits 4..3 the exponent field E (bias 1), bits 2..0 the
+ * mantissa M; the magnitude is M / 8 for E = 0 and (1 + M / 8) * 2^(E - 1)
+ * otherwise -- k / 8 for k < 8, then 1 .. 1.875, 2 .. 3.75, 4 .. 7.5 in eight
+ * steps each, so the magnitude grows with the index 8 E + M.  Ties go to the
+ * even mantissa (0.0625 -> 0, 0.1875 -> 0.25, 1.9375 -> 2, 3.875 -> 4, 7.25 ->
+ * 7), values saturate (every |t| > 7.25 gives 7.5), and the sign bit is set for
+ * t_j < 0 unless the code is zero (there is no -0).
+ * Fragment: the 32 codes of a block are one 24-byte string, the code of column
+ * j of the block in bits [6 j, 6 j + 6) of the string read as a little-endian
+ * 192-bit number -- exactly what the scaled MFMA reads as a lane's FP6 operand
+ * (six VGPRs, lowest bits first), so a stored fragment is an operand.
+ * Layout: a row's d_pad / 32 fragments lie back to back in block order, 24 bytes
+ * apart (the scan copies rows in 16-byte pieces and reads whole fragments at
+ * 8-byte alignment).  Scale order: the MXFP4 format's, even blocks first.
+ * The norm: S_b = sum_j (8 c_j)^2 over the block (S_b <= 115 200), n^2 = sum_b
+ * S_b * 2^(2 e_b - 6) in float64 in block order; inv_norm = n^2 == 0 ? 1.0f :
+ * (float)(1.0 / sqrt(n^2)).  The distance of a scan is fmaf(-acc, invq * invy,
+ * 1), acc the float32 sum of the scaled MFMAs over the blocks.
+ * LMI_E_INVALID before any launch: as for lmi_quantize_rows_mx4. */
+int lmi_quantize_rows_mx6(const void* rows, int32_t dtype /*LMI_F16|LMI_F32*/, int64_t m, int64_t ld,
+                          int32_t d, int32_t d_pad, const int64_t* dst_rows /*nullable*/,
+                          uint8_t* codes, uint8_t* scales, float* inv_norm, void* stream);
+
 /* ---- index update in place (K9): add / remove inside one buffer ------------- */
 /* lmi_index_move_rows with source and destination in the SAME store of
  * `capacity` rows (li.index.DeviceIndex.add / remove with inplace=True): an add
@@ -1092,7 +1136,7 @@ int32_t lmi_scan_set_join_workgroups(int32_t j);
  * LMI_SCAN_V1 still forces scan_i8_kernel.  Returns the previous setting.
  * The 4-bit storage (LMI_MX4) follows the same switch: its ring has 10- and
  * 16-entry lists and no other kernel, so k = 11..16 is LMI_E_INVALID on a
- * thread that has not set it. */
+ * thread that has not set it.  The 6-bit storage (LMI_MX6) does the same. */
 int32_t lmi_scan_set_i8_lists16(int32_t on);
 /* 1 when lmi_bucket_topk (lmi_scan_joinable) or lmi_bucket_topk_f64* (the
  * _f64 form) of these arguments runs a scan that takes j > 0, else 0. */
@@ -1103,7 +1147,8 @@ int lmi_scan_joinable(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t 
  * 2 the 8-wave ring, 3 the 8-wave ring of the 8-bit storage (LMI_I8 with
  * LMI_Q_I8 at d_pad == 768: k <= 10, and k = 11..16 on a thread that set
  * lmi_scan_set_i8_lists16), 4 the 8-wave ring of the 4-bit storage (LMI_MX4
- * with LMI_Q_MX4, d_pad == 768, the same k).  The diagnostic switches LMI_SCAN_V1 /
+ * with LMI_Q_MX4, d_pad == 768, the same k), 5 the 8-wave ring of the 6-bit
+ * storage (LMI_MX6 with LMI_Q_MX6, likewise).  The diagnostic switches LMI_SCAN_V1 /
  * LMI_SCAN_V2 show in the answer (after lmi_config_reload).  A combination the
  * scan refuses -- LMI_I8 without LMI_Q_I8 or with LMI_Q_SEED_ROUND0, k outside
  * [1, LMI_MAX_K], a qmode that is no query class -- is a negative LMI_E_* code

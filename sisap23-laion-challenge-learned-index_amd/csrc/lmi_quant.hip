@@ -2,7 +2,8 @@
 // float32 block to int8 codes and the codes' 1/||c||, one wave per row, straight
 // into their slots of the store (dst_rows: the bucket-sorted scatter of an index
 // build).  4-bit storage: lmi_quantize_rows_mx4, the same for MXFP4 codes, their
-// block scales and 1/n.  New to this project: the reference keeps its rows as the data set
+// block scales and 1/n; 6-bit storage: lmi_quantize_rows_mx6, MXFP6 fragments
+// likewise.  New to this project: the reference keeps its rows as the data set
 // gives them (search.py:79-84) and has no quantised form.
 #include "lmi_quant.hpp"
 
@@ -40,6 +41,23 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_mx4_kernel(
     for (int64_t i = wave; i < m; i += nwaves) {  // (wave-uniform: no barrier below)
         const int64_t to = dst_rows ? dst_rows[i] : i;
         const float inv = quantize_row_mx4<T, VEC>(rows + i * ld, d, d_pad, lane, codes + to * (d_pad / 2),
+                                                   scales + to * (d_pad / 32));
+        if (lane == 0) inv_norm[to] = inv;
+    }
+}
+
+// lmi_quantize_rows_mx6: one wave per row through quantize_row_mx6
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kQuantThreads) void quantize_rows_mx6_kernel(
+    const T* __restrict__ rows, int64_t m, int64_t ld, int32_t d, int32_t d_pad,
+    const int64_t* __restrict__ dst_rows, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
+    float* __restrict__ inv_norm) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (kQuantThreads / 64) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (kQuantThreads / 64);
+    for (int64_t i = wave; i < m; i += nwaves) {  // (wave-uniform: no barrier below)
+        const int64_t to = dst_rows ? dst_rows[i] : i;
+        const float inv = quantize_row_mx6<T, VEC>(rows + i * ld, d, d_pad, lane, codes + to * (d_pad / 4 * 3),
                                                    scales + to * (d_pad / 32));
         if (lane == 0) inv_norm[to] = inv;
     }
@@ -106,5 +124,35 @@ extern "C" int lmi_quantize_rows_mx4(const void* rows, int32_t dtype, int64_t m,
     }
 #undef LMI_QUANT4
     LMI_LAUNCH_CHECK("quantize_rows_mx4_kernel");
+    return LMI_OK;
+}
+
+extern "C" int lmi_quantize_rows_mx6(const void* rows, int32_t dtype, int64_t m, int64_t ld, int32_t d,
+                                     int32_t d_pad, const int64_t* dst_rows, uint8_t* codes, uint8_t* scales,
+                                     float* inv_norm, void* stream) {
+    using namespace lmi;
+    LMI_CHECK_ARG(dtype == LMI_F16 || dtype == LMI_F32, "quantize rows mx6: dtype=%d (LMI_F16 or LMI_F32)", dtype);
+    LMI_CHECK_ARG(m >= 0, "quantize rows mx6: m=%lld", (long long)m);
+    LMI_CHECK_ARG(d > 0 && d_pad >= d && d_pad % 64 == 0 && d_pad - d < 32,
+                  "quantize rows mx6: d=%d d_pad=%d (d rounded up to a multiple of 32 that is one of 64)", d, d_pad);
+    LMI_CHECK_ARG(ld >= d, "quantize rows mx6: ld=%lld < d=%d", (long long)ld, d);
+    if (m == 0) return LMI_OK;
+    LMI_CHECK_ARG(rows && codes && scales && inv_norm, "quantize rows mx6: null pointer");
+    LMI_CHECK_ARG((reinterpret_cast<uintptr_t>(codes) & 3) == 0, "quantize rows mx6: codes not 4-byte aligned");
+    const int64_t el = dtype == LMI_F16 ? 2 : 4;
+    const bool vec = (reinterpret_cast<uintptr_t>(rows) % (4 * el)) == 0 && ld % 4 == 0;
+    const unsigned grid = (unsigned)std::min<int64_t>((m + kQuantThreads / 64 - 1) / (kQuantThreads / 64),
+                                                      kQuantMaxGrid);
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define LMI_QUANT6(T, V)                                                                             \
+    hipLaunchKernelGGL((quantize_rows_mx6_kernel<T, V>), dim3(grid), dim3(kQuantThreads), 0, s,      \
+                       static_cast<const T*>(rows), m, ld, d, d_pad, dst_rows, codes, scales, inv_norm)
+    if (dtype == LMI_F16) {
+        if (vec) LMI_QUANT6(__half, true); else LMI_QUANT6(__half, false);
+    } else {
+        if (vec) LMI_QUANT6(float, true); else LMI_QUANT6(float, false);
+    }
+#undef LMI_QUANT6
+    LMI_LAUNCH_CHECK("quantize_rows_mx6_kernel");
     return LMI_OK;
 }

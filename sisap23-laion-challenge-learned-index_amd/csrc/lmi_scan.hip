@@ -902,12 +902,14 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
     // (the 4-bit storage has one kernel, a ring of its own: 10- and 16-entry
     // lists; i8_gate refuses every call it does not serve)
     w.mx4 = (idx->dtype == LMI_MX4) && (qmode == LMI_Q_MX4);
+    w.mx6 = (idx->dtype == LMI_MX6) && (qmode == LMI_Q_MX6);  // (the 6-bit storage: likewise)
     w.family = w.mx4 ? ScanKernel::Ring8MX4
+               : w.mx6 ? ScanKernel::Ring8MX6
                : ring8i8 ? ScanKernel::Ring8I8
                : ring8 && w.kl != 16 ? ScanKernel::Ring8
                : ring4 && !lo && !tagged && metric == LMI_METRIC_COSINE ? ScanKernel::Ring4 : ScanKernel::General;
     const bool v3 = w.family == ScanKernel::Ring8;
-    w.qb = v3 || ring8i8 || w.mx4 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
+    w.qb = v3 || ring8i8 || w.mx4 || w.mx6 ? v3::QB : w.family == ScanKernel::Ring4 ? v2::QB : (w.f16math || w.i8 ? 64 : 32);
     const size_t P = (size_t)nq * R;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -915,7 +917,7 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
         off = align_up(off + bytes, 256);
         return at;
     };
-    w.qbuf = take(w.mx4 ? mx4_qbuf_bytes(nq) : (size_t)nq * idx->d_pad * (w.i8 ? 1 : w.f16math ? 2 : 4));
+    w.qbuf = take(w.mx4 ? mx4_qbuf_bytes(nq) : w.mx6 ? mx6_qbuf_bytes(nq) : (size_t)nq * idx->d_pad * (w.i8 ? 1 : w.f16math ? 2 : 4));
     w.invq = take((size_t)nq * 4);
     w.counts = take((size_t)idx->n_buckets * 4);
     w.pair_q = take(P * 4);
@@ -955,24 +957,33 @@ ScanPlan scan_plan(const lmi_index_desc* idx, int nq, int R, int k, int qmode, b
 }
 
 namespace {
-// i8_gate's other half: the 4-bit storage's refusals
-int mx4_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t base, int32_t qmode) {
-    const bool mx4 = idx != nullptr && idx->dtype == LMI_MX4;
-    if (!mx4 && base != LMI_Q_MX4) return LMI_OK;
-    LMI_CHECK_ARG(mx4 && base == LMI_Q_MX4,
-                  "%s: LMI_MX4 (the 4-bit storage) and LMI_Q_MX4 come together (dtype=%d, qmode=0x%x)", fn,
-                  idx ? idx->dtype : -1, qmode);
-    LMI_CHECK_ARG(idx->d_pad == kMx4DPad, "%s: LMI_MX4 takes d_pad == %d, not %d", fn, kMx4DPad, idx->d_pad);
-    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: LMI_MX4 takes k in [1, %d], not %d", fn, LMI_MAX_K, k);
+// i8_gate's other half: the refusals of the 4-bit and the 6-bit storage, each
+// by its own name
+int mx_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t base, int32_t qmode, int32_t dtype,
+            int32_t qclass, const char* name, const char* what, int32_t d_pad) {
+    const bool mx = idx != nullptr && idx->dtype == dtype;
+    if (!mx && base != qclass) return LMI_OK;
+    LMI_CHECK_ARG(mx && base == qclass, "%s: LMI_%s (the %s storage) and LMI_Q_%s come together (dtype=%d, qmode=0x%x)",
+                  fn, name, what, name, idx ? idx->dtype : -1, qmode);
+    LMI_CHECK_ARG(idx->d_pad == d_pad, "%s: LMI_%s takes d_pad == %d, not %d", fn, name, d_pad, idx->d_pad);
+    LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: LMI_%s takes k in [1, %d], not %d", fn, name, LMI_MAX_K, k);
     LMI_CHECK_ARG(k <= 10 || t_i8_lists16 != 0,
-                  "%s: LMI_MX4 takes k = %d only on a thread that set lmi_scan_set_i8_lists16 (its 16-entry lists)",
-                  fn, k);
-    LMI_CHECK_ARG(!(qmode & LMI_Q_SEED_ROUND0), "%s: LMI_MX4 is never seeded (LMI_Q_SEED_ROUND0)", fn);
-    LMI_CHECK_ARG(!(qmode & LMI_Q_PHASE_SCAN_JOIN), "%s: LMI_MX4 takes no join workgroups (LMI_Q_PHASE_SCAN_JOIN)", fn);
+                  "%s: LMI_%s takes k = %d only on a thread that set lmi_scan_set_i8_lists16 (its 16-entry lists)",
+                  fn, name, k);
+    LMI_CHECK_ARG(!(qmode & LMI_Q_SEED_ROUND0), "%s: LMI_%s is never seeded (LMI_Q_SEED_ROUND0)", fn, name);
+    LMI_CHECK_ARG(!(qmode & LMI_Q_PHASE_SCAN_JOIN), "%s: LMI_%s takes no join workgroups (LMI_Q_PHASE_SCAN_JOIN)", fn,
+                  name);
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
-                  "%s: LMI_MX4 with corpus32 / corpus64 (the 4-bit storage keeps the codes alone)", fn);
-    LMI_CHECK_ARG(!idx->chunk_centroid, "%s: LMI_MX4 takes no sub-cluster layout (chunk_centroid)", fn);
+                  "%s: LMI_%s with corpus32 / corpus64 (the %s storage keeps the codes alone)", fn, name, what);
+    LMI_CHECK_ARG(!idx->chunk_centroid, "%s: LMI_%s takes no sub-cluster layout (chunk_centroid)", fn, name);
     return LMI_OK;
+}
+int mx4_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t base, int32_t qmode) {
+    // (the index's own storage speaks first, so that its name is in the message)
+    if (idx != nullptr && idx->dtype == LMI_MX6)
+        LMI_TRY(mx_gate(fn, idx, k, base, qmode, LMI_MX6, LMI_Q_MX6, "MX6", "6-bit", kMx6DPad));
+    LMI_TRY(mx_gate(fn, idx, k, base, qmode, LMI_MX4, LMI_Q_MX4, "MX4", "4-bit", kMx4DPad));
+    return mx_gate(fn, idx, k, base, qmode, LMI_MX6, LMI_Q_MX6, "MX6", "6-bit", kMx6DPad);
 }
 }  // namespace
 
@@ -1010,6 +1021,8 @@ int metric_gate(const char* fn, const lmi_index_desc* idx, int32_t metric, int32
                   "%s: metric %s is not offered on the 8-bit storage (LMI_I8 / LMI_Q_I8)", fn, m);
     LMI_CHECK_ARG(idx->dtype != LMI_MX4 && base != LMI_Q_MX4,
                   "%s: metric %s is not offered on the 4-bit storage (LMI_MX4 / LMI_Q_MX4)", fn, m);
+    LMI_CHECK_ARG(idx->dtype != LMI_MX6 && base != LMI_Q_MX6,
+                  "%s: metric %s is not offered on the 6-bit storage (LMI_MX6 / LMI_Q_MX6)", fn, m);
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64,
                   "%s: metric %s takes no split mode and no float64 rows (corpus32 / corpus64)", fn, m);
     LMI_CHECK_ARG(!idx->chunk_centroid, "%s: metric %s takes no sub-cluster layout (chunk_centroid)", fn, m);
@@ -1027,6 +1040,8 @@ int i8_refuse(const char* fn, const lmi_index_desc* idx) {
                   "%s: LMI_I8 (the 8-bit storage) is served by lmi_bucket_topk and lmi_bucket_topk_masked alone", fn);
     LMI_CHECK_ARG(idx == nullptr || idx->dtype != LMI_MX4,
                   "%s: LMI_MX4 (the 4-bit storage) is served by lmi_bucket_topk alone", fn);
+    LMI_CHECK_ARG(idx == nullptr || idx->dtype != LMI_MX6,
+                  "%s: LMI_MX6 (the 6-bit storage) is served by lmi_bucket_topk alone", fn);
     return LMI_OK;
 }
 
@@ -1120,7 +1135,7 @@ int launch_scan3(const Scan2Args& b, hipStream_t s) {
 struct ScanLaunch {
     int (*ring)(const Scan2Args&, hipStream_t);
     int (*general)(const ScanArgs&, int, hipStream_t);
-    int (*mx4)(const ScanMx4Args&, hipStream_t) = nullptr;  // the Ring8MX4 family's (with the scale bytes)
+    int (*mx4)(const ScanMx4Args&, hipStream_t) = nullptr;  // the Ring8MX4 / Ring8MX6 families' (with the scale bytes)
 };
 ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     const int kl = p.kl, mode = c.wide ? c.wide->mode : 0;
@@ -1129,7 +1144,7 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
     if (c.metric != LMI_METRIC_COSINE) {
         // plain lists alone: the 8-wave ring's 10-entry lists, the
         // general kernel's 10 and 16 in the three (math, corpus) classes
-        if (!plain || p.i8 || p.mx4 || c.tags != nullptr || c.range != nullptr) return {nullptr, nullptr};
+        if (!plain || p.i8 || p.mx4 || p.mx6 || c.tags != nullptr || c.range != nullptr) return {nullptr, nullptr};
         const bool l2 = c.metric == LMI_METRIC_L2;
 #define LMI_PICK_M(...) (l2 ? __VA_ARGS__, LMI_METRIC_L2> : __VA_ARGS__, LMI_METRIC_IP>)
         if (p.family == ScanKernel::Ring8)
@@ -1149,6 +1164,11 @@ ScanLaunch pick_launch(const ScanPlan& p, const ScanCall& c) {
         // the 4-bit scan: plain lists, nothing else
         if (!plain || c.tags != nullptr) return {nullptr, nullptr};
         return {nullptr, nullptr, kl == 10 ? launch_scan3_mx4<10> : launch_scan3_mx4<16>};
+    }
+    if (p.mx6) {
+        // the 6-bit scan: likewise
+        if (!plain || c.tags != nullptr) return {nullptr, nullptr};
+        return {nullptr, nullptr, kl == 10 ? launch_scan3_mx6<10> : launch_scan3_mx6<16>};
     }
     if (p.i8) {
         // the 8-bit scan: plain or tagged lists, nothing else
@@ -1311,7 +1331,7 @@ extern "C" size_t lmi_scan_tagged_workspace_bytes(const lmi_index_desc* idx, int
                                                   int32_t k, int32_t qmode) {
     using namespace lmi;
     if (!idx || nq < 0 || R < 1 || k < 1 || k > LMI_MAX_K) return 0;
-    if (idx->corpus32 || idx->corpus64 || idx->chunk_centroid || idx->dtype == LMI_MX4) return 0;
+    if (idx->corpus32 || idx->corpus64 || idx->chunk_centroid || idx->dtype == LMI_MX4 || idx->dtype == LMI_MX6) return 0;
     if (i8_gate("lmi_scan_tagged_workspace_bytes", idx, k, qmode) != LMI_OK) return 0;
     if (qmode != LMI_Q_F16 && qmode != LMI_Q_F32 && qmode != LMI_Q_I8) return 0;
     return scan_plan(idx, nq, R, k, qmode, false, true).total;
@@ -1330,6 +1350,8 @@ int topk_masked(const char* fn, const lmi_index_desc* idx, const uint32_t* tags,
     LMI_CHECK_ARG(tags != nullptr && value != nullptr && mask != nullptr, "%s: null tags or want", fn);
     LMI_CHECK_ARG(idx->dtype != LMI_MX4 && (qmode & 0xff) != LMI_Q_MX4,
                   "%s: LMI_MX4 (the 4-bit storage) takes no tags", fn);
+    LMI_CHECK_ARG(idx->dtype != LMI_MX6 && (qmode & 0xff) != LMI_Q_MX6,
+                  "%s: LMI_MX6 (the 6-bit storage) takes no tags", fn);
     LMI_TRY(i8_gate(fn, idx, k, qmode));  // (the 8-bit storage's own refusals, by name)
     LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "%s: k=%d outside [1, %d]", fn, k, LMI_MAX_K);
     LMI_CHECK_ARG(!idx->corpus32 && !idx->corpus64, "%s: the split mode (corpus32 / corpus64) takes no tags", fn);
@@ -1392,7 +1414,8 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     int32_t *out_pos = c.out_pos, *out_row = c.out_row, *status = c.status;
     hipStream_t s = c.stream;
     LMI_CHECK_ARG(idx != nullptr, "null index");
-    LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32 || idx->dtype == LMI_I8 || idx->dtype == LMI_MX4,
+    LMI_CHECK_ARG(idx->dtype == LMI_F16 || idx->dtype == LMI_F32 || idx->dtype == LMI_I8 || idx->dtype == LMI_MX4 ||
+                      idx->dtype == LMI_MX6,
                   "bad corpus dtype");
     // (the 8-bit storage: the checks of the entry points again, for the
     // internal callers -- the wide path, the float64 mode, the range search --
@@ -1405,6 +1428,10 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     LMI_CHECK_ARG(idx->dtype != LMI_MX4 || (c.lo_g == nullptr && c.wide == nullptr && c.out_bound == nullptr &&
                                             c.range == nullptr && c.tags == nullptr && !(c.phases & kPhaseJoin)),
                   "LMI_MX4 takes plain lists alone (no tags, lower bounds, wide scans, band lists, range scan or "
+                  "join phase)");
+    LMI_CHECK_ARG(idx->dtype != LMI_MX6 || (c.lo_g == nullptr && c.wide == nullptr && c.out_bound == nullptr &&
+                                            c.range == nullptr && c.tags == nullptr && !(c.phases & kPhaseJoin)),
+                  "LMI_MX6 takes plain lists alone (no tags, lower bounds, wide scans, band lists, range scan or "
                   "join phase)");
     // (a metric other than cosine: the entry's checks again, and plain lists alone)
     LMI_TRY(metric_gate("bucket_topk", idx, c.metric, k, qmode | (c.seed_r0 ? LMI_Q_SEED_ROUND0 : 0)));
@@ -1419,7 +1446,9 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
     LMI_CHECK_ARG(idx->n_rows >= 0 && idx->n_rows < (int64_t)UINT32_MAX, "n_rows out of range");
     LMI_CHECK_ARG(nq >= 0 && R >= 1 && (int64_t)nq * R < INT32_MAX, "bad nq/R");
     LMI_CHECK_ARG(k >= 1 && k <= LMI_MAX_K, "k=%d outside [1, %d]", k, LMI_MAX_K);
-    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32 || qmode == LMI_Q_I8 || qmode == LMI_Q_MX4, "bad qmode");
+    LMI_CHECK_ARG(qmode == LMI_Q_F16 || qmode == LMI_Q_F32 || qmode == LMI_Q_I8 || qmode == LMI_Q_MX4 ||
+                      qmode == LMI_Q_MX6,
+                  "bad qmode");
     LMI_CHECK_ARG(ldq >= idx->d, "ldq < d");
     if (nq == 0) return LMI_OK;
     LMI_CHECK_ARG(c.q && classes && out_d && out_pos && status && c.workspace, "null pointer");
@@ -1489,7 +1518,7 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
         add(ws + w.split_mask, 0u, R);
         if (ring) add(ws + w.thr_g, 0xffffffffu, 2 * R);
     }
-    if (do_plan && w.mx4) {
+    if (do_plan && (w.mx4 || w.mx6)) {
         WordFills wf{};
         wf.n = fills.n;
         for (int f = 0; f < fills.n; ++f) {
@@ -1497,8 +1526,9 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
             wf.v[f] = fills.v[f];
             wf.per_q[f] = fills.per_q[f];
         }
-        LMI_TRY(launch_prep_mx4(c.q, nq, ldq, idx->d, idx->d_pad, ws + w.qbuf, (float*)(ws + w.invq), out_d, out_pos,
-                                out_row, c.prefill ? R * ldo : 0, wf, s));
+        LMI_TRY((w.mx6 ? launch_prep_mx6 : launch_prep_mx4)(c.q, nq, ldq, idx->d, idx->d_pad, ws + w.qbuf,
+                                                            (float*)(ws + w.invq), out_d, out_pos, out_row,
+                                                            c.prefill ? R * ldo : 0, wf, s));
     } else if (do_plan && w.i8) {
         const dim3 pg((nq + kThreads / 64 - 1) / (kThreads / 64));
         const bool vec = ((uintptr_t)c.q % 16 == 0) && (ldq % 4 == 0);
@@ -1687,10 +1717,11 @@ int lmi::bucket_topk_impl(const ScanCall& c) {
             b.sub_rows = wide->sub_rows;
             b.sub_take = wide->sub_take;
         }
-        if (w.mx4) {
+        if (w.mx4 || w.mx6) {
             // (no join phase: one launch; the scale bytes lie behind the codes)
             const ScanMx4Args m4{b, reinterpret_cast<const uint8_t*>(idx->corpus) +
-                                        LMI_MX4_SCALE_OFFSET(idx->n_rows, idx->d_pad)};
+                                        (w.mx6 ? LMI_MX6_SCALE_OFFSET(idx->n_rows, idx->d_pad)
+                                               : LMI_MX4_SCALE_OFFSET(idx->n_rows, idx->d_pad))};
             if (do_scan) LMI_TRY(launch.mx4(m4, s));
         } else if (do_scan && join_n > 0) {
             const ScanGrid grid(num_cus() - join_n);
@@ -1772,7 +1803,8 @@ extern "C" int32_t lmi_scan_family(const lmi_index_desc* idx, int32_t k, int32_t
     qmode &= ~LMI_Q_SEED_ROUND0;
     take_phases(qmode);
     if (k < 1 || k > LMI_MAX_K ||
-        (qmode != LMI_Q_F16 && qmode != LMI_Q_F32 && qmode != LMI_Q_I8 && qmode != LMI_Q_MX4)) {
+        (qmode != LMI_Q_F16 && qmode != LMI_Q_F32 && qmode != LMI_Q_I8 && qmode != LMI_Q_MX4 &&
+         qmode != LMI_Q_MX6)) {
         set_error("lmi_scan_family: k=%d outside [1, %d] or qmode 0x%x not a query class", k, LMI_MAX_K, qmode);
         return -LMI_E_INVALID;
     }

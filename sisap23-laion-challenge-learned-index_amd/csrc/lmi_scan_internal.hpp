@@ -263,6 +263,18 @@ int launch_prep_mx4(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t 
                     hipStream_t s);
 // the one width of the 4-bit storage
 constexpr int kMx4DPad = 768;
+// scan3_mx6_kernel (lmi_scan_ring_mx6.hip: the 8-wave ring on the 6-bit storage,
+// d_pad == 768, plain lists of KL = 10 or 16 entries), with the arguments of the
+// 4-bit ring: s.corpus the rows' MXFP6 fragments [n_rows][24][24], scales their
+// scale bytes [n_rows][24], s.qbuf the records prep_mx6_kernel writes
+template <int KL>
+int launch_scan3_mx6(const ScanMx4Args& b, hipStream_t s);
+size_t mx6_qbuf_bytes(int nq);
+int launch_prep_mx6(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t d_pad, void* qbuf, float* invq,
+                    float* out_d, int32_t* out_pos, int32_t* out_row, int32_t out_per_q, const WordFills& fills,
+                    hipStream_t s);
+// the one width of the 6-bit storage
+constexpr int kMx6DPad = 768;
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the
@@ -275,8 +287,9 @@ constexpr int kMx4DPad = 768;
 // d_pad == 768 and k <= 16: the 8-wave ring's tiles, one part, none of its
 // other paths); Ring8MX4: scan3_mx4_kernel (the 4-bit storage: d_pad == 768, k
 // <= 10, and k = 11..16 on a thread that set lmi_scan_set_i8_lists16; it has no
-// other kernel).  The values are lmi_scan_family's.
-enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3, Ring8MX4 = 4 };
+// other kernel); Ring8MX6: scan3_mx6_kernel (the 6-bit storage, on the same
+// terms).  The values are lmi_scan_family's.
+enum class ScanKernel { General = 0, Ring4 = 1, Ring8 = 2, Ring8I8 = 3, Ring8MX4 = 4, Ring8MX6 = 5 };
 struct ScanPlan {
     ScanKernel family;
     // list length of the scan: 10 (k <= 10), 15 (k <= 15 on the 8-wave ring:
@@ -291,6 +304,9 @@ struct ScanPlan {
     // the 4-bit storage (LMI_MX4 with LMI_Q_MX4): the Ring8MX4 family, qbuf
     // holds prep_mx4_kernel's query records
     bool mx4;
+    // the 6-bit storage (LMI_MX6 with LMI_Q_MX6): the Ring8MX6 family, qbuf
+    // holds prep_mx6_kernel's query records
+    bool mx6;
     int32_t split_s;    // row parts of a tail-split chunk (1: the tail split is off)
     int32_t list_stride;  // partial-list slots per pair: split_s * max(max_chunks, 1)
     int32_t max_tiles;
@@ -319,6 +335,7 @@ const char* metric_name(int32_t metric);
 // Both speak for the 4-bit storage too (LMI_MX4 with LMI_Q_MX4, by that name):
 // i8_gate refuses what it refuses of LMI_I8, and d_pad != kMx4DPad, and k =
 // 11..16 off a thread that set lmi_scan_set_i8_lists16; i8_refuse refuses it.
+// And for the 6-bit storage (LMI_MX6 with LMI_Q_MX6), in the same words.
 int i8_gate(const char* fn, const lmi_index_desc* idx, int32_t k, int32_t qmode);
 int i8_refuse(const char* fn, const lmi_index_desc* idx);
 // the 8-wave ring serves this index and query class (the float64 mode's band lists)

@@ -219,10 +219,11 @@ class LearnedIndex(Logger):
         e.g. "i8" for the lossy 8-bit one -- search then answers from float32
         lists of the quantised distances whatever the inputs' dtypes -- or
         "mx4", the 4-bit MXFP4 one (768-wide rows, no `tags`, the cosine
-        alone), made for keep_rows=True with rerank=16.
-        `keep_rows` (an addition; storage "i8" or "mx4"): the 8-bit index also
+        alone), made for keep_rows=True with rerank=16 -- or "mx6", the 6-bit
+        MXFP6 one, on the same terms.
+        `keep_rows` (an addition; storage "i8", "mx4" or "mx6"): the 8-bit index also
         keeps the fp16 rows (DeviceIndex's `keep_rows`).  `rerank` = k2 (an
-        addition; needs storage="i8" or "mx4" and keep_rows=True, 10 < k2 <= 16): search
+        addition; needs storage="i8", "mx4" or "mx6" and keep_rows=True, 10 < k2 <= 16): search
         then scans k2-entry 8-bit lists and re-ranks each to its 10 entries by
         the float64 distances of the kept rows (Searcher.search's `rerank`):
         exact float64 distances on an approximate candidate set.  ValueError
@@ -248,8 +249,9 @@ class LearnedIndex(Logger):
         if rerank is not None:
             if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
                 raise ValueError("rerank must be an integer")
-            if storage not in ("i8", "mx4") or not keep_rows:
-                raise ValueError("rerank needs storage='i8' or 'mx4' and keep_rows=True (the rows it re-ranks from)")
+            if storage not in ("i8", "mx4", "mx6") or not keep_rows:
+                raise ValueError("rerank needs storage='i8', 'mx4' or 'mx6' and keep_rows=True (the rows it "
+                                 "re-ranks from)")
             if not 10 < int(rerank) <= _lib.LMI_MAX_K:
                 raise ValueError(f"rerank = {int(rerank)} must lie in (10, {_lib.LMI_MAX_K}] (search's lists "
                                  "have 10 entries)")
@@ -369,12 +371,12 @@ class LearnedIndex(Logger):
         q_nav = data_X_to_torch(queries_navigation).to(index.device)
         # (the 8-bit storage answers float32 lists whatever the inputs' dtypes,
         # or -- attach(..., rerank=k2) -- float64 ones re-ranked from its fp16 rows)
-        rerank = self._rerank if index.storage in ("i8", "mx4") and index.rows16 is not None else None
+        rerank = self._rerank if index.storage in ("i8", "mx4", "mx6") and index.rows16 is not None else None
         return self._get_searcher(index).search(q_nav, _upload_queries(queries_search, index.device),
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist="f64" if rerank is not None else
-                                                "f32" if index.storage in ("i8", "mx4") or index.metric != "cosine" else
+                                                "f32" if index.storage in ("i8", "mx4", "mx6") or index.metric != "cosine" else
                                                 dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
                                                 timings=timings, want=want, avoid=avoid, rerank=rerank)

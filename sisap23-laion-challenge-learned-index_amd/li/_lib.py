@@ -43,6 +43,8 @@ LMI_Q_F32 = 1
 LMI_Q_I8 = 2
 LMI_MX4 = 3   # 4-bit storage: MXFP4 codes and scale bytes (lmi_quantize_rows_mx4), with LMI_Q_MX4
 LMI_Q_MX4 = 3
+LMI_MX6 = 4   # 6-bit storage: MXFP6 fragments and scale bytes (lmi_quantize_rows_mx6), with LMI_Q_MX6
+LMI_Q_MX6 = 4
 LMI_METRIC_COSINE = 0  # lmi_bucket_topk_metric: 1 - cos, the squared Euclidean distance, -<q, y>
 LMI_METRIC_L2 = 1
 LMI_METRIC_IP = 2
@@ -124,6 +126,7 @@ EXPORTS = (
     "lmi_index_ingest_rows",
     "lmi_quantize_rows_i8",
     "lmi_quantize_rows_mx4",
+    "lmi_quantize_rows_mx6",
     "lmi_index_move_rows_inplace",
     "lmi_bucket_sort_labels_ws_bytes",
     "lmi_bucket_sort_labels",
@@ -280,6 +283,7 @@ _SIGNATURES = {
     "lmi_index_ingest_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "lmi_quantize_rows_i8": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
     "lmi_quantize_rows_mx4": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "lmi_quantize_rows_mx6": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "lmi_index_move_rows_inplace": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P,
                                               _I32, _P, _I64, _P, _P, _I64, _I32, _P, _P]),
     "lmi_bucket_sort_labels_ws_bytes": (C.c_size_t, [_I64, _I32]),

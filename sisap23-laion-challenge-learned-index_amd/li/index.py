@@ -151,24 +151,29 @@ I8_MAX_D_PAD = 992  # the 8-bit scan's widest row (its query tile in LDS)
 
 
 MX4_D_PAD = 768     # the 4-bit scan's one width
-QUANTIZED = ("i8", "mx4")  # the lossy storages: codes quantised on the device, float32 lists of <= 16 entries
+QUANTIZED = ("i8", "mx4", "mx6")  # the lossy storages: codes quantised on the device, float32 lists of <= 16 entries
+# the block-scaled ones, both at d_pad 768 alone: (name in messages, code bytes of a 32-column block, descriptor
+# dtype, query class, quantiser)
+MX = {"mx4": ("4-bit", 16, _lib.LMI_MX4, _lib.LMI_Q_MX4, "lmi_quantize_rows_mx4"),
+      "mx6": ("6-bit", 24, _lib.LMI_MX6, _lib.LMI_Q_MX6, "lmi_quantize_rows_mx6")}
 
 
 def _check_i8_build(capacity, subcluster: bool, world: int, d: int, storage: str = "i8", tags=None) -> None:
-    """What an index of storage "i8" or "mx4" refuses at construction, before
-    anything is allocated."""
+    """What an index of storage "i8", "mx4" or "mx6" refuses at construction,
+    before anything is allocated."""
     if capacity is not None:
         raise ValueError(f"storage {storage!r}: no reserved capacity (a quantised index takes no updates)")
     if subcluster:
         raise ValueError(f"storage {storage!r} takes no sub-cluster layout (subcluster=True)")
     if world > 1:
         raise ValueError(f"storage {storage!r} is offered on one GPU (world == 1), not on a striped index")
-    if storage == "mx4":
+    if storage in MX:
         if (int(d) + 31) // 32 * 32 != MX4_D_PAD:
-            raise ValueError(f"storage 'mx4' takes rows of {MX4_D_PAD - 31} to {MX4_D_PAD} values (d_pad == "
+            raise ValueError(f"storage {storage!r} takes rows of {MX4_D_PAD - 31} to {MX4_D_PAD} values (d_pad == "
                              f"{MX4_D_PAD}), not {int(d)}")
         if tags is not None:
-            raise ValueError("storage 'mx4' takes no tags (filtered search is not offered on the 4-bit storage)")
+            raise ValueError(f"storage {storage!r} takes no tags (filtered search is not offered on the "
+                             f"{MX[storage][0]} storage)")
     elif (int(d) + 31) // 32 * 32 > I8_MAX_D_PAD:
         raise ValueError(f"storage 'i8' takes rows of at most {I8_MAX_D_PAD} values, not {int(d)}")
 
@@ -179,9 +184,9 @@ def check_i8(index, what: str) -> None:
     if getattr(index, "storage", None) == "i8":
         raise ValueError(f"{what} is not offered on storage 'i8' (the 8-bit storage answers float32 lists of "
                          f"at most {_lib.LMI_MAX_K} entries on one GPU)")
-    if getattr(index, "storage", None) == "mx4":
-        raise ValueError(f"{what} is not offered on storage 'mx4' (the 4-bit storage answers unfiltered float32 "
-                         f"lists of at most {_lib.LMI_MAX_K} entries on one GPU)")
+    if getattr(index, "storage", None) in MX:
+        raise ValueError(f"{what} is not offered on storage {index.storage!r} (the {MX[index.storage][0]} storage "
+                         f"answers unfiltered float32 lists of at most {_lib.LMI_MAX_K} entries on one GPU)")
 
 
 METRICS = {"cosine": _lib.LMI_METRIC_COSINE, "l2": _lib.LMI_METRIC_L2, "ip": _lib.LMI_METRIC_IP}
@@ -275,16 +280,48 @@ def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm:
         ptr(dst_rows), ptr(codes), ptr(inv_norm), s))
 
 
-def mx4_views(store: torch.Tensor, n_rows: int, d_pad: int):
-    """(codes uint8 [n_rows, d_pad / 2], scales uint8 [n_rows, d_pad / 32]): the
-    two arrays of an LMI_MX4 store (a flat uint8 tensor of mx4_store_bytes)."""
-    off = (n_rows * (d_pad // 2) + 255) // 256 * 256  # LMI_MX4_SCALE_OFFSET
-    return (store[: n_rows * (d_pad // 2)].view(n_rows, d_pad // 2),
+def mx4_views(store: torch.Tensor, n_rows: int, d_pad: int, storage: str = "mx4"):
+    """(codes uint8 [n_rows, cb], scales uint8 [n_rows, d_pad / 32]): the two
+    arrays of an LMI_MX4 / LMI_MX6 store (a flat uint8 tensor of
+    mx4_store_bytes); cb = d_pad / 2 code bytes a row on "mx4", d_pad * 3 / 4
+    (24-byte fragments) on "mx6"."""
+    cb = d_pad // 32 * MX[storage][1]
+    off = (n_rows * cb + 255) // 256 * 256  # LMI_MX4_SCALE_OFFSET / LMI_MX6_SCALE_OFFSET
+    return (store[: n_rows * cb].view(n_rows, cb),
             store[off: off + n_rows * (d_pad // 32)].view(n_rows, d_pad // 32))
 
 
-def mx4_store_bytes(n_rows: int, d_pad: int) -> int:
-    return (n_rows * (d_pad // 2) + 255) // 256 * 256 + n_rows * (d_pad // 32)
+def mx4_store_bytes(n_rows: int, d_pad: int, storage: str = "mx4") -> int:
+    return (n_rows * (d_pad // 32 * MX[storage][1]) + 255) // 256 * 256 + n_rows * (d_pad // 32)
+
+
+def _quantize_rows_mx(storage: str, rows, d_pad: int, codes, scales, inv_norm, dst_rows, stream) -> None:
+    fn, cb = MX[storage][4], d_pad // 32 * MX[storage][1]
+    name = fn[4:]
+    if rows.dtype not in (torch.float16, torch.float32):
+        rows = rows.float()
+    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        rows = rows.contiguous()
+    m, d = int(rows.shape[0]), int(rows.shape[1])
+    slots = int(codes.shape[0])
+    if codes.dtype != torch.uint8 or tuple(codes.shape) != (slots, cb) or not codes.is_contiguous() \
+            or scales.dtype != torch.uint8 or tuple(scales.shape) != (slots, d_pad // 32) \
+            or not scales.is_contiguous() or inv_norm.dtype != torch.float32 or inv_norm.shape != (slots,) \
+            or not inv_norm.is_contiguous():
+        raise ValueError(f"{name}: codes uint8 [slots, {cb}], scales uint8 [slots, d_pad/32] and "
+                         "inv_norm float32 [slots], contiguous")
+    if dst_rows is None:
+        if slots < m:
+            raise ValueError(f"{name}: fewer slots than rows")
+    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
+        raise ValueError(f"{name}: dst_rows must be a contiguous int64 [m] device tensor")
+    if m == 0:
+        return
+    ld = max(int(rows.stride(0)), d)
+    s = stream if stream is not None else _lib.stream_handle(codes.device)
+    check(fn, getattr(_lib.load(), fn)(
+        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
+        ptr(dst_rows), ptr(codes), ptr(scales), ptr(inv_norm), s))
 
 
 def quantize_rows_mx4(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, scales: torch.Tensor,
@@ -293,30 +330,14 @@ def quantize_rows_mx4(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, scale
     codes [slots, d_pad / 2], scale bytes [slots, d_pad / 32] (uint8) and the
     codes' 1/n in `inv_norm` [slots] -- row i in slot dst_rows[i] or, without
     dst_rows, slot i.  Every slot named must exist: the kernel does not check."""
-    if rows.dtype not in (torch.float16, torch.float32):
-        rows = rows.float()
-    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
-        rows = rows.contiguous()
-    m, d = int(rows.shape[0]), int(rows.shape[1])
-    slots = int(codes.shape[0])
-    if codes.dtype != torch.uint8 or tuple(codes.shape) != (slots, d_pad // 2) or not codes.is_contiguous() \
-            or scales.dtype != torch.uint8 or tuple(scales.shape) != (slots, d_pad // 32) \
-            or not scales.is_contiguous() or inv_norm.dtype != torch.float32 or inv_norm.shape != (slots,) \
-            or not inv_norm.is_contiguous():
-        raise ValueError("quantize_rows_mx4: codes uint8 [slots, d_pad/2], scales uint8 [slots, d_pad/32] and "
-                         "inv_norm float32 [slots], contiguous")
-    if dst_rows is None:
-        if slots < m:
-            raise ValueError("quantize_rows_mx4: fewer slots than rows")
-    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
-        raise ValueError("quantize_rows_mx4: dst_rows must be a contiguous int64 [m] device tensor")
-    if m == 0:
-        return
-    ld = max(int(rows.stride(0)), d)
-    s = stream if stream is not None else _lib.stream_handle(codes.device)
-    check("lmi_quantize_rows_mx4", _lib.load().lmi_quantize_rows_mx4(
-        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
-        ptr(dst_rows), ptr(codes), ptr(scales), ptr(inv_norm), s))
+    _quantize_rows_mx("mx4", rows, d_pad, codes, scales, inv_norm, dst_rows, stream)
+
+
+def quantize_rows_mx6(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, scales: torch.Tensor,
+                      inv_norm: torch.Tensor, dst_rows: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lmi_quantize_rows_mx6: as quantize_rows_mx4, with MXFP6 codes
+    [slots, d_pad * 3 / 4]: d_pad / 32 fragments of 24 bytes a row."""
+    _quantize_rows_mx("mx6", rows, d_pad, codes, scales, inv_norm, dst_rows, stream)
 
 
 # ---------------------------------------------------------------------------
@@ -365,7 +386,12 @@ class DeviceIndex:
     than cosine; lists of 11..16 entries need lists16=True.  Made for
     keep_rows + rerank=16: 16 candidates a pair re-scored from the fp16 rows.
 
-    keep_rows=True (storage "i8" or "mx4"): the index also holds `rows16`, the
+    "mx6" (opt-in, never picked by "auto"): the lossy 6-bit storage -- MXFP6
+    (lmi_quantize_rows_mx6: E2M3 codes, 32 of them a 24-byte fragment, one E8M0
+    scale byte per fragment), `codes` [n_rows, d_pad * 3 / 4]; everything else
+    as "mx4", its refusals included.
+
+    keep_rows=True (storage "i8", "mx4" or "mx6"): the index also holds `rows16`, the
     bucket-sorted fp16 rows [n_rows, d_pad] (zero past d; row r of `rows16` is
     row r of `corpus`, so a list's position indexes both).  Searcher.lists /
     search(..., dist="f64", rerank=k2) then scan k2-entry 8-bit lists and
@@ -376,8 +402,8 @@ class DeviceIndex:
     index of storage "f16" shares that index's corpus tensor (no copy): the
     source must then not be updated in place while this index is in use."""
 
-    rows16 = None  # the fp16 rows kept beside the codes (storage "i8" / "mx4", keep_rows=True)
-    codes = scales = None  # storage "mx4": the two arrays of the flat store `corpus` (mx4_views)
+    rows16 = None  # the fp16 rows kept beside the codes (storage "i8" / "mx4" / "mx6", keep_rows=True)
+    codes = scales = None  # storage "mx4" / "mx6": the two arrays of the flat store `corpus` (mx4_views)
     _rows_desc = None  # the descriptor over rows16 (rows_desc)
     corpus64 = None  # float64 rows (float64 input that float32 rounding changes)
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
@@ -437,7 +463,7 @@ class DeviceIndex:
         self.metric = metric
         if keep_rows:
             if storage not in QUANTIZED:
-                raise ValueError("keep_rows: the fp16 rows are kept beside storage 'i8' or 'mx4' alone, not "
+                raise ValueError("keep_rows: the fp16 rows are kept beside storage 'i8', 'mx4' or 'mx6' alone, not "
                                  f"{storage!r}")
             if isinstance(data, RowSource):
                 raise ValueError(f"keep_rows: a RowSource builds storage {storage!r} so that no fp16 copy exists")
@@ -539,14 +565,14 @@ class DeviceIndex:
                           torch.empty((cap,), dtype=torch.float32, device=self.device), n_rows)
 
     def _alloc_mx4(self, n_rows: int):
-        """The store of storage "mx4": one flat uint8 tensor (codes, then the
-        scale bytes at LMI_MX4_SCALE_OFFSET) as `corpus`, its two arrays as
+        """The store of storage "mx4" / "mx6": one flat uint8 tensor (codes, then the
+        scale bytes at LMI_MX4_SCALE_OFFSET / LMI_MX6_SCALE_OFFSET) as `corpus`, its two arrays as
         `codes` / `scales`, and `inv_norm`; nothing is reserved."""
-        self._store = self.corpus = torch.empty((max(mx4_store_bytes(n_rows, self.d_pad), 256),),
+        self._store = self.corpus = torch.empty((max(mx4_store_bytes(n_rows, self.d_pad, self.storage), 256),),
                                                 dtype=torch.uint8, device=self.device)
         self._store_inv = self.inv_norm = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
         self._capacity = n_rows
-        self.codes, self.scales = mx4_views(self.corpus, n_rows, self.d_pad)
+        self.codes, self.scales = mx4_views(self.corpus, n_rows, self.d_pad, self.storage)
         self._desc = self._desc32 = self._desc64 = None
 
     def _adopt_store(self, store, store_inv, n_rows: int, inv64: bool = False):
@@ -727,14 +753,14 @@ class DeviceIndex:
         shard (world > 1), duplicate ids, words outside [0, 2^32); an id the
         index does not hold raises as `remove` reports it (a KeyError that is a
         ValueError too); a consumed index raises as every call on it does."""
-        if self.storage == "mx4":
+        if self.storage in MX:
             check_i8(self, "edit_tags")
         index_update.edit_tags(self, ids, set_bits, clear_bits)
 
     def set_tags(self, ids, tags) -> None:
         """The tag words of the stored objects `ids` := `tags` (an int or one
         word per id): edit_tags with every bit cleared first."""
-        if self.storage == "mx4":
+        if self.storage in MX:
             check_i8(self, "set_tags")
         index_update.edit_tags(self, ids, tags, 0xFFFFFFFF)
 
@@ -838,8 +864,8 @@ class DeviceIndex:
             storage = "f16" if src.dtype == torch.float16 or all(
                 fp16_exact(src[a:a + step].to(self.device)) for a in range(0, n, step)) else \
                 ("f32x" if self.d_pad == SPLIT_D_PAD and self.metric == "cosine" else "f32")
-        if storage not in ("f16", "f32", "f32x", "i8", "mx4"):
-            raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x', 'i8' or 'mx4'")
+        if storage not in ("f16", "f32", "f32x", "i8", "mx4", "mx6"):
+            raise ValueError("storage must be 'auto', 'f16', 'f32', 'f32x', 'i8', 'mx4' or 'mx6'")
         if storage == "f32x" and self.d_pad != SPLIT_D_PAD:
             raise ValueError(f"storage='f32x' needs d_pad {SPLIT_D_PAD}")
         self.storage = storage
@@ -856,7 +882,7 @@ class DeviceIndex:
             if keep and src.dtype != torch.float16 and not all(
                     fp16_exact(src[a:a + step]) for a in range(0, n, step)):
                 raise ValueError("keep_rows needs fp16-representable data (the rule of storage='f16')")
-            if storage == "mx4":
+            if storage in MX:
                 self._alloc_mx4(n_rows)
             else:
                 self._alloc_store(n_rows, torch.int8)
@@ -864,9 +890,9 @@ class DeviceIndex:
                 self.rows16 = torch.zeros((n_rows, self.d_pad), dtype=torch.float16, device=self.device)
             for a in range(0, n_rows, step):
                 blk = src.index_select(0, rows[a:a + step].to(src.device)).to(self.device)
-                if storage == "mx4":
-                    quantize_rows_mx4(blk, self.d_pad, self.codes[a:a + step], self.scales[a:a + step],
-                                      self.inv_norm[a:a + step])
+                if storage in MX:
+                    _quantize_rows_mx(storage, blk, self.d_pad, self.codes[a:a + step], self.scales[a:a + step],
+                                      self.inv_norm[a:a + step], None, None)
                 else:
                     quantize_rows(blk, self.d_pad, self.corpus[a:a + step], self.inv_norm[a:a + step])
                 if keep:
@@ -925,15 +951,15 @@ class DeviceIndex:
         n = self.n_total
         if src.n != n:
             raise ValueError("RowSource must have one row per label")
-        if storage not in ("auto", "f16", "i8", "mx4"):
-            raise ValueError("a RowSource builds storage 'f16' ('auto'), 'i8' or 'mx4'")
+        if storage not in ("auto", "f16", "i8", "mx4", "mx6"):
+            raise ValueError("a RowSource builds storage 'f16' ('auto'), 'i8', 'mx4' or 'mx6'")
         if storage in QUANTIZED:
             check_metric(self, f"storage {storage!r}")
         self.d = src.d
         self.d_pad = (self.d + 31) // 32 * 32
         self.storage = storage if storage in QUANTIZED else "f16"
         n_rows = int(gpos.size)
-        if self.storage == "mx4":
+        if self.storage in MX:
             self._alloc_mx4(n_rows)
         elif self.storage == "i8":
             self._alloc_store(n_rows, torch.int8)
@@ -949,8 +975,8 @@ class DeviceIndex:
             m = sl >= 0
             dst = sl[m]
             x = blk[m]
-            if self.storage == "mx4":
-                quantize_rows_mx4(x, self.d_pad, self.codes, self.scales, self.inv_norm, dst_rows=dst)
+            if self.storage in MX:
+                _quantize_rows_mx(self.storage, x, self.d_pad, self.codes, self.scales, self.inv_norm, dst, None)
                 del blk, x
                 continue
             if self.storage == "i8":
@@ -1045,7 +1071,7 @@ class DeviceIndex:
 
     @torch.no_grad()
     def quantized(self, keep_rows: bool = False, storage: str = "i8") -> "DeviceIndex":
-        """A NEW index of storage "i8" (or `storage` = "mx4": lmi_quantize_rows_mx4,
+        """A NEW index of storage "i8" (or `storage` = "mx4" / "mx6": lmi_quantize_rows_mx4 / _mx6,
         d_pad 768, an untagged index) with this one's rows quantised on the
         device (lmi_quantize_rows_i8 over the stored rows): the same layout,
         ids, tags and chunk tables, and bitwise the index
@@ -1058,7 +1084,7 @@ class DeviceIndex:
         this index in place while the new one is in use."""
         self._check_live()
         if storage not in QUANTIZED:
-            raise ValueError(f"quantized: storage must be 'i8' or 'mx4', not {storage!r}")
+            raise ValueError(f"quantized: storage must be 'i8', 'mx4' or 'mx6', not {storage!r}")
         check_metric(self, f"quantized() (storage {storage!r})")
         if self.storage not in ("f16", "f32"):
             raise ValueError(f"quantized: storage {self.storage!r} is not supported (only 'f16' and 'f32')")
@@ -1071,9 +1097,10 @@ class DeviceIndex:
         _check_i8_build(None, False, 1, self.d, storage, self.tags_by_pos)
         new = self._successor(self.layout, self.pos_to_id, self.tags_by_pos)
         new.storage = storage
-        if storage == "mx4":
+        if storage in MX:
             new._alloc_mx4(self.n_rows)
-            quantize_rows_mx4(self.corpus[:, : self.d], self.d_pad, new.codes, new.scales, new.inv_norm)
+            _quantize_rows_mx(storage, self.corpus[:, : self.d], self.d_pad, new.codes, new.scales, new.inv_norm,
+                              None, None)
         else:
             new._adopt_store(torch.empty((self.n_rows, self.d_pad), dtype=torch.int8, device=self.device),
                              torch.empty((self.n_rows,), dtype=torch.float32, device=self.device), self.n_rows)
@@ -1089,7 +1116,7 @@ class DeviceIndex:
         takes: the rows, their width and count; nothing else is read."""
         self._check_live()
         if self.rows16 is None:
-            raise ValueError("this index keeps no fp16 rows (build it with storage='i8' or 'mx4', keep_rows=True)")
+            raise ValueError("this index keeps no fp16 rows (build it with storage='i8', 'mx4' or 'mx6', keep_rows=True)")
         if self._rows_desc is None:
             d = _lib.IndexDesc()
             d.corpus = ptr(self.rows16)
@@ -1141,7 +1168,7 @@ class IndexDescHolder:
         d = _lib.IndexDesc()
         d.corpus = ptr(ix.corpus32 if general32 else ix.corpus)
         d.dtype = _lib.LMI_F32 if (general32 or ix.storage == "f32") else \
-            _lib.LMI_I8 if ix.storage == "i8" else _lib.LMI_MX4 if ix.storage == "mx4" else _lib.LMI_F16
+            _lib.LMI_I8 if ix.storage == "i8" else MX[ix.storage][2] if ix.storage in MX else _lib.LMI_F16
         d.d = ix.d
         d.d_pad = ix.d_pad
         d.n_rows = ix.n_rows
@@ -1328,13 +1355,13 @@ class i8_lists16:
         _lib.load().lmi_scan_set_i8_lists16(self.prev)
 
 
-def check_mx4_k(k: int) -> None:
-    """The lists storage "mx4" scans: at most 10 entries, or at most 16 inside
+def check_mx4_k(k: int, storage: str = "mx4") -> None:
+    """The lists storage "mx4" / "mx6" scans: at most 10 entries, or at most 16 inside
     i8_lists16() (lists16=True); ValueError otherwise, before anything is launched."""
     if k > _lib.LMI_MAX_K:
-        raise ValueError(f"storage 'mx4' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
+        raise ValueError(f"storage {storage!r} takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
     if k > 10 and getattr(i8_lists16.on, "depth", 0) == 0:
-        raise ValueError(f"storage 'mx4' takes lists of {k} entries with lists16=True alone (its ring has 10- "
+        raise ValueError(f"storage {storage!r} takes lists of {k} entries with lists16=True alone (its ring has 10- "
                          "and 16-entry lists)")
 
 
@@ -1377,11 +1404,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
             raise ValueError(f"storage 'i8' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
         # (the one query class of the 8-bit storage; its scan is never seeded)
         qmode, seed_round0 = _lib.LMI_Q_I8, False
-    if index.storage == "mx4":
-        check_mx4_k(k)
+    if index.storage in MX:
+        check_mx4_k(k, index.storage)
         if want is not None or avoid is not None:
             check_i8(index, "filtered search (want / avoid)")
-        qmode, seed_round0 = _lib.LMI_Q_MX4, False
+        qmode, seed_round0 = MX[index.storage][3], False
     if qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     if index.metric != "cosine":
@@ -1424,13 +1451,14 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     return out_d, out_pos, status
 
 
-SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8", "ring8-mx4")
+SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8", "ring8-mx4", "ring8-mx6")
 
 
 def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None,
                 lists16: bool = False) -> str:
     """The kernel family bucket_topk (tagged: with want / avoid) of this index
-    and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" | "ring8-mx4" -- as
+    and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" | "ring8-mx4" |
+    "ring8-mx6" -- as
     lmi_scan_family reads it from the plan the launch uses (the diagnostic
     switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk;
     `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan."""
@@ -1439,8 +1467,8 @@ def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optiona
             return scan_family(index, k, tagged, qmode)
     if index.storage == "i8":
         qmode = _lib.LMI_Q_I8
-    elif index.storage == "mx4":
-        qmode = _lib.LMI_Q_MX4
+    elif index.storage in MX:
+        qmode = MX[index.storage][3]
     elif qmode is None:
         qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
     fam = _lib.load().lmi_scan_family(C.byref(index.desc_for(k)), k, qmode, 1 if tagged else 0)
@@ -1697,7 +1725,7 @@ def check_rerank(index: DeviceIndex, rerank, k_list: int, dist: str) -> None:
     if isinstance(rerank, bool) or not isinstance(rerank, (int, np.integer)):
         raise ValueError("rerank must be an integer (the entries of the 8-bit lists to re-rank)")
     if getattr(index, "storage", None) not in QUANTIZED:
-        raise ValueError(f"rerank: re-ranking is for storage 'i8' or 'mx4', not {getattr(index, 'storage', None)!r}")
+        raise ValueError(f"rerank: re-ranking is for storage 'i8', 'mx4' or 'mx6', not {getattr(index, 'storage', None)!r}")
     if getattr(index, "rows16", None) is None:
         raise ValueError("rerank: this index keeps no fp16 rows (build it with keep_rows=True)")
     if dist != "f64":
@@ -2034,8 +2062,8 @@ class Searcher:
         batch, so every rank decides the same."""
         if self.index.storage == "i8":
             return _lib.LMI_Q_I8  # (the queries are quantised inside the call)
-        if self.index.storage == "mx4":
-            return _lib.LMI_Q_MX4
+        if self.index.storage in MX:
+            return MX[self.index.storage][3]
         if self.index.storage != "f16":
             return _lib.LMI_Q_F32
         import weakref
@@ -2129,7 +2157,7 @@ class Searcher:
               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
               lists16: bool = False):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
-        `lists16`: the call runs inside i8_lists16() -- storage "mx4" needs it
+        `lists16`: the call runs inside i8_lists16() -- storage "mx4" / "mx6" needs it
         for k_list = 11..16, storage "i8" takes its ring's 16-entry lists with it.
         `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64",
         k_list < k2 <= 16): the 8-bit scan keeps k2 entries a pair and their
@@ -2152,7 +2180,7 @@ class Searcher:
         check_stop(stop_mass, min_probes)
         self.index._check_live()
         self._check_i8_lists(k_list, dist, rerank)
-        if self.index.storage == "mx4" and (want is not None or avoid is not None):
+        if self.index.storage in MX and (want is not None or avoid is not None):
             check_i8(self.index, "filtered search (want / avoid)")
         if want is not None or avoid is not None:
             check_metric(self.index, "filtered search (want / avoid)")
@@ -2187,8 +2215,8 @@ class Searcher:
                 check_i8(self.index, "dist='f64' (float64 lists)")
             if k_list > _lib.LMI_MAX_K:
                 check_i8(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
-        if self.index.storage == "mx4":
-            check_mx4_k(k_list)
+        if self.index.storage in MX:
+            check_mx4_k(k_list, self.index.storage)
 
     def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
         """K1 classes [nq, R]; with G > 1 ranks each routes nq/G queries and
@@ -2438,7 +2466,7 @@ class Searcher:
                lists16: bool = False):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
 
-        `lists16`: as in lists (storage "mx4" with lists of 11..16 entries).
+        `lists16`: as in lists (storage "mx4" / "mx6" with lists of 11..16 entries).
 
         `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64"; as
         in lists): the lists the merge or the replay reads are the k2-entry
@@ -2494,7 +2522,7 @@ class Searcher:
                                    rerank=rerank)
         check_stop(stop_mass, min_probes)
         self.index._check_live()
-        if self.index.storage == "mx4" and (want is not None or avoid is not None):
+        if self.index.storage in MX and (want is not None or avoid is not None):
             check_i8(self.index, "filtered search (want / avoid)")
         if replay_on not in ("device", "host"):
             raise ValueError("replay_on must be 'device' or 'host'")
