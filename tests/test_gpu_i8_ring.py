@@ -13,7 +13,9 @@ whose `classes` are written out so that the buckets receive
 (1, 31, 32, 33, 255, 256, 257, 4, 258) probing pairs: one live lane, a partial
 wave, one full wave, a wave plus one, a tile one short, a full tile, a tile plus
 a one-pair tile, a few probes of the empty bucket, and on the 300-row bucket a
-full tile plus a two-pair tile; one class lies outside [0, C)."""
+full tile plus a two-pair tile; one class lies outside [0, C).
+These fixtures stop at 16 blocks a tile; tiles of 32 and more blocks (the bound
+exchange, the ring's steady state) are in test_gpu_ring_long.py."""
 import functools
 import os
 

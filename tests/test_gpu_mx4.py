@@ -2,7 +2,8 @@
 scan3_mx4_kernel) against the numpy restatement of tests/mx4_cases.py, on the i8
 ring's fixture shape: chunk_rows = 64, R = 2, buckets of (1, 31, 32, 33, 64, 65,
 97, 0, 300) rows probed by (1, 31, 32, 33, 255, 256, 257, 4, 258) pairs, one
-class outside [0, C).
+class outside [0, C).  These fixtures stop at 2 blocks a tile; the ring's steady state
+(in-loop DMA, slot and norm-area wraps, the bound exchange) is in test_gpu_ring_long.py.
 
 tol = d_pad * 2^-23: any fp32 summation order of n terms errs by at most
 (n - 1) 2^-24 sum |terms|, sum |q^ y^| invq invy <= 1, and tol is twice that."""
@@ -152,10 +153,16 @@ def test_search_and_phases_run_on_the_lists():
 
 
 # ---- 3. exact inputs, bit for bit -----------------------------------------------------------------
-@pytest.mark.parametrize("k", [10, 16])
-def test_exact_inputs_bit_for_bit(k):
+SAME = (3, 9, 60, 64, 70, 127, 128, 130, 190, 200, 255, 256, 257, 300, 319, 320, 321, 350, 382, 383)
+
+
+def _exact_inputs(k, sizes, same, chunk):
+    """Grid-valued rows and queries (the codes hold them exactly, the sums are exact
+    in float32) in two buckets of `sizes` rows; the 20 rows `same` of bucket 0 are
+    equal and query 0 is twice them.  Every list bit for bit against distances32."""
     rng = np.random.default_rng(4410)
-    sizes, d, nq = (384, 33), 768, 40
+    d, nq = 768, 40
+    same = np.asarray(same)
     n = sum(sizes)
 
     def grid(m):
@@ -164,12 +171,11 @@ def test_exact_inputs_bit_for_bit(k):
         return (v * 2.0 ** rng.integers(-3, 4, (m, 1))).astype(np.float32)
     x, q = grid(n), grid(nq)
     labels = np.repeat(np.arange(2), sizes).astype(np.int64)
-    same = np.array([3, 9, 60, 64, 70, 127, 128, 130, 190, 200, 255, 256, 257, 300, 319, 320, 321, 350, 382, 383])
-    assert same.size == 20 and np.unique(same // CHUNK).size == 6
+    assert same.size == 20
     x[same] = x[same[0]]
     q[0] = x[same[0]] * 2.0
     classes = np.tile(np.array([[0, 1]], np.int32), (nq, 1))
-    s = Searcher(DeviceIndex(x, labels, 2, chunk_rows=CHUNK, device=DEV, storage="mx4"), None)
+    s = Searcher(DeviceIndex(x, labels, 2, chunk_rows=chunk, device=DEV, storage="mx4"), None)
     assert np.array_equal(s.index.layout.order, np.arange(n))
     vq, iq, vy, iy = _restate(x, q, s.index)
     assert np.array_equal(vy, x) and np.array_equal(vq, q)        # the codes hold the inputs exactly
@@ -184,6 +190,12 @@ def test_exact_inputs_bit_for_bit(k):
             best = rows[np.lexsort((rows, dist[i, rows]))][:k]
             assert np.array_equal(got_p[i, r, :best.size], best), (i, r)
             assert np.array_equal(got_d[i, r, :best.size].view(np.uint32), dist[i, best].view(np.uint32)), (i, r)
+
+
+@pytest.mark.parametrize("k", [10, 16])
+def test_exact_inputs_bit_for_bit(k):
+    assert np.unique(np.array(SAME) // CHUNK).size == 6
+    _exact_inputs(k, (384, 33), SAME, CHUNK)
 
 
 # ---- 4. re-rank -----------------------------------------------------------------------------------
