@@ -351,6 +351,33 @@ int lmi_bucket_topk_metric(const lmi_index_desc* idx, int32_t metric, const floa
                            float* out_d, int32_t* out_pos, int32_t* status, void* workspace,
                            size_t ws_bytes, void* stream);
 
+/* K2 for a few queries (additions: LMI_ABI_VERSION does not change):
+ * lmi_bucket_topk's cosine lists -- fp16 rows, queries taken as LMI_Q_F16, 1 <= k
+ * <= LMI_MAX_K, float32 distances, the same outputs and status bits -- for a
+ * call of at most LMI_FEW_MAX_PAIRS pairs (nq * R), by a kernel that cuts every
+ * probed bucket into slices of few_rows rows so that one query spreads over
+ * every CU (scan_few_kernel).  few_rows is a multiple of 32, or 0: the call then
+ * chooses it (about six slices per CU, at least 256 rows); the index's
+ * chunk_rows plays no part.  A few_rows above the largest bucket the index can
+ * hold (max_chunks * chunk_rows), or above 2^30 / (2 d_pad) rows, is cut to that
+ * cap, not refused.  The call's own choice reads the scan's workgroup count
+ * (lmi_scan_set_workgroups, LMI_SCAN_WGS), so the workspace is sized on the
+ * thread, and under the setting, that makes the call.  Nothing selects this
+ * entry automatically.  The
+ * workspace is lmi_scan_few_workspace_bytes of the same (nq, R, k, few_rows),
+ * which is 0 for a call this entry refuses.  Refused before any launch, device
+ * or no device (lmi_last_error names the reason) -- LMI_E_UNSUPPORTED: more
+ * than LMI_FEW_MAX_PAIRS pairs, k > LMI_MAX_K, a storage other than LMI_F16,
+ * d_pad > 992, idx->corpus32 / corpus64 / chunk_centroid; LMI_E_INVALID:
+ * few_rows negative or no multiple of 32, k < 1, join workgroups set on the
+ * thread (lmi_scan_set_join_workgroups).  It has no qmode: no phase, seed or
+ * join flag, no tags and no metric other than cosine can be asked of it. */
+#define LMI_FEW_MAX_PAIRS 256
+size_t lmi_scan_few_workspace_bytes(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, int32_t few_rows);
+int lmi_bucket_topk_few(const lmi_index_desc* idx, const float* q, int32_t nq, int32_t ldq, const int32_t* classes,
+                        int32_t R, int32_t k, int32_t few_rows, void* workspace, size_t ws_bytes, float* out_d,
+                        int32_t* out_pos, int32_t* status, void* stream);
+
 /* The per-row word of LMI_METRIC_L2: sqnorm[t] = sum_j rows[i][j]^2 over j < d,
  * accumulated in float64 and rounded once to float32, t = dst_rows ? dst_rows[i]
  * : i (an index build scatters each block into its bucket-sorted slots).  One

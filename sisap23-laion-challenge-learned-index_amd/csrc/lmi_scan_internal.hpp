@@ -275,6 +275,8 @@ int launch_prep_mx6(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t 
                     hipStream_t s);
 // the one width of the 6-bit storage
 constexpr int kMx6DPad = 768;
+// the widest row of the few-query scan (lmi_scan_few.hip: its query image in LDS)
+constexpr int kFewMaxDPad = 992;
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the

@@ -344,8 +344,11 @@ class LearnedIndex(Logger):
     # ---- search -------------------------------------------------------------
     def search(self, data_navigation, queries_navigation, data_search, queries_search,
                pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference",
-               stop_mass=None, min_buckets=1, timings=None, want=None, avoid=None):
+               stop_mass=None, min_buckets=1, timings=None, want=None, avoid=None, few=False):
         """Search for k nearest neighbors of each query (LearnedIndex.py:22-101).
+        `few` (an addition; default off, nothing turns it on): the scan of
+        Searcher.search(few=True), for a handful of queries -- float32 distances;
+        ValueError for what li.index.check_few names.
         `semantics="exact"` (an addition; default off) returns the exact top-k of
         the union of the probed buckets instead of the reference's round merge.
         `stop_mass` (an addition; default off): adaptive probing -- `n_buckets`
@@ -376,10 +379,10 @@ class LearnedIndex(Logger):
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist="f64" if rerank is not None else
-                                                "f32" if index.storage in ("i8", "mx4", "mx6") or index.metric != "cosine" else
+                                                "f32" if index.storage in ("i8", "mx4", "mx6") or index.metric != "cosine" or few else
                                                 dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
-                                                timings=timings, want=want, avoid=avoid, rerank=rerank)
+                                                timings=timings, want=want, avoid=avoid, rerank=rerank, few=few)
 
     def range_search(self, data_navigation, queries_navigation, data_search, queries_search,
                      pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None,

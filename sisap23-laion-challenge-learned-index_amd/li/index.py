@@ -1367,8 +1367,12 @@ def check_mx4_k(k: int, storage: str = "mx4") -> None:
 
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                 qmode: Optional[int] = None, stream=None, out=None, ws=None,
-                seed_round0: bool = False, phases: int = 0, want=None, avoid=None, lists16: bool = False):
-    """K2 on one shard.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
+                seed_round0: bool = False, phases: int = 0, want=None, avoid=None, lists16: bool = False,
+                few: bool = False, few_rows: Optional[int] = None):
+    """K2 on one shard.  `few` (nothing sets it for the caller): the few-query
+    scan, lmi_bucket_topk_few -- at most 256 pairs, each probed bucket cut into
+    slices of `few_rows` rows (None: the call chooses) so that one query spreads
+    over every CU; ValueError for what check_few names.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
     `out` = such a triple to write into (the status word zeroed by the caller);
     `ws` = a caller-owned uint8 workspace (default: the index's cached one,
     which a later call with a larger batch may replace — a captured graph
@@ -1384,6 +1388,12 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     one bit is the caller's check (mask_words makes it on the host).
     `lists16`: the call runs inside i8_lists16() (storage "i8" at d_pad 768:
     k = 11..16 on the ring's 16-entry lists; the workspace is sized there too)."""
+    if few:
+        return _bucket_topk_few(index, q, classes, k, few_rows, stream, out, ws,
+                                flags=dict(qmode=qmode, seed_round0=seed_round0, phases=phases, want=want,
+                                           avoid=avoid, lists16=lists16))
+    if few_rows is not None:
+        raise ValueError("few_rows comes with few=True")
     if lists16:
         with i8_lists16():
             return bucket_topk(index, q, classes, k, qmode=qmode, stream=stream, out=out, ws=ws,
@@ -1451,17 +1461,89 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     return out_d, out_pos, status
 
 
+FEW_MAX_PAIRS = 256  # LMI_FEW_MAX_PAIRS
+FEW_MAX_D_PAD = 992
+
+
+def check_few(index: DeviceIndex, nq: int, R: int, k: int, few_rows=None, **flags) -> None:
+    """ValueError for what the few-query scan (few=True) does not take, before
+    anything is uploaded or launched: more than 256 pairs (nq * R), k > 16, a
+    storage other than "f16", a metric other than cosine, d_pad > 992, a
+    sub-cluster layout, a striped index, tags (want / avoid), a phase, seed or
+    lists16 flag, a query class other than fp16, `few_rows` that is no positive
+    multiple of 32."""
+    def no(what):
+        raise ValueError(f"few=True (the few-query scan) takes {what}")
+    if nq * R > FEW_MAX_PAIRS:
+        no(f"at most {FEW_MAX_PAIRS} pairs (nq * R), not {nq} * {R}")
+    if not 1 <= k <= _lib.LMI_MAX_K:
+        no(f"k in [1, {_lib.LMI_MAX_K}], not {k}")
+    if index.storage != "f16":
+        no(f"storage 'f16' alone, not {index.storage!r}")
+    if index.metric != "cosine":
+        no(f"metric 'cosine' alone, not {index.metric!r}")
+    if index.d_pad > FEW_MAX_D_PAD:
+        no(f"d_pad <= {FEW_MAX_D_PAD}, not {index.d_pad}")
+    if index.chunk_centroid is not None:
+        no("no sub-cluster layout (subcluster=True)")
+    if getattr(index, "world", 1) > 1:
+        no("one GPU (not a striped index)")
+    if flags.get("want") is not None or flags.get("avoid") is not None:
+        no("no tags (want / avoid)")
+    if flags.get("seed_round0") or flags.get("phases") or flags.get("lists16"):
+        no("no seed, phase or lists16 flag")
+    if flags.get("qmode") not in (None, _lib.LMI_Q_F16):
+        no("fp16-exact queries (LMI_Q_F16) alone")
+    if few_rows is not None and (few_rows <= 0 or few_rows % 32):
+        no(f"few_rows a positive multiple of 32, not {few_rows}")
+
+
+def _bucket_topk_few(index, q, classes, k, few_rows, stream, out, ws, flags):
+    """bucket_topk(few=True): lmi_bucket_topk_few with a workspace of its own size."""
+    lib = _lib.load()
+    q = _rows_f32(q, index.device)
+    classes = _as_torch(classes, index.device, torch.int32)
+    nq, R = classes.shape
+    if q.shape[0] != nq or q.shape[1] != index.d:
+        raise ValueError("query shape does not match the index")
+    check_few(index, nq, R, k, few_rows, **flags)
+    desc, fr = index.desc, int(few_rows or 0)
+    if out is None:
+        out = (torch.empty((nq, R, k), dtype=torch.float32, device=index.device),
+               torch.empty((nq, R, k), dtype=torch.int32, device=index.device),
+               torch.zeros((1,), dtype=torch.int32, device=index.device))
+    out_d, out_pos, status = out
+    need = lib.lmi_scan_few_workspace_bytes(C.byref(desc), nq, R, k, fr)
+    if need == 0 and nq > 0:
+        raise ValueError(f"few=True: {lib.lmi_last_error().decode(errors='replace')}")
+    if ws is None:
+        ws = getattr(index, "_few_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = index._few_ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=index.device)
+    else:
+        _workspace(ws, need, "scan")
+    s = stream if stream is not None else _lib.stream_handle(index.device)
+    check("lmi_bucket_topk_few", lib.lmi_bucket_topk_few(
+        C.byref(desc), ptr(q), nq, q.stride(0), ptr(classes), R, k, fr, ptr(ws), ws.numel(), ptr(out_d),
+        ptr(out_pos), ptr(status), s))
+    return out_d, out_pos, status
+
+
 SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8", "ring8-mx4", "ring8-mx6")
 
 
 def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optional[int] = None,
-                lists16: bool = False) -> str:
+                lists16: bool = False, few: bool = False) -> str:
     """The kernel family bucket_topk (tagged: with want / avoid) of this index
     and k scans with -- "general" | "ring4" | "ring8" | "ring8-i8" | "ring8-mx4" |
     "ring8-mx6" -- as
     lmi_scan_family reads it from the plan the launch uses (the diagnostic
     switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk;
-    `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan."""
+    `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan.
+    `few`: "few", the kernel of bucket_topk(..., few=True), after its checks."""
+    if few:
+        check_few(index, 1, 1, k, qmode=qmode, want=True if tagged else None, lists16=lists16)
+        return "few"
     if lists16:
         with i8_lists16():
             return scan_family(index, k, tagged, qmode)
@@ -2079,7 +2161,7 @@ class Searcher:
         return mode
 
     def _scan(self, q_search, classes, k_list: int, qmode: int, f64: bool, lap=None,
-              status_out=None, ws=None, seed_round0: bool = False, want=None, rerank=None):
+              status_out=None, ws=None, seed_round0: bool = False, want=None, rerank=None, few=None):
         """K2 on this shard (+ all-gather and K3 for G > 1 ranks, the status
         words riding along so every rank sees every rank's bits).  `lap`
         (measurement only) is called after the scan and after the exchange.
@@ -2087,7 +2169,23 @@ class Searcher:
         `ws`: a caller-owned scan workspace (GraphedSearch's).  `want`: the
         want words of a filtered scan (want_words; float32 lists only).
         `rerank` (checked by check_rerank; f64, one GPU): the 8-bit scan keeps
-        `rerank` entries a pair and rerank_f64 cuts them to k_list float64 ones."""
+        `rerank` entries a pair and rerank_f64 cuts them to k_list float64 ones.
+        `few` = (few_rows,): the few-query scan (_check_few made the checks)."""
+        if few is not None:
+            if qmode != _lib.LMI_Q_F16:
+                # (the default path would scan these queries in exact fp32; this
+                # kernel rounds them to fp16)
+                raise ValueError("few=True (the few-query scan) takes fp16-exact queries (LMI_Q_F16) alone: "
+                                 "a value of this batch is not fp16-representable")
+            nq, R = classes.shape
+            dev = self.index.device
+            st = status_out if status_out is not None else torch.zeros((1,), dtype=torch.int32, device=dev)
+            out = (torch.empty((nq, R, k_list), dtype=torch.float32, device=dev),
+                   torch.empty((nq, R, k_list), dtype=torch.int32, device=dev), st)
+            d, pos, status = bucket_topk(self.index, q_search, classes, k_list, out=out, few=True, few_rows=few[0])
+            if lap:
+                lap("scan")
+            return d, pos, status
         if rerank is not None:
             st = status_out if status_out is not None else torch.zeros((1,), dtype=torch.int32,
                                                                        device=self.index.device)
@@ -2155,8 +2253,14 @@ class Searcher:
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
-              lists16: bool = False):
+              lists16: bool = False, few: bool = False, few_rows: Optional[int] = None):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
+        `few` (nothing sets it for the caller): the scan is the few-query one,
+        bucket_topk(few=True) -- float32 lists of at most 256 pairs on one GPU,
+        `few_rows` rows a slice (None: the call chooses); ValueError for what
+        check_few names, with dist="f64", rerank, tags or lists16, and for a batch
+        with a value that is not fp16-representable (the default path scans
+        such a batch in exact fp32; this kernel would round it).
         `lists16`: the call runs inside i8_lists16() -- storage "mx4" / "mx6" needs it
         for k_list = 11..16, storage "i8" takes its ring's 16-entry lists with it.
         `rerank` = k2 (an index of storage "i8" with keep_rows, dist="f64",
@@ -2173,6 +2277,7 @@ class Searcher:
         `avoid` (the same forms; alone it means want = 0): and only rows with
         (tag & avoid) == 0.  A query that wants and avoids one bit is a
         ValueError, like every refusal of `want`, before anything is launched."""
+        self._check_few(few, few_rows, k_list, dist, rerank, want, avoid, lists16, q_search, classes, R)
         if lists16:
             with i8_lists16():
                 return self.lists(q_nav, q_search, R, k_list, classes=classes, dist=dist, stop_mass=stop_mass,
@@ -2192,8 +2297,25 @@ class Searcher:
             classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
         q_search = _rows_q(q_search, self.index.device)
         d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
-                                    want=want, rerank=None if rerank is None else int(rerank))
+                                    want=want, rerank=None if rerank is None else int(rerank),
+                                    few=(few_rows,) if few else None)
         return classes, d, pos, status
+
+    def _check_few(self, few, few_rows, k_list, dist, rerank, want, avoid, lists16, q_search, classes, R) -> None:
+        """lists / search with few=True: check_few, and what the Searcher adds
+        (float32 lists, no re-rank, one process); ValueError before any launch."""
+        if not few:
+            if few_rows is not None:
+                raise ValueError("few_rows comes with few=True")
+            return
+        if dist != "f32":
+            raise ValueError("few=True (the few-query scan) takes dist='f32' alone")
+        if rerank is not None:
+            raise ValueError("few=True (the few-query scan) takes no rerank")
+        if self.exchange:
+            raise ValueError("few=True (the few-query scan) takes one GPU (no list exchange over a process group)")
+        nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
+        check_few(self.index, nq, R, k_list, few_rows, want=want, avoid=avoid, lists16=lists16)
 
     def _check_i8_lists(self, k_list: int, dist: str, rerank=None) -> None:
         """The lists an index of storage "i8" answers: float32, at most
@@ -2463,8 +2585,11 @@ class Searcher:
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
                min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
-               lists16: bool = False):
+               lists16: bool = False, few: bool = False, few_rows: Optional[int] = None):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `few`, `few_rows`: as in lists -- the scan alone changes; K3, the replay,
+        `stop_mass` and both semantics run unchanged on its lists (never seeded).
 
         `lists16`: as in lists (storage "mx4" / "mx6" with lists of 11..16 entries).
 
@@ -2514,6 +2639,9 @@ class Searcher:
         replay).  `timings` (measurement only) receives per-stage wall times in
         ms; the stages are then separated by stream synchronisations."""
         import time
+        if few or few_rows is not None:  # (before the lists16 re-entry, which would drop them)
+            self._check_few(few, few_rows, k_round if semantics == "reference" else max(k_round, k), dist, rerank,
+                            want, avoid, lists16, q_search, classes, R)
         if lists16:
             with i8_lists16():
                 return self.search(q_nav, q_search, R, k, k_round=k_round, use_threshold=use_threshold,
@@ -2583,10 +2711,11 @@ class Searcher:
         # the running threshold then never exceeds round 0's k-th distance;
         # with k > k_round the first merge pads with 10000s)
         seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
-                and want_w is None and self.index.metric == "cosine")
+                and want_w is None and self.index.metric == "cosine" and not few)
         d, pos, status = self._scan(q_search, classes, k_list, qmode, f64, lap_at if sync else None,
                                     status_out=None if ans is None else ans[3][0:1],
-                                    seed_round0=seed, want=want_w, rerank=rerank)
+                                    seed_round0=seed, want=want_w, rerank=rerank,
+                                    few=(few_rows,) if few else None)
         # (filtered: the replay's bucket sizes are the eligible row counts)
         bsize = self.index.bucket_size
         if want_w is not None and semantics == "reference":
