@@ -81,7 +81,7 @@ __device__ inline float quantize_row_i8(const T* __restrict__ src, int d, int d_
 
 // 4-bit storage: the one device function that turns a vector into MXFP4 codes
 // (include/lmi_hip.h, "the MXFP4 format"); the row quantiser (lmi_quant.hip) and
-// the query prep of an LMI_MX4 scan (prep_mx4_kernel, lmi_scan_ring_mx4.hip)
+// the query prep of an LMI_MX4 scan (prep_mx4_kernel, lmi_scan_ring_mx.hip)
 // both call it.
 // One wave quantises one vector: src[0..d) -> codes[0..d_pad/2) (4-byte
 // aligned) and scales[0..d_pad/32), d_pad a multiple of 64; returns the codes'
@@ -154,7 +154,7 @@ __device__ inline float quantize_row_mx4(const T* __restrict__ src, int d, int d
 
 // 6-bit storage: the one device function that turns a vector into MXFP6 codes
 // (include/lmi_hip.h, "the MXFP6 format"); the row quantiser (lmi_quant.hip) and
-// the query prep of an LMI_MX6 scan (prep_mx6_kernel, lmi_scan_ring_mx6.hip)
+// the query prep of an LMI_MX6 scan (prep_mx6_kernel, lmi_scan_ring_mx.hip)
 // both call it.
 // One wave quantises one vector: src[0..d) -> codes[0..d_pad*3/4) (4-byte
 // aligned) and scales[0..d_pad/32), d_pad a multiple of 64; returns the codes'

@@ -257,20 +257,8 @@ int launch_range(const RangeArgs& a, hipStream_t s) {
         set_error("lmi_bucket_range: d_pad=%d needs %zu B of LDS per workgroup", a.s.d_pad, lds);
         return LMI_E_UNSUPPORTED;
     }
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)range_scan_kernel<F16MATH, TC, TAG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) LMI_TRY(timing_record(s, true, ev));
-    hipLaunchKernelGGL((range_scan_kernel<F16MATH, TC, TAG>), dim3(num_cus()), dim3(kThreads), lds, s, a);
-    LMI_LAUNCH_CHECK("range_scan_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<range_scan_kernel<F16MATH, TC, TAG>>("range_scan_kernel", dim3(num_cus()), dim3(kThreads),
+                                                               lds, s, a);
 }
 
 // ---------------------------------------------------------------------------

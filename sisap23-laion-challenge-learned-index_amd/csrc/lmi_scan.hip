@@ -124,14 +124,7 @@ __global__ __launch_bounds__(kThreads) void prep_kernel(const float* __restrict_
         // sklearn _handle_zeros_in_scale: norms < 10*eps are replaced by 1
         invq[row] = (n < 10.0f * 1.1920929e-07f) ? 1.0f : 1.0f / n;
     }
-    for (int e = lane; e < out_per_q; e += 64) {
-        out_d[(size_t)row * out_per_q + e] = __builtin_inff();
-        out_pos[(size_t)row * out_per_q + e] = -1;
-        if (out_row) out_row[(size_t)row * out_per_q + e] = -1;
-    }
-    for (int f = 0; f < fills.n; ++f)
-        for (int e = lane; e < fills.per_q[f]; e += 64)
-            fills.p[f][(size_t)row * fills.per_q[f] + e] = fills.v[f];
+    prep_fill_tail(row, lane, out_d, out_pos, out_row, out_per_q, fills);
 }
 
 // prep_kernel for an LMI_I8 scan: qbuf = the int8 codes [nq][d_pad] of every
@@ -152,14 +145,7 @@ __global__ __launch_bounds__(kThreads) void prep_i8_kernel(const float* __restri
     const float inv = quantize_row_i8<float, VEC>(q + (size_t)row * ldq, d, d_pad, lane,
                                                   qbuf + (size_t)row * d_pad);
     if (lane == 0) invq[row] = inv;
-    for (int e = lane; e < out_per_q; e += 64) {
-        out_d[(size_t)row * out_per_q + e] = __builtin_inff();
-        out_pos[(size_t)row * out_per_q + e] = -1;
-        if (out_row) out_row[(size_t)row * out_per_q + e] = -1;
-    }
-    for (int f = 0; f < fills.n; ++f)
-        for (int e = lane; e < fills.per_q[f]; e += 64)
-            fills.p[f][(size_t)row * fills.per_q[f] + e] = fills.v[f];
+    prep_fill_tail(row, lane, out_d, out_pos, out_row, out_per_q, fills);
 }
 
 // ---------------------------------------------------------------------------

@@ -1068,23 +1068,8 @@ __global__ __launch_bounds__(512, 1) void scan3_kernel(Scan2Args a) {
 template <int KL, int ABL, bool LO = false, int MODE = 0>
 int launch_scan3_v(const Scan2Args& b, hipStream_t s) {
     constexpr size_t lds = v3::lds_bytes<KL>() + (MODE == 4 ? v3::TAG_AREA + v3::WANT_AREA : 0);
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan3_kernel<KL, ABL, LO, MODE>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan3_kernel<KL, ABL, LO, MODE>), dim3(scan_grid()), dim3(v3::NW * 64), lds, s, b);
-    LMI_LAUNCH_CHECK("scan3_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan3_kernel<KL, ABL, LO, MODE>, (int)lds>("scan3_kernel", dim3(scan_grid()),
+                                                                     dim3(v3::NW * 64), lds, s, b);
 }
 
 }  // namespace

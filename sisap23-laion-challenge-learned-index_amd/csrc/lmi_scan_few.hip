@@ -509,20 +509,7 @@ FewPlan few_plan(const lmi_index_desc* idx, int32_t nq, int32_t R, int32_t k, in
 template <int KL>
 int launch_scan_few(const FewArgs& a, hipStream_t s) {
     const size_t lds = few_lds_bytes(a.d_pad);
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan_few_kernel<KL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) LMI_TRY(timing_record(s, true, ev));
-    hipLaunchKernelGGL((scan_few_kernel<KL>), dim3(num_cus()), dim3(kThreads), lds, s, a);
-    LMI_LAUNCH_CHECK("scan_few_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan_few_kernel<KL>>("scan_few_kernel", dim3(num_cus()), dim3(kThreads), lds, s, a);
 }
 
 }  // namespace

@@ -208,6 +208,44 @@ struct Timing {
 Timing& timing();
 int timing_record(hipStream_t s, bool start, std::pair<hipEvent_t, hipEvent_t>& pr);
 
+// One launch of a scan kernel with dynamic LDS: the kernel's limit raised to
+// MaxLds once per kernel, HIP events around the launch while lmi_timing_enable
+// is on, the launch checked.  name: the kernel's, for the error text.
+constexpr int kLdsMax = 160 * 1024;
+template <auto Kernel, int MaxLds = kLdsMax, typename Args>
+int launch_dyn_lds(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& args) {
+    static std::once_flag once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(once, [] {
+        attr_err = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MaxLds);
+    });
+    LMI_HIP_TRY(attr_err);
+    const bool timed = timing().on;
+    std::pair<hipEvent_t, hipEvent_t> ev{};
+    if (timed) LMI_TRY(timing_record(s, true, ev));
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args);
+    LMI_LAUNCH_CHECK(name);
+    if (timed) return timing_record(s, false, ev);
+    return LMI_OK;
+}
+
+// The tail of every prep kernel, by the wave of query `row`: the (+inf, -1)
+// prefill of its out_per_q output entries and the call's word fills (Fills:
+// PrepFills or WordFills -- array f gets v[f] in the row's per_q[f] words)
+template <typename Fills>
+__device__ __forceinline__ void prep_fill_tail(int row, int lane, float* __restrict__ out_d,
+                                               int32_t* __restrict__ out_pos, int32_t* __restrict__ out_row,
+                                               int32_t out_per_q, const Fills& fills) {
+    for (int e = lane; e < out_per_q; e += 64) {
+        out_d[(size_t)row * out_per_q + e] = __builtin_inff();
+        out_pos[(size_t)row * out_per_q + e] = -1;
+        if (out_row) out_row[(size_t)row * out_per_q + e] = -1;
+    }
+    for (int f = 0; f < fills.n; ++f)
+        for (int e = lane; e < fills.per_q[f]; e += 64)
+            fills.p[f][(size_t)row * fills.per_q[f] + e] = fills.v[f];
+}
+
 // lmi_scan_v12.hip (explicitly instantiated there for the shapes the host
 // dispatch in lmi_scan.hip uses)
 template <int KL, bool F16MATH, typename TC, bool LO = false, bool TAG = false>
@@ -245,7 +283,7 @@ constexpr int kI8MaxDPad = 992;
 // d_pad == 768, lists of KL = 10 or 16 entries, plain or TAG)
 template <int KL, bool TAG>
 int launch_scan3_i8(const Scan2Args& b, hipStream_t s);
-// scan3_mx4_kernel (lmi_scan_ring_mx4.hip: the 8-wave ring on the 4-bit storage,
+// scan3_mx4_kernel (lmi_scan_ring_mx.hip: the 8-wave ring on the 4-bit storage,
 // d_pad == 768, plain lists of KL = 10 or 16 entries).  s.corpus: the rows'
 // MXFP4 codes [n_rows][384]; scales: their scale bytes [n_rows][24]; s.qbuf:
 // the query records prep_mx4_kernel writes (mx4_qbuf_bytes)
@@ -263,7 +301,7 @@ int launch_prep_mx4(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t 
                     hipStream_t s);
 // the one width of the 4-bit storage
 constexpr int kMx4DPad = 768;
-// scan3_mx6_kernel (lmi_scan_ring_mx6.hip: the 8-wave ring on the 6-bit storage,
+// scan3_mx6_kernel (lmi_scan_ring_mx.hip: the 8-wave ring on the 6-bit storage,
 // d_pad == 768, plain lists of KL = 10 or 16 entries), with the arguments of the
 // 4-bit ring: s.corpus the rows' MXFP6 fragments [n_rows][24][24], scales their
 // scale bytes [n_rows][24], s.qbuf the records prep_mx6_kernel writes

@@ -324,14 +324,7 @@ __global__ __launch_bounds__(kThreads) void prep_metric_kernel(const float* __re
         const float qq = row_sqnorm<float, VEC>(src, d, lane);
         if (lane == 0) invq[row] = qq;
     }
-    for (int e = lane; e < out_per_q; e += 64) {
-        out_d[(size_t)row * out_per_q + e] = __builtin_inff();
-        out_pos[(size_t)row * out_per_q + e] = -1;
-        if (out_row) out_row[(size_t)row * out_per_q + e] = -1;
-    }
-    for (int f = 0; f < fills.n; ++f)
-        for (int e = lane; e < fills.per_q[f]; e += 64)
-            fills.p[f][(size_t)row * fills.per_q[f] + e] = fills.v[f];
+    prep_fill_tail(row, lane, out_d, out_pos, out_row, out_per_q, fills);
 }
 
 }  // namespace
@@ -362,23 +355,8 @@ int launch_scan_metric(const ScanArgs& a, int d_pad, hipStream_t s) {
         set_error("metric scan: d_pad=%d above %d", d_pad, kMetricMaxDPad);
         return LMI_E_UNSUPPORTED;
     }
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan_kernel_metric<KL, F16MATH, TC, METRIC>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan_kernel_metric<KL, F16MATH, TC, METRIC>), dim3(num_cus()), dim3(kThreads), lds, s, a);
-    LMI_LAUNCH_CHECK("scan_kernel_metric");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan_kernel_metric<KL, F16MATH, TC, METRIC>>("scan_kernel_metric", dim3(num_cus()),
+                                                                       dim3(kThreads), lds, s, a);
 }
 
 #define LMI_METRIC_INST(M)                                                                        \

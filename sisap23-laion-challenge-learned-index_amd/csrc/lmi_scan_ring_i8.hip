@@ -5,11 +5,9 @@
 // (lmi_scan_v12.hip), which LMI_SCAN_V1=1 also forces here.  The lists are
 // scan_i8_kernel's bit for bit: the integer sums are exact and the distance
 // expression is the same one.
-#include "lmi_scan3.hpp"
+#include "lmi_ring8.hpp"
 
 #include <algorithm>
-#include <mutex>
-#include <utility>
 
 namespace lmi {
 namespace {
@@ -188,13 +186,7 @@ __global__ __launch_bounds__(512, 1) void scan3_i8_kernel(Scan2Args a) {
                 my_invq = live ? a.invq[q] : 0.0f;
             }
         }
-        {
-            uint64_t E[KL];
-            list_clear<KL>(E);
-            list_store<KL>(opaque_u(lbase), E);
-        }
-        __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
-        __syncthreads();
+        ring_lists_clear<KL>(lbase);
 
         // a lane's A-fragment base inside a block (row col, half h: + 64 h k bytes)
         const uint32_t lane_off = (uint32_t)((col >> 2) * PIECEP + (col & 3) * 16 + h * 256);
@@ -329,58 +321,17 @@ __global__ __launch_bounds__(512, 1) void scan3_i8_kernel(Scan2Args a) {
             epilogue(blk);
         }
         if (defer && nblk > 0) epilogue(nblk - 1);
-        // lanes still in append mode hold an unsorted (EMPTY-padded) buffer
-        if (__any(cnt < KL)) {
-            if (cnt < KL) {
-                uint64_t L[KL];
-                list_load<KL>(lbase, L);
-                list_sort<KL>(L);
-                list_store<KL>(lbase, L);
-            }
-        }
-        __syncthreads();  // every wave's DMA drained (the tail waited vmcnt(0))
-
-        // ---- merge the two partial lists of each query (lanes col, col+32) ----
-        if (h == 0 && live) {
-            uint64_t L[KL], P[KL];
-            list_load<KL, 0>(lbase, L);
-            list_load<KL, 32 * 8>(lbase, P);
-#pragma unroll
-            for (int i = 0; i < KL; ++i) {
-                if (P[i] >= L[KL - 1]) break;
-                list_insert<KL>(L, P[i]);
-            }
-            uint64_t* out = a.partial + ((size_t)pp * a.max_chunks + tile.chunk) * KL;
-#pragma unroll
-            for (int i = 0; i < KL; ++i) out[i] = L[i];
-            if (L[KL - 1] != kEmptyKey) atomicMin(&a.thr_g[pp], (unsigned long long)L[KL - 1]);
-        }
+        ring_finish<KL>(a.partial, a.max_chunks, a.thr_g, pp, tile.chunk, h, live, lbase, cnt);
     }
 }
 
 }  // namespace
 
-// one launch of the persistent grid (one workgroup per CU, dynamic LDS); HIP
-// events around it while lmi_timing_enable is on
+// one launch of the persistent grid (one workgroup per CU, dynamic LDS)
 template <int KL, bool TAG>
 int launch_scan3_i8(const Scan2Args& b, hipStream_t s) {
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan3_i8_kernel<KL, TAG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)r8::kLds<KL>);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan3_i8_kernel<KL, TAG>), dim3(scan_grid()), dim3(r8::NW * 64), r8::kLds<KL>, s, b);
-    LMI_LAUNCH_CHECK("scan3_i8_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan3_i8_kernel<KL, TAG>, (int)r8::kLds<KL>>("scan3_i8_kernel", dim3(scan_grid()),
+                                                                       dim3(r8::NW * 64), r8::kLds<KL>, s, b);
 }
 
 template int launch_scan3_i8<10, false>(const Scan2Args&, hipStream_t);

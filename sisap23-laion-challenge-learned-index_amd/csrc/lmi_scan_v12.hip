@@ -782,23 +782,7 @@ int launch_scan(const ScanArgs& a, int d_pad, hipStream_t s) {
         set_error("d_pad=%d needs %zu B of LDS per workgroup", d_pad, lds);
         return LMI_E_UNSUPPORTED;
     }
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan_kernel<KL, F16MATH, TC, LO, TAG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan_kernel<KL, F16MATH, TC, LO, TAG>), dim3(num_cus()), dim3(kThreads), lds, s, a);
-    LMI_LAUNCH_CHECK("scan_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan_kernel<KL, F16MATH, TC, LO, TAG>>("scan_kernel", dim3(num_cus()), dim3(kThreads), lds, s, a);
 }
 
 template <int KL, bool TAG>
@@ -808,23 +792,7 @@ int launch_scan_i8(const ScanArgs& a, int d_pad, hipStream_t s) {
         set_error("LMI_I8: d_pad=%d above %d", d_pad, kI8MaxDPad);
         return LMI_E_UNSUPPORTED;
     }
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan_i8_kernel<KL, TAG>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan_i8_kernel<KL, TAG>), dim3(num_cus()), dim3(kThreads), lds, s, a);
-    LMI_LAUNCH_CHECK("scan_i8_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan_i8_kernel<KL, TAG>>("scan_i8_kernel", dim3(num_cus()), dim3(kThreads), lds, s, a);
 }
 
 namespace {
@@ -832,23 +800,7 @@ template <int KL, int ABL>
 int launch_scan2_v(const Scan2Args& b, hipStream_t s) {
     constexpr size_t lds = v2::lds_bytes<KL>();
     static_assert(lds <= 160 * 1024, "scan2 LDS budget");
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)scan2_kernel<KL, ABL>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    LMI_HIP_TRY(attr_err);
-    const bool timed = timing().on;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (timed) {
-        const int rc = timing_record(s, true, ev);
-        if (rc != LMI_OK) return rc;
-    }
-    hipLaunchKernelGGL((scan2_kernel<KL, ABL>), dim3(num_cus()), dim3(kThreads), lds, s, b);
-    LMI_LAUNCH_CHECK("scan2_kernel");
-    if (timed) return timing_record(s, false, ev);
-    return LMI_OK;
+    return launch_dyn_lds<scan2_kernel<KL, ABL>, (int)lds>("scan2_kernel", dim3(num_cus()), dim3(kThreads), lds, s, b);
 }
 
 }  // namespace
