@@ -240,10 +240,10 @@ class LearnedIndex(Logger):
         semantics="reference" is the reference's while every distance stays
         below 10000 (always for "ip" rows with |<q, y>| < 10000)."""
         if metric is not None:
-            from .index import _check_metric_build, check_metric
+            from .index import _check_build, check_metric
             pg = self._proc_group()
-            _check_metric_build(metric, "auto" if storage is None else storage, False, capacity,
-                                1 if pg is None else pg[2], tags, keep_rows)
+            _check_build(metric, "auto" if storage is None else storage, capacity=capacity,
+                         world=1 if pg is None else pg[2], tags=tags, keep_rows=keep_rows)
             if rerank is not None:
                 check_metric(metric, "rerank")
         if rerank is not None:

@@ -148,79 +148,193 @@ def _as_i32_bits(a: np.ndarray) -> torch.Tensor:
 
 
 I8_MAX_D_PAD = 992  # the 8-bit scan's widest row (its query tile in LDS)
-
-
-MX4_D_PAD = 768     # the 4-bit scan's one width
+MX_D_PAD = 768      # the block-scaled scans' one width
 QUANTIZED = ("i8", "mx4", "mx6")  # the lossy storages: codes quantised on the device, float32 lists of <= 16 entries
 # the block-scaled ones, both at d_pad 768 alone: (name in messages, code bytes of a 32-column block, descriptor
 # dtype, query class, quantiser)
 MX = {"mx4": ("4-bit", 16, _lib.LMI_MX4, _lib.LMI_Q_MX4, "lmi_quantize_rows_mx4"),
       "mx6": ("6-bit", 24, _lib.LMI_MX6, _lib.LMI_Q_MX6, "lmi_quantize_rows_mx6")}
+METRICS = {"cosine": _lib.LMI_METRIC_COSINE, "l2": _lib.LMI_METRIC_L2, "ip": _lib.LMI_METRIC_IP}
+FEW_MAX_PAIRS = 256  # LMI_FEW_MAX_PAIRS
+FEW_MAX_D_PAD = 992
+
+# What an index does not offer, by the property that restricts: property -> (does it hold for this storage and
+# metric?, {row: message}).  A row's key names the one feature it refuses; the row "*" refuses any feature, named
+# in its message by the caller (`what`).  `refuse` raises from the table and every check_* below reads it: the next
+# storage, metric or scan flag states its limits here.
+_QUANTIZED_BUILD = {  # (what storage "i8" and the MX ones refuse alike at construction)
+    "capacity": "storage {s!r}: no reserved capacity (a quantised index takes no updates)",
+    "subcluster": "storage {s!r} takes no sub-cluster layout (subcluster=True)",
+    "world": "storage {s!r} is offered on one GPU (world == 1), not on a striped index"}
+REFUSALS = {
+    "i8": (lambda s, m: s == "i8", {
+        "*": "{what} is not offered on storage 'i8' (the 8-bit storage answers float32 lists of at most {K} "
+             "entries on one GPU)",
+        "k": "storage 'i8' takes lists of at most {K} entries, not {k}",
+        "d": "storage 'i8' takes rows of at most {hi} values, not {d}", **_QUANTIZED_BUILD}),
+    "mx": (lambda s, m: s in MX, {
+        "*": "{what} is not offered on storage {s!r} (the {bits} storage answers unfiltered float32 lists of at "
+             "most {K} entries on one GPU)",
+        "k": "storage {s!r} takes lists of at most {K} entries, not {k}",
+        "k > 10": "storage {s!r} takes lists of {k} entries with lists16=True alone (its ring has 10- and 16-entry "
+                  "lists)",
+        "d": "storage {s!r} takes rows of {lo} to {hi} values (d_pad == {hi}), not {d}",
+        "tags": "storage {s!r} takes no tags (filtered search is not offered on the {bits} storage)",
+        **_QUANTIZED_BUILD}),
+    "metric": (lambda s, m: m != "cosine", {
+        "*": "{what} is not offered with metric {m!r} (an index searched by squared Euclidean distance or inner "
+             "product answers float32 lists of at most {K} entries on one GPU)"}),
+    "f32x": (lambda s, m: s == "f32x", {
+        "filtered": "{name}: filtered search is not offered on storage 'f32x' (the split mode)",
+        "range": "range search is not offered on storage 'f32x' (the split mode)"}),
+    # (a property of the call, not of the index: it holds whenever it is asked)
+    "few": (lambda s, m: True, {key: "few=True (the few-query scan) takes " + text for key, text in {
+        "pairs": f"at most {FEW_MAX_PAIRS} pairs (nq * R), not {{nq}} * {{R}}",
+        "k": "k in [1, {K}], not {k}",
+        "storage": "storage 'f16' alone, not {s!r}",
+        "metric": "metric 'cosine' alone, not {m!r}",
+        "d_pad": f"d_pad <= {FEW_MAX_D_PAD}, not {{d_pad}}",
+        "subcluster": "no sub-cluster layout (subcluster=True)",
+        "world": "one GPU (not a striped index)",
+        "tags": "no tags (want / avoid)",
+        "flags": "no seed, phase or lists16 flag",
+        "qmode": "fp16-exact queries (LMI_Q_F16) alone",
+        "few_rows": "few_rows a positive multiple of 32, not {few_rows}",
+        "dist": "dist='f32' alone",
+        "rerank": "no rerank",
+        "exchange": "one GPU (no list exchange over a process group)",
+        # (the default path would scan such queries in exact fp32; this kernel rounds them to fp16)
+        "batch": "fp16-exact queries (LMI_Q_F16) alone: a value of this batch is not fp16-representable",
+    }.items()}),
+}
 
 
-def _check_i8_build(capacity, subcluster: bool, world: int, d: int, storage: str = "i8", tags=None) -> None:
-    """What an index of storage "i8", "mx4" or "mx6" refuses at construction,
-    before anything is allocated."""
-    if capacity is not None:
-        raise ValueError(f"storage {storage!r}: no reserved capacity (a quantised index takes no updates)")
-    if subcluster:
-        raise ValueError(f"storage {storage!r} takes no sub-cluster layout (subcluster=True)")
-    if world > 1:
-        raise ValueError(f"storage {storage!r} is offered on one GPU (world == 1), not on a striped index")
-    if storage in MX:
-        if (int(d) + 31) // 32 * 32 != MX4_D_PAD:
-            raise ValueError(f"storage {storage!r} takes rows of {MX4_D_PAD - 31} to {MX4_D_PAD} values (d_pad == "
-                             f"{MX4_D_PAD}), not {int(d)}")
-        if tags is not None:
-            raise ValueError(f"storage {storage!r} takes no tags (filtered search is not offered on the "
-                             f"{MX[storage][0]} storage)")
-    elif (int(d) + 31) // 32 * 32 > I8_MAX_D_PAD:
-        raise ValueError(f"storage 'i8' takes rows of at most {I8_MAX_D_PAD} values, not {int(d)}")
+def refuse(prop: str, index, row: str = "*", *, what: Optional[str] = None, **fmt) -> None:
+    """ValueError with the message of REFUSALS[prop]'s row `row` when the property holds for `index`: an index
+    or, at construction, the name of its storage (of its metric, for the property "metric").  The row "*" names
+    the feature refused, `what`, in its message; a row's key is never read from `what`.  `fmt`: the row's fields
+    beyond what, s, bits, m and K."""
+    s, m = (index, index) if isinstance(index, str) else \
+        (getattr(index, "storage", None), getattr(index, "metric", "cosine"))
+    holds, rows = REFUSALS[prop]
+    if holds(s, m):
+        raise ValueError(rows[row].format(what=what, s=s, m=m, bits=MX[s][0] if s in MX else None,
+                                          K=_lib.LMI_MAX_K, **fmt))
 
 
 def check_i8(index, what: str) -> None:
-    """ValueError when `index` is of storage "i8" and `what` (the feature's
-    name in the message) is not offered on it; before anything is launched."""
-    if getattr(index, "storage", None) == "i8":
-        raise ValueError(f"{what} is not offered on storage 'i8' (the 8-bit storage answers float32 lists of "
-                         f"at most {_lib.LMI_MAX_K} entries on one GPU)")
-    if getattr(index, "storage", None) in MX:
-        raise ValueError(f"{what} is not offered on storage {index.storage!r} (the {MX[index.storage][0]} storage "
-                         f"answers unfiltered float32 lists of at most {_lib.LMI_MAX_K} entries on one GPU)")
-
-
-METRICS = {"cosine": _lib.LMI_METRIC_COSINE, "l2": _lib.LMI_METRIC_L2, "ip": _lib.LMI_METRIC_IP}
+    """ValueError when `index` is of storage "i8", "mx4" or "mx6" and `what` (the
+    feature's name in the message) is not offered on it; before anything is launched."""
+    refuse("i8", index, what=what)
+    refuse("mx", index, what=what)
 
 
 def check_metric(index, what: str) -> None:
     """ValueError when `index` is searched by a metric other than cosine and
     `what` (the feature's name in the message) is not offered on it; before
     anything is allocated or launched."""
-    m = index if isinstance(index, str) else getattr(index, "metric", "cosine")
-    if m != "cosine":
-        raise ValueError(f"{what} is not offered with metric {m!r} (an index searched by squared Euclidean "
-                         f"distance or inner product answers float32 lists of at most {_lib.LMI_MAX_K} entries "
-                         "on one GPU)")
+    refuse("metric", index, what=what)
 
 
-def _check_metric_build(metric, storage, subcluster: bool, capacity, world: int, tags, keep_rows: bool) -> None:
-    """What DeviceIndex(metric=...) refuses at construction, before anything is allocated."""
+def check_mx4_k(k: int, storage: str = "mx4") -> None:
+    """The lists storage "mx4" / "mx6" scans: at most 10 entries, or at most 16 inside
+    i8_lists16() (lists16=True); ValueError otherwise, before anything is launched."""
+    if k > _lib.LMI_MAX_K:
+        refuse("mx", storage, "k", k=k)
+    if k > 10 and getattr(i8_lists16.on, "depth", 0) == 0:
+        refuse("mx", storage, "k > 10", k=k)
+
+
+def check_few(index: DeviceIndex, nq: int, R: int, k: int, few_rows=None, **flags) -> None:
+    """ValueError for what the few-query scan (few=True) does not take, before
+    anything is uploaded or launched: more than 256 pairs (nq * R), k > 16, a
+    storage other than "f16", a metric other than cosine, d_pad > 992, a
+    sub-cluster layout, a striped index, tags (want / avoid), a phase, seed or
+    lists16 flag, a query class other than fp16, `few_rows` that is no positive
+    multiple of 32."""
+    f = flags.get
+    # (the first row of the table that applies; a chain, not a list of pairs: this runs on the latency path)
+    row = "pairs" if nq * R > FEW_MAX_PAIRS else \
+        "k" if not 1 <= k <= _lib.LMI_MAX_K else \
+        "storage" if index.storage != "f16" else \
+        "metric" if index.metric != "cosine" else \
+        "d_pad" if index.d_pad > FEW_MAX_D_PAD else \
+        "subcluster" if index.chunk_centroid is not None else \
+        "world" if getattr(index, "world", 1) > 1 else \
+        "tags" if f("want") is not None or f("avoid") is not None else \
+        "flags" if f("seed_round0") or f("phases") or f("lists16") else \
+        "qmode" if f("qmode") not in (None, _lib.LMI_Q_F16) else \
+        "few_rows" if few_rows is not None and (few_rows <= 0 or few_rows % 32) else None
+    if row:
+        refuse("few", index, row, nq=nq, R=R, k=k, d_pad=index.d_pad, few_rows=few_rows)
+
+
+_FILTERED = "filtered search (want / avoid)"  # the feature's name where a metric or an MX storage refuses it
+
+
+def _check_filtered(index) -> None:
+    """want / avoid on an index that offers no filtered search: Searcher's check before it uploads the words (an
+    MX index has no tags: filter_words would call it untagged); bucket_topk calls the same two rows."""
+    check_metric(index, _FILTERED)
+    refuse("mx", index, what=_FILTERED)
+
+
+def _check_few_rows(few, few_rows) -> None:
+    """few_rows without few=True, in bucket_topk and -- before the router is launched -- in Searcher's calls."""
+    if few_rows is not None and not few:
+        raise ValueError("few_rows comes with few=True")
+
+
+def _check_build(metric, storage, d=None, *, subcluster: bool = False, capacity=None, world: int = 1, tags=None,
+                 keep_rows: bool = False) -> None:
+    """What DeviceIndex(metric=..., storage=...) refuses at construction, before anything is allocated: the
+    metric's limits, then those of a quantised storage.  `d` (None: not known yet): the rows' width."""
     if metric not in METRICS:
         raise ValueError(f"metric must be 'cosine', 'l2' or 'ip', not {metric!r}")
-    if metric == "cosine":
+    for given, what in ((storage not in ("auto", "f16", "f32"), f"storage {storage!r}"),
+                        (subcluster, "a sub-cluster layout (subcluster=True)"),
+                        (capacity is not None, "reserved capacity (capacity=)"),
+                        (world > 1, "a striped index (world > 1)"), (tags is not None, "filtered search (tags=)"),
+                        (keep_rows, "keep_rows")):
+        if given:
+            check_metric(metric, what)
+    if storage not in QUANTIZED:
         return
-    if storage not in ("auto", "f16", "f32"):
-        check_metric(metric, f"storage {storage!r}")
-    if subcluster:
-        check_metric(metric, "a sub-cluster layout (subcluster=True)")
-    if capacity is not None:
-        check_metric(metric, "reserved capacity (capacity=)")
-    if world > 1:
-        check_metric(metric, "a striped index (world > 1)")
+    prop = "mx" if storage in MX else "i8"
+    for given, row in ((capacity is not None, "capacity"), (subcluster, "subcluster"), (world > 1, "world")):
+        if given:
+            refuse(prop, storage, row)
+    d_pad = None if d is None else (int(d) + 31) // 32 * 32
+    if d_pad is not None and (d_pad != MX_D_PAD if storage in MX else d_pad > I8_MAX_D_PAD):
+        refuse(prop, storage, "d", d=int(d), lo=MX_D_PAD - 31, hi=MX_D_PAD if storage in MX else I8_MAX_D_PAD)
     if tags is not None:
-        check_metric(metric, "filtered search (tags=)")
-    if keep_rows:
-        check_metric(metric, "keep_rows")
+        refuse("mx", storage, "tags")
+
+
+def _stream(stream, device):
+    """The caller's stream handle, or torch's current stream on `device`."""
+    return stream if stream is not None else _lib.stream_handle(device)
+
+
+def _rows_call(name: str, rows: torch.Tensor, slots: int, dst_rows, stream, device):
+    """The part the row kernels' wrappers share, after each one's check of its destination arrays (`slots` rows of
+    them): `rows` as fp16 or float32 with unit stride along a row, the dst_rows check, and (rows, dtype code, m, ld,
+    d, stream) for the C call -- None when there is no row."""
+    if rows.dtype not in (torch.float16, torch.float32):
+        rows = rows.float()
+    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        rows = rows.contiguous()
+    m, d = int(rows.shape[0]), int(rows.shape[1])
+    if dst_rows is None:
+        if slots < m:
+            raise ValueError(f"{name}: fewer slots than rows")
+    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
+        raise ValueError(f"{name}: dst_rows must be a contiguous int64 [m] device tensor")
+    if m == 0:
+        return None
+    # (a single row may report any stride)
+    return (rows, _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, max(int(rows.stride(0)), d), d,
+            _stream(stream, device))
 
 
 def row_sqnorms(rows: torch.Tensor, sqnorm: torch.Tensor, dst_rows: Optional[torch.Tensor] = None,
@@ -229,25 +343,12 @@ def row_sqnorms(rows: torch.Tensor, sqnorm: torch.Tensor, dst_rows: Optional[tor
     stride along a row, any row stride), accumulated in float64 and rounded
     once, into `sqnorm` (float32, contiguous) -- row i at dst_rows[i] (device
     int64 [m]) or, without dst_rows, at i.  Every slot named must exist."""
-    if rows.dtype not in (torch.float16, torch.float32):
-        rows = rows.float()
-    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
-        rows = rows.contiguous()
-    m, d = int(rows.shape[0]), int(rows.shape[1])
     if sqnorm.dtype != torch.float32 or sqnorm.dim() != 1 or not sqnorm.is_contiguous():
         raise ValueError("row_sqnorms: sqnorm must be a contiguous float32 vector")
-    if dst_rows is None:
-        if sqnorm.shape[0] < m:
-            raise ValueError("row_sqnorms: fewer slots than rows")
-    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
-        raise ValueError("row_sqnorms: dst_rows must be a contiguous int64 [m] device tensor")
-    if m == 0:
-        return
-    ld = max(int(rows.stride(0)), d)
-    s = stream if stream is not None else _lib.stream_handle(sqnorm.device)
-    check("lmi_row_sqnorms", _lib.load().lmi_row_sqnorms(
-        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, ptr(dst_rows),
-        ptr(sqnorm), s))
+    call = _rows_call("row_sqnorms", rows, sqnorm.shape[0], dst_rows, stream, sqnorm.device)
+    if call is not None:
+        rows, dtype, m, ld, d, s = call
+        check("lmi_row_sqnorms", _lib.load().lmi_row_sqnorms(ptr(rows), dtype, m, ld, d, ptr(dst_rows), ptr(sqnorm), s))
 
 
 def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm: torch.Tensor,
@@ -257,33 +358,21 @@ def quantize_rows(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, inv_norm:
     and the codes' 1/||c|| in `inv_norm` [slots] -- row i in slot dst_rows[i]
     (device int64 [m]) or, without dst_rows, slot i.  Every slot named must
     exist: the kernel does not check."""
-    if rows.dtype not in (torch.float16, torch.float32):
-        rows = rows.float()
-    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
-        rows = rows.contiguous()
-    m, d = int(rows.shape[0]), int(rows.shape[1])
     if codes.dtype != torch.int8 or codes.dim() != 2 or codes.shape[1] != d_pad or not codes.is_contiguous() \
             or inv_norm.dtype != torch.float32 or inv_norm.shape != (codes.shape[0],) \
             or not inv_norm.is_contiguous():
         raise ValueError("quantize_rows: codes must be int8 [slots, d_pad] and inv_norm float32 [slots], contiguous")
-    if dst_rows is None:
-        if codes.shape[0] < m:
-            raise ValueError("quantize_rows: fewer slots than rows")
-    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
-        raise ValueError("quantize_rows: dst_rows must be a contiguous int64 [m] device tensor")
-    if m == 0:
-        return
-    ld = max(int(rows.stride(0)), d)  # (a single row may report any stride)
-    s = stream if stream is not None else _lib.stream_handle(codes.device)
-    check("lmi_quantize_rows_i8", _lib.load().lmi_quantize_rows_i8(
-        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
-        ptr(dst_rows), ptr(codes), ptr(inv_norm), s))
+    call = _rows_call("quantize_rows", rows, codes.shape[0], dst_rows, stream, codes.device)
+    if call is not None:
+        rows, dtype, m, ld, d, s = call
+        check("lmi_quantize_rows_i8", _lib.load().lmi_quantize_rows_i8(
+            ptr(rows), dtype, m, ld, d, d_pad, ptr(dst_rows), ptr(codes), ptr(inv_norm), s))
 
 
-def mx4_views(store: torch.Tensor, n_rows: int, d_pad: int, storage: str = "mx4"):
+def mx_views(store: torch.Tensor, n_rows: int, d_pad: int, storage: str):
     """(codes uint8 [n_rows, cb], scales uint8 [n_rows, d_pad / 32]): the two
     arrays of an LMI_MX4 / LMI_MX6 store (a flat uint8 tensor of
-    mx4_store_bytes); cb = d_pad / 2 code bytes a row on "mx4", d_pad * 3 / 4
+    mx_store_bytes); cb = d_pad / 2 code bytes a row on "mx4", d_pad * 3 / 4
     (24-byte fragments) on "mx6"."""
     cb = d_pad // 32 * MX[storage][1]
     off = (n_rows * cb + 255) // 256 * 256  # LMI_MX4_SCALE_OFFSET / LMI_MX6_SCALE_OFFSET
@@ -291,18 +380,13 @@ def mx4_views(store: torch.Tensor, n_rows: int, d_pad: int, storage: str = "mx4"
             store[off: off + n_rows * (d_pad // 32)].view(n_rows, d_pad // 32))
 
 
-def mx4_store_bytes(n_rows: int, d_pad: int, storage: str = "mx4") -> int:
+def mx_store_bytes(n_rows: int, d_pad: int, storage: str) -> int:
     return (n_rows * (d_pad // 32 * MX[storage][1]) + 255) // 256 * 256 + n_rows * (d_pad // 32)
 
 
 def _quantize_rows_mx(storage: str, rows, d_pad: int, codes, scales, inv_norm, dst_rows, stream) -> None:
     fn, cb = MX[storage][4], d_pad // 32 * MX[storage][1]
     name = fn[4:]
-    if rows.dtype not in (torch.float16, torch.float32):
-        rows = rows.float()
-    if rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1):
-        rows = rows.contiguous()
-    m, d = int(rows.shape[0]), int(rows.shape[1])
     slots = int(codes.shape[0])
     if codes.dtype != torch.uint8 or tuple(codes.shape) != (slots, cb) or not codes.is_contiguous() \
             or scales.dtype != torch.uint8 or tuple(scales.shape) != (slots, d_pad // 32) \
@@ -310,18 +394,11 @@ def _quantize_rows_mx(storage: str, rows, d_pad: int, codes, scales, inv_norm, d
             or not inv_norm.is_contiguous():
         raise ValueError(f"{name}: codes uint8 [slots, {cb}], scales uint8 [slots, d_pad/32] and "
                          "inv_norm float32 [slots], contiguous")
-    if dst_rows is None:
-        if slots < m:
-            raise ValueError(f"{name}: fewer slots than rows")
-    elif dst_rows.dtype != torch.int64 or dst_rows.shape != (m,) or not dst_rows.is_contiguous():
-        raise ValueError(f"{name}: dst_rows must be a contiguous int64 [m] device tensor")
-    if m == 0:
-        return
-    ld = max(int(rows.stride(0)), d)
-    s = stream if stream is not None else _lib.stream_handle(codes.device)
-    check(fn, getattr(_lib.load(), fn)(
-        ptr(rows), _lib.LMI_F16 if rows.dtype == torch.float16 else _lib.LMI_F32, m, ld, d, d_pad,
-        ptr(dst_rows), ptr(codes), ptr(scales), ptr(inv_norm), s))
+    call = _rows_call(name, rows, slots, dst_rows, stream, codes.device)
+    if call is not None:
+        rows, dtype, m, ld, d, s = call
+        check(fn, getattr(_lib.load(), fn)(
+            ptr(rows), dtype, m, ld, d, d_pad, ptr(dst_rows), ptr(codes), ptr(scales), ptr(inv_norm), s))
 
 
 def quantize_rows_mx4(rows: torch.Tensor, d_pad: int, codes: torch.Tensor, scales: torch.Tensor,
@@ -403,7 +480,7 @@ class DeviceIndex:
     source must then not be updated in place while this index is in use."""
 
     rows16 = None  # the fp16 rows kept beside the codes (storage "i8" / "mx4" / "mx6", keep_rows=True)
-    codes = scales = None  # storage "mx4" / "mx6": the two arrays of the flat store `corpus` (mx4_views)
+    codes = scales = None  # storage "mx4" / "mx6": the two arrays of the flat store `corpus` (mx_views)
     _rows_desc = None  # the descriptor over rows16 (rows_desc)
     corpus64 = None  # float64 rows (float64 input that float32 rounding changes)
     corpus32 = None  # float32 rows of the split mode (storage "f32x")
@@ -459,7 +536,9 @@ class DeviceIndex:
         sub-cluster layout): ValueError otherwise, or when below the row
         count."""
         _lib.load()
-        _check_metric_build(metric, storage, subcluster, capacity, world, tags, keep_rows)
+        _check_build(metric, storage, None if storage not in QUANTIZED else
+                     int(data.shape[1]) if hasattr(data, "shape") else int(np.shape(data)[1]),
+                     subcluster=subcluster, capacity=capacity, world=world, tags=tags, keep_rows=keep_rows)
         self.metric = metric
         if keep_rows:
             if storage not in QUANTIZED:
@@ -489,9 +568,6 @@ class DeviceIndex:
 
         gpos, loc_off = self.layout.shard(rank, world)
         self._capacity = None
-        if storage in QUANTIZED:
-            _check_i8_build(capacity, subcluster, world, int(np.shape(data)[1]) if not hasattr(data, "shape")
-                            else int(data.shape[1]), storage, tags)
         if capacity is not None:
             if world > 1 or subcluster:
                 raise ValueError("capacity: only an index that add / remove support can reserve rows "
@@ -564,15 +640,15 @@ class DeviceIndex:
         self._adopt_store(make((cap, self.d_pad), dtype=dtype, device=self.device),
                           torch.empty((cap,), dtype=torch.float32, device=self.device), n_rows)
 
-    def _alloc_mx4(self, n_rows: int):
+    def _alloc_mx(self, n_rows: int):
         """The store of storage "mx4" / "mx6": one flat uint8 tensor (codes, then the
         scale bytes at LMI_MX4_SCALE_OFFSET / LMI_MX6_SCALE_OFFSET) as `corpus`, its two arrays as
         `codes` / `scales`, and `inv_norm`; nothing is reserved."""
-        self._store = self.corpus = torch.empty((max(mx4_store_bytes(n_rows, self.d_pad, self.storage), 256),),
+        self._store = self.corpus = torch.empty((max(mx_store_bytes(n_rows, self.d_pad, self.storage), 256),),
                                                 dtype=torch.uint8, device=self.device)
         self._store_inv = self.inv_norm = torch.empty((n_rows,), dtype=torch.float32, device=self.device)
         self._capacity = n_rows
-        self.codes, self.scales = mx4_views(self.corpus, n_rows, self.d_pad, self.storage)
+        self.codes, self.scales = mx_views(self.corpus, n_rows, self.d_pad, self.storage)
         self._desc = self._desc32 = self._desc64 = None
 
     def _adopt_store(self, store, store_inv, n_rows: int, inv64: bool = False):
@@ -753,15 +829,13 @@ class DeviceIndex:
         shard (world > 1), duplicate ids, words outside [0, 2^32); an id the
         index does not hold raises as `remove` reports it (a KeyError that is a
         ValueError too); a consumed index raises as every call on it does."""
-        if self.storage in MX:
-            check_i8(self, "edit_tags")
+        refuse("mx", self, what="edit_tags")
         index_update.edit_tags(self, ids, set_bits, clear_bits)
 
     def set_tags(self, ids, tags) -> None:
         """The tag words of the stored objects `ids` := `tags` (an int or one
         word per id): edit_tags with every bit cleared first."""
-        if self.storage in MX:
-            check_i8(self, "set_tags")
+        refuse("mx", self, what="set_tags")
         index_update.edit_tags(self, ids, tags, 0xFFFFFFFF)
 
     def ids_with(self, want: int = 0, avoid: int = 0) -> np.ndarray:
@@ -883,7 +957,7 @@ class DeviceIndex:
                     fp16_exact(src[a:a + step]) for a in range(0, n, step)):
                 raise ValueError("keep_rows needs fp16-representable data (the rule of storage='f16')")
             if storage in MX:
-                self._alloc_mx4(n_rows)
+                self._alloc_mx(n_rows)
             else:
                 self._alloc_store(n_rows, torch.int8)
             if keep:
@@ -953,14 +1027,13 @@ class DeviceIndex:
             raise ValueError("RowSource must have one row per label")
         if storage not in ("auto", "f16", "i8", "mx4", "mx6"):
             raise ValueError("a RowSource builds storage 'f16' ('auto'), 'i8', 'mx4' or 'mx6'")
-        if storage in QUANTIZED:
-            check_metric(self, f"storage {storage!r}")
+        # (what the storage and the metric refuse: _check_build, made by __init__, this method's one caller)
         self.d = src.d
         self.d_pad = (self.d + 31) // 32 * 32
         self.storage = storage if storage in QUANTIZED else "f16"
         n_rows = int(gpos.size)
         if self.storage in MX:
-            self._alloc_mx4(n_rows)
+            self._alloc_mx(n_rows)
         elif self.storage == "i8":
             self._alloc_store(n_rows, torch.int8)
         else:
@@ -1094,11 +1167,11 @@ class DeviceIndex:
             raise ValueError(f"quantized: storage {storage!r} is offered on one GPU (world == 1), not on a stripe")
         if self.chunk_centroid is not None:
             raise ValueError(f"quantized: storage {storage!r} takes no sub-cluster layout (chunk_centroid)")
-        _check_i8_build(None, False, 1, self.d, storage, self.tags_by_pos)
+        _check_build(self.metric, storage, self.d, tags=self.tags_by_pos)
         new = self._successor(self.layout, self.pos_to_id, self.tags_by_pos)
         new.storage = storage
         if storage in MX:
-            new._alloc_mx4(self.n_rows)
+            new._alloc_mx(self.n_rows)
             _quantize_rows_mx(storage, self.corpus[:, : self.d], self.d_pad, new.codes, new.scales, new.inv_norm,
                               None, None)
         else:
@@ -1156,10 +1229,17 @@ class DeviceIndex:
             need = lib.lmi_scan_metric_workspace_bytes(C.byref(self.desc), METRICS[self.metric], nq, R, k, qmode)
         else:
             need = lib.lmi_scan_workspace_bytes(C.byref(self.desc_for(k)), nq, R, k, qmode)
-        ws = self._ws.get("buf")
+        return self._workspace("buf", need)
+
+    def _workspace(self, key: str, need: int, ws=None, what: str = "scan") -> torch.Tensor:
+        """A workspace of at least `need` bytes for the call named `what`: the caller's `ws` after a size check, or
+        the index's own under the cache key `key` ("buf": the float32 scans, "f64", "range", "few"), which a later
+        call that needs more replaces."""
+        if ws is not None:
+            return _workspace(ws, need, what)
+        ws = self._ws.get(key)
         if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-            self._ws["buf"] = ws
+            ws = self._ws[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         return ws
 
 
@@ -1302,7 +1382,7 @@ class DeviceRouter:
         else:
             classes = torch.empty((nq, R), dtype=torch.int32, device=self.device)
         probs = torch.empty((nq, R), dtype=torch.float32, device=self.device) if with_probs else None
-        s = stream if stream is not None else _lib.stream_handle(self.device)
+        s = _stream(stream, self.device)
         if stop_mass is not None:
             if n_probes_out is not None and (n_probes_out.dtype != torch.int32
                                              or n_probes_out.numel() != nq
@@ -1320,7 +1400,7 @@ class DeviceRouter:
         x = _rows_f32(x, self.device)
         nq = x.shape[0]
         out = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        s = stream if stream is not None else _lib.stream_handle(self.device)
+        s = _stream(stream, self.device)
         check("lmi_router", _lib.load().lmi_router(ptr(x), nq, x.stride(0), C.byref(self._desc), 1,
                                                    _lib.LMI_ROUTER_ARGMAX, ptr(out), 0, s))
         return out
@@ -1355,14 +1435,36 @@ class i8_lists16:
         _lib.load().lmi_scan_set_i8_lists16(self.prev)
 
 
-def check_mx4_k(k: int, storage: str = "mx4") -> None:
-    """The lists storage "mx4" / "mx6" scans: at most 10 entries, or at most 16 inside
-    i8_lists16() (lists16=True); ValueError otherwise, before anything is launched."""
-    if k > _lib.LMI_MAX_K:
-        raise ValueError(f"storage {storage!r} takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
-    if k > 10 and getattr(i8_lists16.on, "depth", 0) == 0:
-        raise ValueError(f"storage {storage!r} takes lists of {k} entries with lists16=True alone (its ring has 10- "
-                         "and 16-entry lists)")
+def _query_class(index: DeviceIndex, qmode: Optional[int]) -> int:
+    """The query class a scan of `index` runs: the one of a quantised storage, else the caller's `qmode`, else
+    the storage's own arithmetic."""
+    if index.storage == "i8":
+        return _lib.LMI_Q_I8
+    if index.storage in MX:
+        return MX[index.storage][3]
+    if qmode is None:
+        return _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    return qmode
+
+
+def _call_head(index: DeviceIndex, q, classes):
+    """A scan call's operands on the index's device: (q float32 rows, classes int32 [nq, R], nq, R); ValueError
+    unless q is [nq, index.d]."""
+    q = _rows_f32(q, index.device)
+    classes = _as_torch(classes, index.device, torch.int32)
+    nq, R = classes.shape
+    if q.shape[0] != nq or q.shape[1] != index.d:
+        raise ValueError("query shape does not match the index")
+    return q, classes, nq, R
+
+
+def _triple(out, shape, dtype, device, status=None):
+    """The (d, pos, status) triple a scan call writes: the caller's `out`, or new tensors of `shape` (d of `dtype`,
+    pos int32) with the status word `status` (None: a new zeroed one)."""
+    if out is not None:
+        return out
+    return (torch.empty(shape, dtype=dtype, device=device), torch.empty(shape, dtype=torch.int32, device=device),
+            status if status is not None else torch.zeros((1,), dtype=torch.int32, device=device))
 
 
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
@@ -1388,145 +1490,77 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     one bit is the caller's check (mask_words makes it on the host).
     `lists16`: the call runs inside i8_lists16() (storage "i8" at d_pad 768:
     k = 11..16 on the ring's 16-entry lists; the workspace is sized there too)."""
-    if few:
-        return _bucket_topk_few(index, q, classes, k, few_rows, stream, out, ws,
-                                flags=dict(qmode=qmode, seed_round0=seed_round0, phases=phases, want=want,
-                                           avoid=avoid, lists16=lists16))
-    if few_rows is not None:
-        raise ValueError("few_rows comes with few=True")
-    if lists16:
-        with i8_lists16():
-            return bucket_topk(index, q, classes, k, qmode=qmode, stream=stream, out=out, ws=ws,
-                               seed_round0=seed_round0, phases=phases, want=want, avoid=avoid)
-    if index.metric != "cosine":  # (refused before anything is uploaded)
-        if want is not None or avoid is not None:
-            check_metric(index, "filtered search (want / avoid)")
+    tagged = want is not None or avoid is not None
+    _check_few_rows(few, few_rows)
+    # (no context object on the eager path: entered on demand, left in the finally)
+    ctx = i8_lists16().__enter__() if lists16 else None
+    try:
+        if index.metric != "cosine" and not few:  # (refused before anything is uploaded)
+            if tagged:
+                check_metric(index, _FILTERED)
+            if k > _lib.LMI_MAX_K:
+                check_metric(index, f"k = {k} > {_lib.LMI_MAX_K}")
+        lib = _lib.load()
+        q, classes, nq, R = _call_head(index, q, classes)
+        if few:
+            check_few(index, nq, R, k, few_rows, qmode=qmode, seed_round0=seed_round0, phases=phases, want=want,
+                      avoid=avoid, lists16=lists16)
+            desc, fr = index.desc, int(few_rows or 0)
+            need = lib.lmi_scan_few_workspace_bytes(C.byref(desc), nq, R, k, fr)
+            if need == 0 and nq > 0:
+                raise ValueError(f"few=True: {lib.lmi_last_error().decode(errors='replace')}")
+            ws = index._workspace("few", need, ws)
+            out_d, out_pos, status = _triple(out, (nq, R, k), torch.float32, index.device)
+            check("lmi_bucket_topk_few", lib.lmi_bucket_topk_few(
+                C.byref(desc), ptr(q), nq, q.stride(0), ptr(classes), R, k, fr, ptr(ws), ws.numel(), ptr(out_d),
+                ptr(out_pos), ptr(status), _stream(stream, index.device)))
+            return out_d, out_pos, status
         if k > _lib.LMI_MAX_K:
-            check_metric(index, f"k = {k} > {_lib.LMI_MAX_K}")
-    lib = _lib.load()
-    q = _rows_f32(q, index.device)
-    classes = _as_torch(classes, index.device, torch.int32)
-    nq, R = classes.shape
-    if q.shape[0] != nq or q.shape[1] != index.d:
-        raise ValueError("query shape does not match the index")
-    if index.storage == "i8":
-        if k > _lib.LMI_MAX_K:
-            raise ValueError(f"storage 'i8' takes lists of at most {_lib.LMI_MAX_K} entries, not {k}")
-        # (the one query class of the 8-bit storage; its scan is never seeded)
-        qmode, seed_round0 = _lib.LMI_Q_I8, False
-    if index.storage in MX:
-        check_mx4_k(k, index.storage)
-        if want is not None or avoid is not None:
-            check_i8(index, "filtered search (want / avoid)")
-        qmode, seed_round0 = MX[index.storage][3], False
-    if qmode is None:
-        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
-    if index.metric != "cosine":
-        # (lmi_bucket_topk_metric: plain float32 lists, never seeded)
-        desc, mcode = index.desc, METRICS[index.metric]
-        if out is None:
-            out = (torch.empty((nq, R, k), dtype=torch.float32, device=index.device),
-                   torch.empty((nq, R, k), dtype=torch.int32, device=index.device),
-                   torch.zeros((1,), dtype=torch.int32, device=index.device))
-        out_d, out_pos, status = out
-        if ws is None:
-            ws = index.workspace(nq, R, k, qmode)
-        else:
-            _workspace(ws, lib.lmi_scan_metric_workspace_bytes(C.byref(desc), mcode, nq, R, k, qmode), "scan")
-        s = stream if stream is not None else _lib.stream_handle(index.device)
-        check("lmi_bucket_topk_metric", lib.lmi_bucket_topk_metric(
-            C.byref(desc), mcode, ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode | phases, ptr(out_d),
-            ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
+            refuse("i8", index, "k", k=k)
+        if index.storage in MX:
+            check_mx4_k(k, index.storage)
+            if tagged:
+                refuse("mx", index, what=_FILTERED)
+        qmode = _query_class(index, qmode)
+        if index.metric != "cosine":
+            # (lmi_bucket_topk_metric: plain float32 lists, never seeded)
+            desc, mcode = index.desc, METRICS[index.metric]
+            ws = index._workspace("buf", lib.lmi_scan_metric_workspace_bytes(C.byref(desc), mcode, nq, R, k, qmode), ws)
+            out_d, out_pos, status = _triple(out, (nq, R, k), torch.float32, index.device)
+            check("lmi_bucket_topk_metric", lib.lmi_bucket_topk_metric(
+                C.byref(desc), mcode, ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode | phases, ptr(out_d),
+                ptr(out_pos), ptr(status), ptr(ws), ws.numel(), _stream(stream, index.device)))
+            return out_d, out_pos, status
+        desc = index.desc_for(k)
+        if tagged:
+            if index.tags is None:
+                raise ValueError("want / avoid: this index is untagged (build it with `tags`)")
+            if phases:
+                raise ValueError("want / avoid: the tagged scan runs whole (no phases)")
+            value, mask = _tag_words(want, avoid, nq, q.device)
+            need = lib.lmi_scan_tagged_workspace_bytes(C.byref(desc), nq, R, k, qmode)
+            if need == 0 and nq:
+                raise ValueError("want: this index or call takes no tagged scan "
+                                 "(k > 16, the split mode or a sub-cluster layout)")
+            ws = index._workspace("buf", need, ws, "tagged scan")
+            out_d, out_pos, status = _triple(out, (nq, R, k), torch.float32, index.device)
+            check("lmi_bucket_topk_masked", lib.lmi_bucket_topk_masked(
+                C.byref(desc), ptr(index.tags), ptr(value), ptr(mask), None, None, ptr(q), nq, q.stride(0),
+                ptr(classes), R, k, qmode, ptr(out_d), ptr(out_pos), ptr(status), ptr(ws), ws.numel(),
+                _stream(stream, index.device)))
+            return out_d, out_pos, status
+        ws = index._workspace("buf", lib.lmi_scan_workspace_bytes(C.byref(desc), nq, R, k, qmode), ws)
+        out_d, out_pos, status = _triple(out, (nq, R, k), torch.float32, index.device)
+        # (never seeded: the split mode scans every pair whole, and so do the quantised storages)
+        seeded = seed_round0 and index.storage != "f32x" and index.storage not in QUANTIZED
+        flags = (_lib.LMI_Q_SEED_ROUND0 if seeded else 0) | phases
+        check("lmi_bucket_topk", lib.lmi_bucket_topk(
+            C.byref(desc), ptr(q), nq, q.stride(0), ptr(classes), R, k, qmode | flags, ptr(out_d), ptr(out_pos),
+            ptr(status), ptr(ws), ws.numel(), _stream(stream, index.device)))
         return out_d, out_pos, status
-    if want is not None or avoid is not None:
-        return _bucket_topk_tagged(index, q, classes, k, qmode, want, avoid, stream, out, ws, phases)
-    desc = index.desc_for(k)
-    if out is None:
-        out_d = torch.empty((nq, R, k), dtype=torch.float32, device=index.device)
-        out_pos = torch.empty((nq, R, k), dtype=torch.int32, device=index.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=index.device)
-    else:
-        out_d, out_pos, status = out
-    if ws is None:
-        ws = index.workspace(nq, R, k, qmode)
-    else:
-        _workspace(ws, lib.lmi_scan_workspace_bytes(C.byref(desc), nq, R, k, qmode), "scan")
-    s = stream if stream is not None else _lib.stream_handle(index.device)
-    if index.storage == "f32x":
-        seed_round0 = False  # (the split mode scans every pair whole)
-    flags = (_lib.LMI_Q_SEED_ROUND0 if seed_round0 else 0) | phases
-    check("lmi_bucket_topk", lib.lmi_bucket_topk(C.byref(desc), ptr(q), nq, q.stride(0),
-                                                 ptr(classes), R, k, qmode | flags, ptr(out_d),
-                                                 ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
-    return out_d, out_pos, status
-
-
-FEW_MAX_PAIRS = 256  # LMI_FEW_MAX_PAIRS
-FEW_MAX_D_PAD = 992
-
-
-def check_few(index: DeviceIndex, nq: int, R: int, k: int, few_rows=None, **flags) -> None:
-    """ValueError for what the few-query scan (few=True) does not take, before
-    anything is uploaded or launched: more than 256 pairs (nq * R), k > 16, a
-    storage other than "f16", a metric other than cosine, d_pad > 992, a
-    sub-cluster layout, a striped index, tags (want / avoid), a phase, seed or
-    lists16 flag, a query class other than fp16, `few_rows` that is no positive
-    multiple of 32."""
-    def no(what):
-        raise ValueError(f"few=True (the few-query scan) takes {what}")
-    if nq * R > FEW_MAX_PAIRS:
-        no(f"at most {FEW_MAX_PAIRS} pairs (nq * R), not {nq} * {R}")
-    if not 1 <= k <= _lib.LMI_MAX_K:
-        no(f"k in [1, {_lib.LMI_MAX_K}], not {k}")
-    if index.storage != "f16":
-        no(f"storage 'f16' alone, not {index.storage!r}")
-    if index.metric != "cosine":
-        no(f"metric 'cosine' alone, not {index.metric!r}")
-    if index.d_pad > FEW_MAX_D_PAD:
-        no(f"d_pad <= {FEW_MAX_D_PAD}, not {index.d_pad}")
-    if index.chunk_centroid is not None:
-        no("no sub-cluster layout (subcluster=True)")
-    if getattr(index, "world", 1) > 1:
-        no("one GPU (not a striped index)")
-    if flags.get("want") is not None or flags.get("avoid") is not None:
-        no("no tags (want / avoid)")
-    if flags.get("seed_round0") or flags.get("phases") or flags.get("lists16"):
-        no("no seed, phase or lists16 flag")
-    if flags.get("qmode") not in (None, _lib.LMI_Q_F16):
-        no("fp16-exact queries (LMI_Q_F16) alone")
-    if few_rows is not None and (few_rows <= 0 or few_rows % 32):
-        no(f"few_rows a positive multiple of 32, not {few_rows}")
-
-
-def _bucket_topk_few(index, q, classes, k, few_rows, stream, out, ws, flags):
-    """bucket_topk(few=True): lmi_bucket_topk_few with a workspace of its own size."""
-    lib = _lib.load()
-    q = _rows_f32(q, index.device)
-    classes = _as_torch(classes, index.device, torch.int32)
-    nq, R = classes.shape
-    if q.shape[0] != nq or q.shape[1] != index.d:
-        raise ValueError("query shape does not match the index")
-    check_few(index, nq, R, k, few_rows, **flags)
-    desc, fr = index.desc, int(few_rows or 0)
-    if out is None:
-        out = (torch.empty((nq, R, k), dtype=torch.float32, device=index.device),
-               torch.empty((nq, R, k), dtype=torch.int32, device=index.device),
-               torch.zeros((1,), dtype=torch.int32, device=index.device))
-    out_d, out_pos, status = out
-    need = lib.lmi_scan_few_workspace_bytes(C.byref(desc), nq, R, k, fr)
-    if need == 0 and nq > 0:
-        raise ValueError(f"few=True: {lib.lmi_last_error().decode(errors='replace')}")
-    if ws is None:
-        ws = getattr(index, "_few_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = index._few_ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=index.device)
-    else:
-        _workspace(ws, need, "scan")
-    s = stream if stream is not None else _lib.stream_handle(index.device)
-    check("lmi_bucket_topk_few", lib.lmi_bucket_topk_few(
-        C.byref(desc), ptr(q), nq, q.stride(0), ptr(classes), R, k, fr, ptr(ws), ws.numel(), ptr(out_d),
-        ptr(out_pos), ptr(status), s))
-    return out_d, out_pos, status
+    finally:
+        if ctx is not None:
+            ctx.__exit__()
 
 
 SCAN_FAMILIES = ("general", "ring4", "ring8", "ring8-i8", "ring8-mx4", "ring8-mx6")
@@ -1541,22 +1575,19 @@ def scan_family(index: DeviceIndex, k: int, tagged: bool = False, qmode: Optiona
     switches LMI_SCAN_V1 / LMI_SCAN_V2 included).  `qmode` as in bucket_topk;
     `lists16`: the family of bucket_topk(..., lists16=True), the re-rank's scan.
     `few`: "few", the kernel of bucket_topk(..., few=True), after its checks."""
-    if few:
-        check_few(index, 1, 1, k, qmode=qmode, want=True if tagged else None, lists16=lists16)
-        return "few"
-    if lists16:
-        with i8_lists16():
-            return scan_family(index, k, tagged, qmode)
-    if index.storage == "i8":
-        qmode = _lib.LMI_Q_I8
-    elif index.storage in MX:
-        qmode = MX[index.storage][3]
-    elif qmode is None:
-        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
-    fam = _lib.load().lmi_scan_family(C.byref(index.desc_for(k)), k, qmode, 1 if tagged else 0)
-    if fam < 0:
-        check("lmi_scan_family", -fam)
-    return SCAN_FAMILIES[fam]
+    ctx = i8_lists16().__enter__() if lists16 else None
+    try:
+        if few:
+            check_few(index, 1, 1, k, qmode=qmode, want=True if tagged else None, lists16=lists16)
+            return "few"
+        fam = _lib.load().lmi_scan_family(C.byref(index.desc_for(k)), k, _query_class(index, qmode),
+                                          1 if tagged else 0)
+        if fam < 0:
+            check("lmi_scan_family", -fam)
+        return SCAN_FAMILIES[fam]
+    finally:
+        if ctx is not None:
+            ctx.__exit__()
 
 
 def want_words(index: DeviceIndex, want, nq: int, k_list: int, dist: str = "f32",
@@ -1576,8 +1607,7 @@ def _host_words(index, word, nq, k_list, dist, per_query, name) -> np.ndarray:
         raise ValueError(f"{name}: this index is untagged (build it with `tags`)")
     if dist != "f32":
         raise ValueError(f"{name}: filtered search is not offered with dist='f64'")
-    if index.storage == "f32x":
-        raise ValueError(f"{name}: filtered search is not offered on storage 'f32x' (the split mode)")
+    refuse("f32x", index, "filtered", name=name)
     if k_list > _lib.LMI_MAX_K:
         raise ValueError(f"{name}: filtered search takes lists of at most {_lib.LMI_MAX_K} entries, not {k_list}")
     if isinstance(word, (int, np.integer)) and not isinstance(word, bool):
@@ -1659,39 +1689,6 @@ def _tag_words(want, avoid, nq, device):
     return want, torch.bitwise_or(want, avoid)
 
 
-def _bucket_topk_tagged(index, q, classes, k, qmode, want, avoid, stream, out, ws, phases):
-    """bucket_topk's tagged call (q, classes already on the device)."""
-    lib = _lib.load()
-    nq, R = classes.shape
-    if index.tags is None:
-        raise ValueError("want / avoid: this index is untagged (build it with `tags`)")
-    if phases:
-        raise ValueError("want / avoid: the tagged scan runs whole (no phases)")
-    value, mask = _tag_words(want, avoid, nq, q.device)
-    desc = index.desc_for(k)
-    need = lib.lmi_scan_tagged_workspace_bytes(C.byref(desc), nq, R, k, qmode)
-    if need == 0 and nq:
-        raise ValueError("want: this index or call takes no tagged scan "
-                         "(k > 16, the split mode or a sub-cluster layout)")
-    if out is None:
-        out_d = torch.empty((nq, R, k), dtype=torch.float32, device=index.device)
-        out_pos = torch.empty((nq, R, k), dtype=torch.int32, device=index.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=index.device)
-    else:
-        out_d, out_pos, status = out
-    if ws is None:
-        ws = index._ws.get("buf")
-        if ws is None or ws.numel() < need:
-            ws = index._ws["buf"] = torch.empty(max(need, 256), dtype=torch.uint8, device=index.device)
-    else:
-        _workspace(ws, need, "tagged scan")
-    s = stream if stream is not None else _lib.stream_handle(index.device)
-    check("lmi_bucket_topk_masked", lib.lmi_bucket_topk_masked(
-        C.byref(desc), ptr(index.tags), ptr(value), ptr(mask), None, None, ptr(q), nq, q.stride(0), ptr(classes),
-        R, k, qmode, ptr(out_d), ptr(out_pos), ptr(status), ptr(ws), ws.numel(), s))
-    return out_d, out_pos, status
-
-
 def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
     """What a range search refuses about the index, as a ValueError before
     anything is launched or allocated: the split mode (storage "f32x"), float64
@@ -1700,8 +1697,7 @@ def check_range_index(index: DeviceIndex, dist: str = "f32") -> None:
     arithmetic a width whose query tile the collect scan cannot stage
     (lmi_range_workspace_bytes answers 0: d_pad > 1248)."""
     check_metric(index, "range search (range_search / bucket_range)")
-    if index.storage == "f32x":
-        raise ValueError("range search is not offered on storage 'f32x' (the split mode)")
+    refuse("f32x", index, "range")
     check_i8(index, "range search")
     if index.corpus64 is not None:
         raise ValueError("range search is not offered on an index that keeps float64 rows (corpus64)")
@@ -1742,11 +1738,7 @@ def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, rad
     tagged = want is not None or avoid is not None
     if tagged and index.tags is None:
         raise ValueError("want / avoid: this index is untagged (build it with `tags`)")
-    q = _rows_f32(q, index.device)
-    classes = _as_torch(classes, index.device, torch.int32)
-    nq, R = classes.shape
-    if q.shape[0] != nq or q.shape[1] != index.d:
-        raise ValueError("query shape does not match the index")
+    q, classes, nq, R = _call_head(index, q, classes)
     value, mask = _tag_words(want, avoid, nq, q.device) if tagged else (None, None)
     if isinstance(radius, torch.Tensor):
         bound = radius.to(device=index.device, dtype=torch.float32).contiguous()
@@ -1755,22 +1747,16 @@ def bucket_range(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, rad
             np.asarray(radius, dtype=np.float32), (nq,)))).to(index.device)
     if bound.shape != (nq,) or bool(torch.isnan(bound).any()):
         raise ValueError(f"radius must be a number or [{nq}] values, none NaN")
-    if qmode is None:
-        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    qmode = _query_class(index, qmode)
     desc = index.desc_for(1, f64=f64)
     need = lib.lmi_range_workspace_bytes(C.byref(desc), nq, R, qmode, int(tagged), int(pair_cap))
     if need == 0:
         raise ValueError("range search: this index or call takes no range scan")
-    if ws is None:
-        ws = index._ws.get("range")
-        if ws is None or ws.numel() < need:
-            ws = index._ws["range"] = torch.empty(max(need, 256), dtype=torch.uint8, device=index.device)
-    else:
-        _workspace(ws, need, "range scan")
+    ws = index._workspace("range", need, ws, "range scan")
     count = torch.empty((nq, R), dtype=torch.int32, device=index.device)
     cand = torch.empty((nq, R, int(pair_cap)), dtype=torch.int64, device=index.device)
     status = torch.zeros((1,), dtype=torch.int32, device=index.device)
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    s = _stream(stream, index.device)
     check("lmi_bucket_range_masked", lib.lmi_bucket_range_masked(
         C.byref(desc), ptr(index.tags) if tagged else None, ptr(value), ptr(mask), None, None, ptr(q), nq,
         q.stride(0), ptr(classes), R, qmode, ptr(bound), int(pair_cap), ptr(cand), ptr(count), ptr(status),
@@ -1789,7 +1775,7 @@ def range_rescore_f64(index: DeviceIndex, q: torch.Tensor, radius64: torch.Tenso
     nq, R, cap = cand.shape
     d64 = torch.empty((nq, R, cap), dtype=torch.float64, device=index.device)
     kept = torch.empty((nq, R), dtype=torch.int32, device=index.device)
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    s = _stream(stream, index.device)
     check("lmi_range_rescore_f64", lib.lmi_range_rescore_f64(
         C.byref(index.desc_for(1, f64=True)), ptr(q), nq, q.stride(0), R, ptr(radius64), cap, ptr(cand),
         ptr(count), ptr(d64), ptr(kept), s))
@@ -1841,14 +1827,9 @@ def rerank_f64(index: DeviceIndex, q: torch.Tensor, pos: torch.Tensor, k: int, s
     if q.shape[0] != nq or q.shape[1] != index.d:
         raise ValueError("rerank_f64: query shape does not match the lists or the index")
     pos = pos.to(index.device).contiguous()
-    if out is None:
-        out = (torch.empty((nq, R, int(k)), dtype=torch.float64, device=index.device),
-               torch.empty((nq, R, int(k)), dtype=torch.int32, device=index.device),
-               torch.zeros((1,), dtype=torch.int32, device=index.device))
-    out_d, out_pos, status = out
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    out_d, out_pos, status = _triple(out, (nq, R, int(k)), torch.float64, index.device)
     check("lmi_rerank_f64", lib.lmi_rerank_f64(C.byref(desc), ptr(q), nq, q.stride(0), R, ptr(pos), k_in, int(k),
-                                               ptr(out_d), ptr(out_pos), ptr(status), s))
+                                               ptr(out_d), ptr(out_pos), ptr(status), _stream(stream, index.device)))
     return out_d, out_pos, status
 
 
@@ -1859,7 +1840,7 @@ def range_pack(index: DeviceIndex, count: torch.Tensor, cand: torch.Tensor, off:
     of out = (d float64, pos int32, query int32), unsorted."""
     lib = _lib.load()
     nq, R, cap = cand.shape
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    s = _stream(stream, index.device)
     check("lmi_range_pack", lib.lmi_range_pack(
         C.byref(index.desc), nq, R, cap, ptr(cand), ptr(count), ptr(off), ptr(d64), ptr(radius64),
         ptr(out[0]), ptr(out[1]), ptr(out[2]), s))
@@ -1888,32 +1869,15 @@ def bucket_topk_f64(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, 
         q = q64.float()
         if torch.equal(q.double(), q64):
             q64 = None
-    q = _rows_f32(q, index.device)
-    classes = _as_torch(classes, index.device, torch.int32)
-    nq, R = classes.shape
-    if q.shape[0] != nq or q.shape[1] != index.d:
-        raise ValueError("query shape does not match the index")
-    if qmode is None:
-        qmode = _lib.LMI_Q_F16 if index.storage == "f16" else _lib.LMI_Q_F32
+    q, classes, nq, R = _call_head(index, q, classes)
+    qmode = _query_class(index, qmode)
     if eps is None:
         eps = refine_eps(index.d_pad, index.storage == "f16" and qmode == _lib.LMI_Q_F16,
                          rounded_inputs=q64 is not None or index.corpus64 is not None)
-    if out is None:
-        out_d = torch.empty((nq, R, k), dtype=torch.float64, device=index.device)
-        out_pos = torch.empty((nq, R, k), dtype=torch.int32, device=index.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=index.device)
-    else:
-        out_d, out_pos, status = out
+    out_d, out_pos, status = _triple(out, (nq, R, k), torch.float64, index.device)
     desc = index.desc_for(k, f64=True)
-    need = lib.lmi_scan_f64_workspace_bytes(C.byref(desc), nq, R, k, qmode)
-    if ws is None:
-        ws = index._ws.get("f64")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 256), dtype=torch.uint8, device=index.device)
-            index._ws["f64"] = ws
-    else:
-        _workspace(ws, need, "float64 scan")
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    ws = index._workspace("f64", lib.lmi_scan_f64_workspace_bytes(C.byref(desc), nq, R, k, qmode), ws, "float64 scan")
+    s = _stream(stream, index.device)
     if index.storage == "f32x":
         seed_round0 = False  # (the split mode scans every pair whole)
     flags = (_lib.LMI_Q_SEED_ROUND0 if seed_round0 else 0) | phases
@@ -1947,7 +1911,7 @@ def split_sample_fallback_count(index: DeviceIndex, nq: int, R: int, k: int, ws=
     if ws is None:
         ws = index._ws.get("f64" if f64 else "buf")
     n = C.c_int32(0)
-    s = stream if stream is not None else _lib.stream_handle(index.device)
+    s = _stream(stream, index.device)
     check("lmi_split_sample_fallback_count", lib.lmi_split_sample_fallback_count(
         ptr(ws), C.byref(index.desc_for(k)), nq, R, k, C.byref(n), s))
     return int(n.value)
@@ -1971,7 +1935,7 @@ def merge_topk(d_in: torch.Tensor, pos_in: torch.Tensor, k: int, stream=None):
     f64 = d_in.dtype == torch.float64
     out_d = torch.empty(d_in.shape[1:], dtype=d_in.dtype, device=d_in.device)
     out_pos = torch.empty(d_in.shape[1:], dtype=torch.int32, device=d_in.device)
-    s = stream if stream is not None else _lib.stream_handle(d_in.device)
+    s = _stream(stream, d_in.device)
     fn = "lmi_merge_topk_f64" if f64 else "lmi_merge_topk"
     check(fn, getattr(_lib.load(), fn)(ptr(d_in.contiguous()), ptr(pos_in.contiguous()), G, rows, k,
                                        ptr(out_d), ptr(out_pos), s))
@@ -2053,7 +2017,7 @@ def replay_device(classes: torch.Tensor, lists_d: torch.Tensor, lists_pos: torch
         thr = _as_torch(thr_round0, dev, torch.float64).reshape(-1)
         if thr.numel() != nq:
             raise ValueError("threshold_dist must have one value per query")
-    s = stream if stream is not None else _lib.stream_handle(dev)
+    s = _stream(stream, dev)
     check("lmi_replay_device_phase", lib.lmi_replay_device_phase(
         int(phases), int(f64), ptr(classes), nq, R, k_list, ptr(lists_d), ptr(lists_pos), k_round,
         k_final, ptr(bucket_size), n_b, ptr(pos_to_id), int(pos_to_id.numel()),
@@ -2170,52 +2134,36 @@ class Searcher:
         want words of a filtered scan (want_words; float32 lists only).
         `rerank` (checked by check_rerank; f64, one GPU): the 8-bit scan keeps
         `rerank` entries a pair and rerank_f64 cuts them to k_list float64 ones.
-        `few` = (few_rows,): the few-query scan (_check_few made the checks)."""
+        `few` = (few_rows,): the few-query scan (_checked made the checks)."""
+        nq, R = classes.shape
+        dev = self.index.device
         if few is not None:
             if qmode != _lib.LMI_Q_F16:
-                # (the default path would scan these queries in exact fp32; this
-                # kernel rounds them to fp16)
-                raise ValueError("few=True (the few-query scan) takes fp16-exact queries (LMI_Q_F16) alone: "
-                                 "a value of this batch is not fp16-representable")
-            nq, R = classes.shape
-            dev = self.index.device
-            st = status_out if status_out is not None else torch.zeros((1,), dtype=torch.int32, device=dev)
-            out = (torch.empty((nq, R, k_list), dtype=torch.float32, device=dev),
-                   torch.empty((nq, R, k_list), dtype=torch.int32, device=dev), st)
-            d, pos, status = bucket_topk(self.index, q_search, classes, k_list, out=out, few=True, few_rows=few[0])
+                refuse("few", self.index, "batch")
+            d, pos, status = bucket_topk(self.index, q_search, classes, k_list, few=True, few_rows=few[0],
+                                         out=_triple(None, (nq, R, k_list), torch.float32, dev, status_out))
             if lap:
                 lap("scan")
             return d, pos, status
         if rerank is not None:
-            st = status_out if status_out is not None else torch.zeros((1,), dtype=torch.int32,
-                                                                       device=self.index.device)
-            nq, R = classes.shape
-            scan_out = (torch.empty((nq, R, rerank), dtype=torch.float32, device=self.index.device),
-                        torch.empty((nq, R, rerank), dtype=torch.int32, device=self.index.device), st)
             # (the over-fetch runs on the ring's 16-entry lists where the plan has them)
-            _, pos2, _ = bucket_topk(self.index, q_search, classes, rerank, qmode=qmode, out=scan_out, ws=ws,
-                                     want=want, lists16=True)
+            _, pos2, st = bucket_topk(self.index, q_search, classes, rerank, qmode=qmode, ws=ws, want=want,
+                                      lists16=True, out=_triple(None, (nq, R, rerank), torch.float32, dev, status_out))
             if lap:
                 lap("scan")
-            d, pos, status = rerank_f64(self.index, q_search, pos2, k_list, out=(
-                torch.empty((nq, R, k_list), dtype=torch.float64, device=self.index.device),
-                torch.empty((nq, R, k_list), dtype=torch.int32, device=self.index.device), st))
+            d, pos, status = rerank_f64(self.index, q_search, pos2, k_list,
+                                        out=_triple(None, (nq, R, k_list), torch.float64, dev, st))
             if lap:
                 lap("rerank")
             return d, pos, status
         out = None
         if not self.exchange and status_out is not None:
-            nq, R = classes.shape
-            dev = self.index.device
-            out = (torch.empty((nq, R, k_list), dtype=torch.float64 if f64 else torch.float32,
-                               device=dev),
-                   torch.empty((nq, R, k_list), dtype=torch.int32, device=dev), status_out)
+            out = _triple(None, (nq, R, k_list), torch.float64 if f64 else torch.float32, dev, status_out)
         if self.exchange:
             # the lists and the status word land in this rank's slice of the
             # all-gather's packed send buffer (li.dist.packed_lists)
             from .dist import packed_lists
-            nq, R = classes.shape
-            buf, dv, pv, sv = packed_lists(nq * R, k_list, f64, self.index.device)
+            buf, dv, pv, sv = packed_lists(nq * R, k_list, f64, dev)
             out = (dv.view(nq, R, k_list), pv.view(nq, R, k_list), sv)
         if f64 and self.exchange and global_band(self.index, nq, R, k_list, qmode):
             # the band decided over every rank's lists (ABI 10): the ranks'
@@ -2277,68 +2225,66 @@ class Searcher:
         `avoid` (the same forms; alone it means want = 0): and only rows with
         (tag & avoid) == 0.  A query that wants and avoids one bit is a
         ValueError, like every refusal of `want`, before anything is launched."""
-        self._check_few(few, few_rows, k_list, dist, rerank, want, avoid, lists16, q_search, classes, R)
-        if lists16:
-            with i8_lists16():
-                return self.lists(q_nav, q_search, R, k_list, classes=classes, dist=dist, stop_mass=stop_mass,
-                                  min_probes=min_probes, want=want, avoid=avoid, rerank=rerank)
+        ctx = i8_lists16().__enter__() if lists16 else None
+        try:
+            k_list, want, rerank = self._checked(k_list, R, q_search, classes, dist, stop_mass, min_probes, want,
+                                                 avoid, rerank, lists16, few, few_rows)
+            if classes is None:
+                classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
+            q_search = _rows_q(q_search, self.index.device)
+            d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
+                                        want=want, rerank=rerank, few=(few_rows,) if few else None)
+            return classes, d, pos, status
+        finally:
+            if ctx is not None:
+                ctx.__exit__()
+
+    def _checked(self, k_list: int, R: int, q_search, classes, dist, stop_mass, min_probes, want, avoid, rerank,
+                 lists16, few, few_rows, per_query: bool = True):
+        """Every check lists / search make of their keywords, in one order, before the router is launched or a word
+        is uploaded: few=True (check_few, and what the Searcher adds: float32 lists, no re-rank, one process),
+        the stop rule, a consumed index, the lists' shape, and want / avoid.  Returns (k_list, the scan's `want`
+        -- filter_words' device words or None --, rerank as an int or None)."""
+        ix = self.index
+        _check_few_rows(few, few_rows)
+        if few:
+            for given, row in ((dist != "f32", "dist"), (rerank is not None, "rerank"), (self.exchange, "exchange")):
+                if given:
+                    refuse("few", ix, row)
+            check_few(ix, int((q_search if classes is None else classes).shape[0]), R, k_list, few_rows, want=want,
+                      avoid=avoid, lists16=lists16)
         check_stop(stop_mass, min_probes)
-        self.index._check_live()
-        self._check_i8_lists(k_list, dist, rerank)
-        if self.index.storage in MX and (want is not None or avoid is not None):
-            check_i8(self.index, "filtered search (want / avoid)")
+        ix._check_live()
+        self._check_list_shape(k_list, dist, rerank)
+        rerank = None if rerank is None else int(rerank)
+        want_w = None
         if want is not None or avoid is not None:
-            check_metric(self.index, "filtered search (want / avoid)")
-            nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
+            _check_filtered(ix)
             # (re-ranked: the filtered scan is the float32 one of `rerank` entries)
-            want = filter_words(self.index, want, avoid, nq, *((k_list, dist) if rerank is None else
-                                                               (int(rerank), "f32")))
-        if classes is None:
-            classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
-        q_search = _rows_q(q_search, self.index.device)
-        d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
-                                    want=want, rerank=None if rerank is None else int(rerank),
-                                    few=(few_rows,) if few else None)
-        return classes, d, pos, status
+            want_w = filter_words(ix, want, avoid, int((q_search if classes is None else classes).shape[0]),
+                                  *((k_list, dist) if rerank is None else (rerank, "f32")), per_query=per_query)
+        return k_list, want_w, rerank
 
-    def _check_few(self, few, few_rows, k_list, dist, rerank, want, avoid, lists16, q_search, classes, R) -> None:
-        """lists / search with few=True: check_few, and what the Searcher adds
-        (float32 lists, no re-rank, one process); ValueError before any launch."""
-        if not few:
-            if few_rows is not None:
-                raise ValueError("few_rows comes with few=True")
-            return
-        if dist != "f32":
-            raise ValueError("few=True (the few-query scan) takes dist='f32' alone")
+    def _check_list_shape(self, k_list: int, dist: str, rerank=None) -> None:
+        """The lists a call may ask of this index: float32 ones of at most LMI_MAX_K entries where a metric or a
+        quantised storage restricts them -- or, with `rerank`, float64 ones re-ranked from the kept fp16 rows
+        (check_rerank, on any index); ValueError otherwise, before anything is launched."""
+        ix = self.index
+        asked = ()  # (what a metric or a quantised storage does not offer; nothing is built on the timed path)
+        K = _lib.LMI_MAX_K
+        if dist != "f32" or k_list > K:
+            asked = [what for asks, what in ((dist != "f32", "dist='f64' (float64 lists)"),
+                                             (k_list > K, f"k_list = {k_list} > {K}")) if asks]
         if rerank is not None:
-            raise ValueError("few=True (the few-query scan) takes no rerank")
-        if self.exchange:
-            raise ValueError("few=True (the few-query scan) takes one GPU (no list exchange over a process group)")
-        nq = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-        check_few(self.index, nq, R, k_list, few_rows, want=want, avoid=avoid, lists16=lists16)
-
-    def _check_i8_lists(self, k_list: int, dist: str, rerank=None) -> None:
-        """The lists an index of storage "i8" answers: float32, at most
-        LMI_MAX_K entries -- or, with `rerank`, float64 ones re-ranked from its
-        kept fp16 rows (check_rerank, on any index); ValueError otherwise,
-        before anything is launched."""
-        if self.index.metric != "cosine":
-            if rerank is not None:
-                check_metric(self.index, "rerank")
-            if dist != "f32":
-                check_metric(self.index, "dist='f64' (float64 lists)")
-            if k_list > _lib.LMI_MAX_K:
-                check_metric(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
-        if rerank is not None:
-            check_rerank(self.index, rerank, k_list, dist)
+            for what in ("rerank", *asked):
+                check_metric(ix, what)
+            check_rerank(ix, rerank, k_list, dist)
             return
-        if self.index.storage in QUANTIZED:
-            if dist != "f32":
-                check_i8(self.index, "dist='f64' (float64 lists)")
-            if k_list > _lib.LMI_MAX_K:
-                check_i8(self.index, f"k_list = {k_list} > {_lib.LMI_MAX_K}")
-        if self.index.storage in MX:
-            check_mx4_k(k_list, self.index.storage)
+        for what in asked:
+            check_metric(ix, what)
+            check_i8(ix, what)
+        if ix.storage in MX:
+            check_mx4_k(k_list, ix.storage)
 
     def route(self, q_nav, R: int, stop_mass=None, min_probes: int = 1) -> torch.Tensor:
         """K1 classes [nq, R]; with G > 1 ranks each routes nq/G queries and
@@ -2638,179 +2584,136 @@ class Searcher:
         lists back and runs lmi_replay (same results, the checker of the device
         replay).  `timings` (measurement only) receives per-stage wall times in
         ms; the stages are then separated by stream synchronisations."""
-        import time
-        if few or few_rows is not None:  # (before the lists16 re-entry, which would drop them)
-            self._check_few(few, few_rows, k_round if semantics == "reference" else max(k_round, k), dist, rerank,
-                            want, avoid, lists16, q_search, classes, R)
-        if lists16:
-            with i8_lists16():
-                return self.search(q_nav, q_search, R, k, k_round=k_round, use_threshold=use_threshold,
-                                   classes=classes, timings=timings, replay_on=replay_on, semantics=semantics,
-                                   dist=dist, stop_mass=stop_mass, min_probes=min_probes, want=want, avoid=avoid,
-                                   rerank=rerank)
-        check_stop(stop_mass, min_probes)
-        self.index._check_live()
-        if self.index.storage in MX and (want is not None or avoid is not None):
-            check_i8(self.index, "filtered search (want / avoid)")
         if replay_on not in ("device", "host"):
             raise ValueError("replay_on must be 'device' or 'host'")
         if semantics not in ("reference", "exact"):
             raise ValueError("semantics must be 'reference' or 'exact'")
         if dist not in ("f32", "f64"):
             raise ValueError("dist must be 'f32' or 'f64'")
-        k_list = k_round if semantics == "reference" else max(k_round, k)
-        self._check_i8_lists(k_list, dist, rerank)
-        rerank = None if rerank is None else int(rerank)
-        f64 = dist == "f64"
-        kmax = _lib.LMI_MAX_K_F64 if f64 else _lib.LMI_MAX_K_PASSES
-        if k_list > kmax:
-            raise ValueError(f"k={k_list} > {kmax}")
-        if k_round > _lib.LMI_REPLAY_DEVICE_MAX_KR or k > _lib.LMI_REPLAY_DEVICE_MAX_K:
-            replay_on = "host"  # the device replay holds rows of <= 32 / 64 entries
-        dev = self.index.device
-        want_w = None
-        if want is not None or avoid is not None:
-            check_metric(self.index, "filtered search (want / avoid)")
-            nq_w = int(q_search.shape[0]) if classes is None else int(classes.shape[0])
-            want_w = filter_words(self.index, want, avoid, nq_w, *((k_list, dist) if rerank is None else
-                                                                   (rerank, "f32")),
-                                  per_query=semantics == "exact")
-        sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
+        ctx = i8_lists16().__enter__() if lists16 else None
+        try:
+            k_list, want_w, rerank = self._checked(
+                k_round if semantics == "reference" else max(k_round, k), R, q_search, classes, dist, stop_mass,
+                min_probes, want, avoid, rerank, lists16, few, few_rows, per_query=semantics == "exact")
+            f64 = dist == "f64"
+            kmax = _lib.LMI_MAX_K_F64 if f64 else _lib.LMI_MAX_K_PASSES
+            if k_list > kmax:
+                raise ValueError(f"k={k_list} > {kmax}")
+            if k_round > _lib.LMI_REPLAY_DEVICE_MAX_KR or k > _lib.LMI_REPLAY_DEVICE_MAX_K:
+                replay_on = "host"  # the device replay holds rows of <= 32 / 64 entries
+            dev = self.index.device
+            sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if timings is not None else None
+            tl = [time.perf_counter()]
 
-        def lap(name, t0):
-            if sync:
-                sync()
-                t1 = time.perf_counter()
-                timings[name] = timings.get(name, 0.0) + (t1 - t0) * 1e3
-                return t1
-            return t0
+            def lap(name):
+                if sync:
+                    sync()
+                    t1 = time.perf_counter()
+                    timings[name] = timings.get(name, 0.0) + (t1 - tl[0]) * 1e3
+                    tl[0] = t1
 
-        t0 = time.perf_counter()
-        q_search = _rows_q(q_search, dev)
-        qmode = self.qmode(q_search)
-        if classes is None:
-            classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
-        t0 = lap("router", t0)
+            q_search = _rows_q(q_search, dev)
+            qmode = self.qmode(q_search)
+            if classes is None:
+                classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
+            lap("router")
+            nq = classes.shape[0]
+            # (valid while the merged width k is at most the round lists' k_round:
+            # the running threshold then never exceeds round 0's k-th distance;
+            # with k > k_round the first merge pads with 10000s)
+            seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
+                    and want_w is None and self.index.metric == "cosine" and not few)
+            h_st = self._host("st", (2,), torch.int32)
+            # the device replay's arm: the answer and both status words in one buffer, one D2H copy
+            ans, w_ans = None, k_round if classes.shape[1] == 1 else k
 
-        def done(out):
+            def scan(mode, lap_scan, few_arg):
+                nonlocal ans
+                if semantics == "reference" and replay_on == "device":
+                    ans = answer_buffer(nq, w_ans, dev)
+                return self._scan(q_search, classes, k_list, mode, f64, lap_scan,
+                                  status_out=None if ans is None else ans[3][0:1], seed_round0=seed, want=want_w,
+                                  rerank=rerank, few=few_arg)
+
+            def check_status(st, rst=0):
+                # every rank holds the OR of all ranks' scan bits (they rode the
+                # all-gather) and runs the same replay: all ranks raise together
+                if st & _lib.LMI_STATUS_INTERNAL or rst:
+                    raise RuntimeError(f"search: internal status {st}/{rst}")
+                return bool(st & _lib.LMI_STATUS_QUERY_NOT_F16)
+
+            # finish(d, pos, status) -> (answer, scan status, replay status): the lists to the answer on the host
+            if semantics == "exact":
+                def finish(d, pos, status):
+                    _, p2id = self._device_tables()
+                    Rr = classes.shape[1]
+                    md, mp = merge_topk(d.view(nq, Rr, k_list).transpose(0, 1).contiguous(),
+                                        pos.view(nq, Rr, k_list).transpose(0, 1).contiguous(), k_list)
+                    md, mp = md[:, :k], mp[:, :k]
+                    none = mp < 0
+                    ids = p2id[mp.clamp(min=0).long()]
+                    rd = torch.where(none, torch.full_like(md, 10000.0), md).double()
+                    ra = torch.where(none, torch.zeros_like(ids), ids).to(torch.int32)
+                    lap("replay")
+                    h_d = self._host("xd", tuple(rd.shape), torch.float64)
+                    h_a = self._host("xa", tuple(ra.shape), torch.int32)
+                    h_d.copy_(rd, non_blocking=True)
+                    h_a.copy_(ra, non_blocking=True)
+                    h_st[0:1].copy_(status, non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+                    lap("d2h")
+                    return (h_d.numpy().copy(), h_a.numpy().view(np.uint32).copy()), int(h_st[0]), 0
+            elif replay_on == "device":
+                def finish(d, pos, status):
+                    bsz, p2id = self._device_tables()
+                    replay_device(classes, d, pos, k_round=k_round, k_final=k, pos_to_id=p2id,
+                                  bucket_size=bsz if want_w is None else torch.from_numpy(
+                                      np.ascontiguousarray(bsize, dtype=np.int64)).to(dev),
+                                  use_threshold=use_threshold, out=(ans[1], ans[2], ans[3][1:2]))
+                    # a fresh pinned buffer from torch's caching host allocator,
+                    # handed to the caller as numpy views (no host copy; it returns
+                    # to the cache when the caller drops the arrays)
+                    h = torch.empty(tuple(ans[0].shape), dtype=torch.int32, pin_memory=True)
+                    h.copy_(ans[0], non_blocking=True)
+                    lap("replay")
+                    torch.cuda.current_stream(dev).synchronize()
+                    lap("d2h")
+                    hd, ha, st0, st1 = answer_views(h, nq, w_ans)
+                    return (hd, ha), st0, st1
+            else:
+                def finish(d, pos, status):
+                    h_cls = self._host("cls", (nq, R), torch.int32)
+                    h_d = self._host("d", tuple(d.shape), d.dtype)
+                    h_pos = self._host("pos", tuple(pos.shape), torch.int32)
+                    h_cls.copy_(classes, non_blocking=True)
+                    h_d.copy_(d, non_blocking=True)
+                    h_pos.copy_(pos, non_blocking=True)
+                    h_st[0:1].copy_(status, non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+                    lap("d2h")
+                    # (the lists: lmi_replay reads them below, once they are final)
+                    return (h_cls.numpy(), h_d.numpy(), h_pos.numpy()), int(h_st[0]), 0
+
+            d, pos, status = scan(qmode, lap if sync else None, (few_rows,) if few else None)
+            # (filtered: the replay's bucket sizes are the eligible row counts)
+            bsize = self.index.bucket_size
+            if want_w is not None and semantics == "reference":
+                bsize = self.eligible_bucket_size(int(want or 0), int(avoid or 0))
+            answer, st, rst = finish(d, pos, status)
+            if check_status(st, rst):
+                # the cached fp16 check was stale: redo once with exact fp32 MFMA, its stages untimed -- on the
+                # default path also under few=True, whose kernel takes fp16-exact queries alone (unseeded then too)
+                timed, sync = sync, None
+                answer, st, rst = finish(*scan(_lib.LMI_Q_F32, None, None))
+                check_status(st & ~_lib.LMI_STATUS_QUERY_NOT_F16, rst)
+                sync = timed  # (the host replay below is timed, the rescan with it)
+            if semantics == "reference" and replay_on == "host":
+                answer = replay(*answer, k_round=k_round, k_final=k, bucket_size=bsize,
+                                pos_to_id=self.index.pos_to_id, use_threshold=use_threshold)
+                lap("replay")
             if timings is not None and stop_mass is not None:
                 timings["mean_probes"] = float((classes >= 0).sum().item()) / max(1, classes.shape[0])
-            return out
-        tl = [t0]
-
-        def lap_at(name):
-            tl[0] = lap(name, tl[0])
-
-        nq = classes.shape[0]
-        ans = None
-        if semantics == "reference" and replay_on == "device":
-            # the answer and both status words in one buffer: one D2H copy
-            w_ans = k_round if classes.shape[1] == 1 else k
-            ans = answer_buffer(nq, w_ans, dev)
-        # (valid while the merged width k is at most the round lists' k_round:
-        # the running threshold then never exceeds round 0's k-th distance;
-        # with k > k_round the first merge pads with 10000s)
-        seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
-                and want_w is None and self.index.metric == "cosine" and not few)
-        d, pos, status = self._scan(q_search, classes, k_list, qmode, f64, lap_at if sync else None,
-                                    status_out=None if ans is None else ans[3][0:1],
-                                    seed_round0=seed, want=want_w, rerank=rerank,
-                                    few=(few_rows,) if few else None)
-        # (filtered: the replay's bucket sizes are the eligible row counts)
-        bsize = self.index.bucket_size
-        if want_w is not None and semantics == "reference":
-            bsize = self.eligible_bucket_size(int(want or 0), int(avoid or 0))
-        t0 = tl[0]
-        h_st = self._host("st", (2,), torch.int32)
-
-        def check_status(st, rst=0):
-            # every rank holds the OR of all ranks' scan bits (they rode the
-            # all-gather) and runs the same replay: all ranks raise together
-            if st & _lib.LMI_STATUS_INTERNAL or rst:
-                raise RuntimeError(f"search: internal status {st}/{rst}")
-            return bool(st & _lib.LMI_STATUS_QUERY_NOT_F16)
-
-        if semantics == "exact":
-            _, p2id = self._device_tables()
-
-            def exact(d, pos):
-                Rr = classes.shape[1]
-                md, mp = merge_topk(d.view(nq, Rr, k_list).transpose(0, 1).contiguous(),
-                                    pos.view(nq, Rr, k_list).transpose(0, 1).contiguous(), k_list)
-                md, mp = md[:, :k], mp[:, :k]
-                none = mp < 0
-                ids = p2id[mp.clamp(min=0).long()]
-                return (torch.where(none, torch.full_like(md, 10000.0), md).double(),
-                        torch.where(none, torch.zeros_like(ids), ids).to(torch.int32))
-
-            rd, ra = exact(d, pos)
-            t0 = lap("replay", t0)
-            h_d = self._host("xd", tuple(rd.shape), torch.float64)
-            h_a = self._host("xa", tuple(ra.shape), torch.int32)
-            h_d.copy_(rd, non_blocking=True)
-            h_a.copy_(ra, non_blocking=True)
-            h_st[0:1].copy_(status, non_blocking=True)
-            torch.cuda.current_stream(dev).synchronize()
-            t0 = lap("d2h", t0)
-            if check_status(int(h_st[0])):
-                # the cached fp16 check was stale: redo with exact fp32 MFMA
-                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64, want=want_w,
-                                            rerank=rerank)
-                rd, ra = exact(d, pos)
-                h_d.copy_(rd)
-                h_a.copy_(ra)
-                h_st[0:1].copy_(status)
-                check_status(int(h_st[0]) & ~_lib.LMI_STATUS_QUERY_NOT_F16)
-            return done((h_d.numpy().copy(), h_a.numpy().view(np.uint32).copy()))
-        if replay_on == "device":
-            bsz, p2id = self._device_tables()
-            if want_w is not None:  # (here semantics == "reference")
-                bsz = torch.from_numpy(np.ascontiguousarray(bsize, dtype=np.int64)).to(dev)
-
-            def run_replay(d, pos, ans):
-                replay_device(classes, d, pos, k_round=k_round, k_final=k, bucket_size=bsz,
-                              pos_to_id=p2id, use_threshold=use_threshold,
-                              out=(ans[1], ans[2], ans[3][1:2]))
-                # a fresh pinned buffer from torch's caching host allocator,
-                # handed to the caller as numpy views (no host copy; it returns
-                # to the cache when the caller drops the arrays)
-                h = torch.empty(tuple(ans[0].shape), dtype=torch.int32, pin_memory=True)
-                h.copy_(ans[0], non_blocking=True)
-                return h
-
-            h = run_replay(d, pos, ans)
-            t0 = lap("replay", t0)
-            torch.cuda.current_stream(dev).synchronize()
-            t0 = lap("d2h", t0)
-            hd, ha, st0, st1 = answer_views(h, nq, w_ans)
-            if check_status(st0, st1):
-                ans = answer_buffer(nq, w_ans, dev)
-                d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                            status_out=ans[3][0:1], seed_round0=seed, want=want_w,
-                                            rerank=rerank)
-                h = run_replay(d, pos, ans)
-                torch.cuda.current_stream(dev).synchronize()
-                hd, ha, st0, st1 = answer_views(h, nq, w_ans)
-                check_status(st0 & ~_lib.LMI_STATUS_QUERY_NOT_F16, st1)
-            return done((hd, ha))
-        h_cls = self._host("cls", (nq, R), torch.int32)
-        h_d = self._host("d", tuple(d.shape), d.dtype)
-        h_pos = self._host("pos", tuple(pos.shape), torch.int32)
-        h_cls.copy_(classes, non_blocking=True)
-        h_d.copy_(d, non_blocking=True)
-        h_pos.copy_(pos, non_blocking=True)
-        h_st[0:1].copy_(status, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        t0 = lap("d2h", t0)
-        if check_status(int(h_st[0])):
-            d, pos, status = self._scan(q_search, classes, k_list, _lib.LMI_Q_F32, f64,
-                                        seed_round0=seed, want=want_w, rerank=rerank)
-            h_d.copy_(d)
-            h_pos.copy_(pos)
-            h_st[0:1].copy_(status)
-            check_status(int(h_st[0]) & ~_lib.LMI_STATUS_QUERY_NOT_F16)
-        out = replay(h_cls.numpy(), h_d.numpy(), h_pos.numpy(), k_round=k_round, k_final=k,
-                     bucket_size=bsize, pos_to_id=self.index.pos_to_id,
-                     use_threshold=use_threshold)
-        lap("replay", t0) if sync else None
-        return done(out)
+            return answer
+        finally:
+            if ctx is not None:
+                ctx.__exit__()

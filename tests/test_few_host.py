@@ -101,6 +101,7 @@ PY_REFUSED = {
     "qmode f32": ({}, lambda ix, s: topk(ix, qmode=_lib.LMI_Q_F32)),
     "few_rows 48": ({}, lambda ix, s: topk(ix, few_rows=48)),
     "few_rows alone": ({}, lambda ix, s: index.bucket_topk(ix, Q, CLS, 10, few_rows=64)),
+    "few_rows alone lists16": ({}, lambda ix, s: index.bucket_topk(ix, Q, CLS, 10, lists16=True, few_rows=64)),
     "family tagged": ({}, lambda ix, s: index.scan_family(ix, 10, tagged=True, few=True)),
     "lists f64": ({}, lambda ix, s: s.lists(None, Q, 1, 10, classes=CLS, few=True, dist="f64")),
     "lists rerank": ({}, lambda ix, s: s.lists(None, Q, 1, 10, classes=CLS, few=True, rerank=16)),
