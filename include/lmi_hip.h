@@ -378,6 +378,37 @@ int lmi_bucket_topk_few(const lmi_index_desc* idx, const float* q, int32_t nq, i
                         int32_t R, int32_t k, int32_t few_rows, void* workspace, size_t ws_bytes, float* out_d,
                         int32_t* out_pos, int32_t* status, void* stream);
 
+/* K2 inside an allow-list of rows (additions: LMI_ABI_VERSION does not change):
+ * lmi_bucket_topk_few's lists -- fp16 rows, queries taken as LMI_Q_F16, 1 <= k <=
+ * LMI_MAX_K, the same distance, outputs and status bits -- over the rows of an
+ * explicit subset alone, for a batch of any size (scan_subset_kernel: the rows
+ * are fetched by position, so the bytes read follow the subset, not the corpus).
+ * sub_pos: device [n_sub] rows of the index (0 <= row < n_rows), ascending, no
+ * row twice; they are then sorted by bucket.  sub_off: device int64
+ * [n_buckets + 1], bucket c's rows are sub_pos[sub_off[c] .. sub_off[c + 1]).
+ * max_range: at least the longest such range (a bucket with a longer one lists
+ * nothing and sets LMI_STATUS_INTERNAL).  Each list is the exact top-k by
+ * (distance, position) of the probed bucket's rows in the subset; a pair with
+ * fewer than k pads (+inf, -1) as an under-full bucket does.  sub_rows: entries
+ * of the subset per work item, a multiple of 32, or 0: the call chooses (about
+ * six items per CU, at least 256 entries); above max_range it is cut to it.
+ * n_sub == 0: the lists are all padding and no scan is launched.  The workspace
+ * is lmi_scan_subset_workspace_bytes of the same arguments, 0 for a call this
+ * entry refuses.  Refused before any launch, device or no device
+ * (lmi_last_error names the subset scan and the reason) -- LMI_E_UNSUPPORTED:
+ * k > LMI_MAX_K, a storage other than LMI_F16, d_pad > 992, idx->corpus32 /
+ * corpus64 / chunk_centroid, a bucket of 2 GiB of rows or more (max_chunks *
+ * chunk_rows * 2 d_pad); LMI_E_INVALID: sub_rows negative or no multiple of
+ * 32, k < 1, n_sub or max_range out of range, join workgroups set on the
+ * thread.  It has no qmode: no phase, seed or join flag, no tags and no metric
+ * other than cosine can be asked of it. */
+size_t lmi_scan_subset_workspace_bytes(const lmi_index_desc* idx, int64_t n_sub, int32_t max_range, int32_t nq,
+                                       int32_t R, int32_t k, int32_t sub_rows);
+int lmi_bucket_topk_subset(const lmi_index_desc* idx, const int32_t* sub_pos, const int64_t* sub_off, int64_t n_sub,
+                           int32_t max_range, const float* q, int32_t nq, int32_t ldq, const int32_t* classes,
+                           int32_t R, int32_t k, int32_t sub_rows, void* workspace, size_t ws_bytes, float* out_d,
+                           int32_t* out_pos, int32_t* status, void* stream);
+
 /* The per-row word of LMI_METRIC_L2: sqnorm[t] = sum_j rows[i][j]^2 over j < d,
  * accumulated in float64 and rounded once to float32, t = dst_rows ? dst_rows[i]
  * : i (an index build scatters each block into its bucket-sorted slots).  One

@@ -39,23 +39,13 @@
 //              (distance, position), positions -> global positions.
 // The LDS reads inside the stage loop are inline asm: a C++ LDS access there
 // makes the compiler wait for every DMA in flight first.
+#include "lmi_few_lds.hpp"
 #include "lmi_scan_internal.hpp"
 
 #include <algorithm>
 
 namespace lmi {
 namespace {
-
-namespace few {
-constexpr int KSEG = 128;                 // k elements of a stage
-constexpr int ROWB = KSEG * 2;            // bytes of one row in one stage
-constexpr int STAGE = 32 * ROWB;          // 8 KiB
-constexpr int NSLOT = 3;                  // per wave: one read, two in flight
-constexpr int NORMB = 32 * 4;             // a stage's norms
-constexpr int QPAD = 8;                   // elements: the query rows' pitch is 2 d_pad + 16 B
-constexpr int DMAS = STAGE / 1024 + 1;    // DMA instructions of a stage
-constexpr int TAB_HDR = 4, TAB_ENT = 5;   // the group table: (n groups, n items, -, -), then entries
-}  // namespace few
 
 struct FewArgs {
     const _Float16* corpus;
@@ -73,42 +63,6 @@ struct FewArgs {
 
 size_t few_lds_bytes(int d_pad) {
     return (size_t)32 * (d_pad + few::QPAD) * 2 + (size_t)kWaves * few::NSLOT * (few::STAGE + few::NORMB);
-}
-
-// four / eight 16-byte LDS reads in flight and their wait, out of the compiler's sight
-__device__ __forceinline__ void lds_read4(half8 (&v)[8], int o, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3) {
-    asm volatile(
-        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[o]), "=&v"(v[o + 1]), "=&v"(v[o + 2]), "=&v"(v[o + 3])
-        : "v"(a0), "v"(a1), "v"(a2), "v"(a3)
-        : "memory");
-}
-__device__ __forceinline__ void lds_read8_affine(half8 (&v)[8], uint32_t a) {
-    asm volatile(
-        "ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:32\n\tds_read_b128 %2, %8 offset:64\n\t"
-        "ds_read_b128 %3, %8 offset:96\n\tds_read_b128 %4, %8 offset:128\n\tds_read_b128 %5, %8 offset:160\n\t"
-        "ds_read_b128 %6, %8 offset:192\n\tds_read_b128 %7, %8 offset:224\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-        : "v"(a)
-        : "memory");
-}
-// (a short last segment: two fragments at a time, so that no read leaves the query row)
-template <int O>
-__device__ __forceinline__ void lds_read2_affine(half8 (&v)[8], uint32_t a) {
-    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(v[O]), "=&v"(v[O + 1])
-                 : "v"(a), "i"(32 * O), "i"(32 * O + 32)
-                 : "memory");
-}
-__device__ __forceinline__ void lds_read_norms(f32x4 (&n)[4], uint32_t a) {
-    asm volatile(
-        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:32\n\tds_read_b128 %2, %4 offset:64\n\t"
-        "ds_read_b128 %3, %4 offset:96\n\ts_waitcnt lgkmcnt(0)"
-        : "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3])
-        : "v"(a)
-        : "memory");
 }
 
 // The (bucket, group)s of a call and each one's first item.  The plan grouped
@@ -514,6 +468,18 @@ int launch_scan_few(const FewArgs& a, hipStream_t s) {
 
 }  // namespace
 
+int launch_few_merge(int kl, const uint64_t* partial, int32_t max_slices, int32_t few_rows, const int32_t* pair_q,
+                     const int32_t* pair_bucket, const int64_t* off, const int32_t* gpos, int64_t n_rows, int32_t P,
+                     int32_t k, float* out_d, int32_t* out_pos, int32_t* status, hipStream_t s) {
+#define LMI_FM(KLV)                                                                                             \
+    hipLaunchKernelGGL((few_merge_kernel<KLV>), dim3(P), dim3(64), 0, s, partial, max_slices, few_rows, pair_q, \
+                       pair_bucket, off, gpos, n_rows, k, out_d, out_pos, status)
+    if (kl == 10) LMI_FM(10); else LMI_FM(16);
+#undef LMI_FM
+    LMI_LAUNCH_CHECK("few_merge_kernel");
+    return LMI_OK;
+}
+
 static_assert(32 * (kFewMaxDPad + few::QPAD) * 2 + kWaves * few::NSLOT * (few::STAGE + few::NORMB) <= 160 * 1024,
               "LDS budget");
 
@@ -577,11 +543,6 @@ extern "C" int lmi_bucket_topk_few(const lmi_index_desc* idx, const float* q, in
     a.partial = (uint64_t*)(ws + f.partial);
     LMI_TRY(f.kl == 10 ? launch_scan_few<10>(a, s) : launch_scan_few<16>(a, s));
 
-#define LMI_FM(KLV)                                                                                          \
-    hipLaunchKernelGGL((few_merge_kernel<KLV>), dim3(P), dim3(64), 0, s, a.partial, f.max_slices, f.few_rows, \
-                       pair_q, pair_bucket, idx->bucket_off, idx->gpos, idx->n_rows, k, out_d, out_pos, status)
-    if (f.kl == 10) LMI_FM(10); else LMI_FM(16);
-#undef LMI_FM
-    LMI_LAUNCH_CHECK("few_merge_kernel");
-    return LMI_OK;
+    return launch_few_merge(f.kl, a.partial, f.max_slices, f.few_rows, pair_q, pair_bucket, idx->bucket_off, idx->gpos,
+                            idx->n_rows, P, k, out_d, out_pos, status, s);
 }

@@ -315,6 +315,14 @@ int launch_prep_mx6(const float* q, int32_t nq, int32_t ldq, int32_t d, int32_t 
 constexpr int kMx6DPad = 768;
 // the widest row of the few-query scan (lmi_scan_few.hip: its query image in LDS)
 constexpr int kFewMaxDPad = 992;
+// few_merge_kernel (kl 10 / 16), one wave per grouped pair: the pair's slice
+// lists partial[pp][slice][kl], ceil((off[c + 1] - off[c]) / few_rows) of them
+// for a pair of bucket c, down to k entries by (distance, row).  off: the
+// buckets' row offsets -- or, for the subset scan (lmi_scan_subset.hip), their
+// offsets into the sorted allow-list, few_rows then its slice length
+int launch_few_merge(int kl, const uint64_t* partial, int32_t max_slices, int32_t few_rows, const int32_t* pair_q,
+                     const int32_t* pair_bucket, const int64_t* off, const int32_t* gpos, int64_t n_rows, int32_t P,
+                     int32_t k, float* out_d, int32_t* out_pos, int32_t* status, hipStream_t s);
 
 // ---- the scan's plan (lmi_scan.hip) -----------------------------------------
 // Every choice a scan of (idx, nq, R, k, qmode, lo) makes, made once: the

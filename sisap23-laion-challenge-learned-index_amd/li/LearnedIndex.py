@@ -344,8 +344,13 @@ class LearnedIndex(Logger):
     # ---- search -------------------------------------------------------------
     def search(self, data_navigation, queries_navigation, data_search, queries_search,
                pred_categories, n_buckets=1, k=10, use_threshold=False, semantics="reference",
-               stop_mass=None, min_buckets=1, timings=None, want=None, avoid=None, few=False):
+               stop_mass=None, min_buckets=1, timings=None, want=None, avoid=None, few=False, subset=None):
         """Search for k nearest neighbors of each query (LearnedIndex.py:22-101).
+        `subset` (an addition; default None, every object): the ids of the objects
+        that may answer, one collection for the batch -- the answer of this search
+        over those objects alone (Searcher.search(subset=)), float32 distances;
+        KeyError for an id that is not stored, ValueError for duplicates and for
+        what li.index.check_subset names.
         `few` (an addition; default off, nothing turns it on): the scan of
         Searcher.search(few=True), for a handful of queries -- float32 distances;
         ValueError for what li.index.check_few names.
@@ -379,10 +384,11 @@ class LearnedIndex(Logger):
                                                 n_buckets, k=k, k_round=10,
                                                 use_threshold=use_threshold, semantics=semantics,
                                                 dist="f64" if rerank is not None else
-                                                "f32" if index.storage in ("i8", "mx4", "mx6") or index.metric != "cosine" or few else
+                                                "f32" if index.storage in ("i8", "mx4", "mx6") or index.metric != "cosine" or few or subset is not None else
                                                 dist_dtype(data_search, queries_search),
                                                 stop_mass=stop_mass, min_probes=min_buckets,
-                                                timings=timings, want=want, avoid=avoid, rerank=rerank, few=few)
+                                                timings=timings, want=want, avoid=avoid, rerank=rerank, few=few,
+                                                subset=subset)
 
     def range_search(self, data_navigation, queries_navigation, data_search, queries_search,
                      pred_categories, radius, n_buckets=1, stop_mass=None, min_buckets=1, want=None,

@@ -89,6 +89,8 @@ EXPORTS = (
     "lmi_bucket_topk_metric",
     "lmi_scan_few_workspace_bytes",
     "lmi_bucket_topk_few",
+    "lmi_scan_subset_workspace_bytes",
+    "lmi_bucket_topk_subset",
     "lmi_row_sqnorms",
     "lmi_scan_tagged_workspace_bytes",
     "lmi_bucket_topk_tagged",
@@ -230,6 +232,9 @@ _SIGNATURES = {
     "lmi_scan_few_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_few": (C.c_int, [C.POINTER(IndexDesc), _P, _I32, _I32, _P, _I32, _I32, _I32, _P, C.c_size_t,
                                       _P, _P, _P, _P]),
+    "lmi_scan_subset_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I64, _I32, _I32, _I32, _I32, _I32]),
+    "lmi_bucket_topk_subset": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I32, _I32,
+                                         _I32, _P, C.c_size_t, _P, _P, _P, _P]),
     "lmi_row_sqnorms": (C.c_int, [_P, _I32, _I64, _I64, _I32, _P, _P, _P]),
     "lmi_scan_tagged_workspace_bytes": (C.c_size_t, [C.POINTER(IndexDesc), _I32, _I32, _I32, _I32]),
     "lmi_bucket_topk_tagged": (C.c_int, [C.POINTER(IndexDesc), _P, _P, _P, _I32, _I32, _P, _I32, _I32,

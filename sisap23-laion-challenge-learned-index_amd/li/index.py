@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib, index_update
+from . import subset as subset_mod
 from ._lib import check, ptr
 from .index_update import DEFAULT_DIRECT_ROWS, DEFAULT_SLAB_ROWS, STAGING_MAX_BYTES  # noqa: F401
 from .layout import DEFAULT_CHUNK_ROWS, BucketLayout, check_tags, default_chunk_rows, eligible_counts  # noqa: F401
@@ -206,6 +207,7 @@ REFUSALS = {
         # (the default path would scan such queries in exact fp32; this kernel rounds them to fp16)
         "batch": "fp16-exact queries (LMI_Q_F16) alone: a value of this batch is not fp16-representable",
     }.items()}),
+    "subset": (lambda s, m: True, subset_mod.ROWS),  # (of the call too: search inside an id allow-list, li/subset.py)
 }
 
 
@@ -267,6 +269,14 @@ def check_few(index: DeviceIndex, nq: int, R: int, k: int, few_rows=None, **flag
         "few_rows" if few_rows is not None and (few_rows <= 0 or few_rows % 32) else None
     if row:
         refuse("few", index, row, nq=nq, R=R, k=k, d_pad=index.d_pad, few_rows=few_rows)
+
+
+def check_subset(index: DeviceIndex, k: int, sub_rows=None, **flags) -> None:
+    """ValueError for what a call with `subset=` does not take (li.subset.ROWS), before anything is uploaded,
+    allocated or launched; `flags`: the call's other keywords, and exchange=True for a Searcher that exchanges."""
+    row = subset_mod.refusal(index, k, sub_rows, **flags)
+    if row:
+        refuse("subset", index, row, k=k, d_pad=index.d_pad, sub_rows=sub_rows)
 
 
 _FILTERED = "filtered search (want / avoid)"  # the feature's name where a metric or an MX storage refuses it
@@ -1233,7 +1243,7 @@ class DeviceIndex:
 
     def _workspace(self, key: str, need: int, ws=None, what: str = "scan") -> torch.Tensor:
         """A workspace of at least `need` bytes for the call named `what`: the caller's `ws` after a size check, or
-        the index's own under the cache key `key` ("buf": the float32 scans, "f64", "range", "few"), which a later
+        the index's own under the cache key `key` ("buf": the float32 scans, "f64", "range", "few", "subset"), which a later
         call that needs more replaces."""
         if ws is not None:
             return _workspace(ws, need, what)
@@ -1470,8 +1480,17 @@ def _triple(out, shape, dtype, device, status=None):
 def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: int,
                 qmode: Optional[int] = None, stream=None, out=None, ws=None,
                 seed_round0: bool = False, phases: int = 0, want=None, avoid=None, lists16: bool = False,
-                few: bool = False, few_rows: Optional[int] = None):
-    """K2 on one shard.  `few` (nothing sets it for the caller): the few-query
+                few: bool = False, few_rows: Optional[int] = None, subset=None, sub_rows: Optional[int] = None):
+    """K2 on one shard.  `subset` (None: every row, today's path): stored ids, a host or
+    device integer array in any order, or a li.subset.Subset prepared once --
+    each list is then the exact top-k, by (distance, position), of the probed
+    bucket's rows whose id is in the subset, padded (+inf, -1) like an
+    under-full bucket's (lmi_bucket_topk_subset: the rows are fetched by
+    position, so the bytes read follow the subset); `sub_rows`: entries of the
+    subset per work item (None: the call chooses).  KeyError for an id the index
+    does not hold, ValueError for duplicates and for what check_subset names.
+    An empty subset gives all-padding lists and launches no scan.
+    `few` (nothing sets it for the caller): the few-query
     scan, lmi_bucket_topk_few -- at most 256 pairs, each probed bucket cut into
     slices of `few_rows` rows (None: the call chooses) so that one query spreads
     over every CU; ValueError for what check_few names.  Returns (d [nq,R,k] f32, pos [nq,R,k] int32, status int32 tensor);
@@ -1492,6 +1511,11 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
     k = 11..16 on the ring's 16-entry lists; the workspace is sized there too)."""
     tagged = want is not None or avoid is not None
     _check_few_rows(few, few_rows)
+    if sub_rows is not None and subset is None:
+        raise ValueError("sub_rows comes with subset=")
+    if subset is not None:  # (refused before anything is uploaded)
+        check_subset(index, k, sub_rows, qmode=qmode, seed_round0=seed_round0, phases=phases, want=want, avoid=avoid,
+                     lists16=lists16, few=few)
     # (no context object on the eager path: entered on demand, left in the finally)
     ctx = i8_lists16().__enter__() if lists16 else None
     try:
@@ -1502,6 +1526,23 @@ def bucket_topk(index: DeviceIndex, q: torch.Tensor, classes: torch.Tensor, k: i
                 check_metric(index, f"k = {k} > {_lib.LMI_MAX_K}")
         lib = _lib.load()
         q, classes, nq, R = _call_head(index, q, classes)
+        if subset is not None:
+            sub = subset_mod.prepare(index, subset)
+            out_d, out_pos, status = _triple(out, (nq, R, k), torch.float32, index.device)
+            if sub.n == 0:
+                out_d.fill_(float("inf"))
+                out_pos.fill_(-1)
+                return out_d, out_pos, status
+            desc, sr = index.desc, int(sub_rows or 0)
+            need = lib.lmi_scan_subset_workspace_bytes(C.byref(desc), sub.n, sub.max_range, nq, R, k, sr)
+            if need == 0 and nq > 0:
+                raise ValueError(f"subset=: {lib.lmi_last_error().decode(errors='replace')}")
+            ws = index._workspace("subset", need, ws)
+            check("lmi_bucket_topk_subset", lib.lmi_bucket_topk_subset(
+                C.byref(desc), ptr(sub.pos), ptr(sub.off), sub.n, sub.max_range, ptr(q), nq, q.stride(0),
+                ptr(classes), R, k, sr, ptr(ws), ws.numel(), ptr(out_d), ptr(out_pos), ptr(status),
+                _stream(stream, index.device)))
+            return out_d, out_pos, status
         if few:
             check_few(index, nq, R, k, few_rows, qmode=qmode, seed_round0=seed_round0, phases=phases, want=want,
                       avoid=avoid, lists16=lists16)
@@ -2125,7 +2166,7 @@ class Searcher:
         return mode
 
     def _scan(self, q_search, classes, k_list: int, qmode: int, f64: bool, lap=None,
-              status_out=None, ws=None, seed_round0: bool = False, want=None, rerank=None, few=None):
+              status_out=None, ws=None, seed_round0: bool = False, want=None, rerank=None, few=None, subset=None):
         """K2 on this shard (+ all-gather and K3 for G > 1 ranks, the status
         words riding along so every rank sees every rank's bits).  `lap`
         (measurement only) is called after the scan and after the exchange.
@@ -2134,9 +2175,18 @@ class Searcher:
         want words of a filtered scan (want_words; float32 lists only).
         `rerank` (checked by check_rerank; f64, one GPU): the 8-bit scan keeps
         `rerank` entries a pair and rerank_f64 cuts them to k_list float64 ones.
-        `few` = (few_rows,): the few-query scan (_checked made the checks)."""
+        `few` = (few_rows,): the few-query scan (_checked made the checks).
+        `subset` = (Subset, sub_rows): the scan inside an allow-list (likewise)."""
         nq, R = classes.shape
         dev = self.index.device
+        if subset is not None:
+            if qmode != _lib.LMI_Q_F16:
+                refuse("subset", self.index, "batch")
+            d, pos, status = bucket_topk(self.index, q_search, classes, k_list, subset=subset[0], sub_rows=subset[1],
+                                         out=_triple(None, (nq, R, k_list), torch.float32, dev, status_out))
+            if lap:
+                lap("scan")
+            return d, pos, status
         if few is not None:
             if qmode != _lib.LMI_Q_F16:
                 refuse("few", self.index, "batch")
@@ -2201,8 +2251,13 @@ class Searcher:
     def lists(self, q_nav: torch.Tensor, q_search: torch.Tensor, R: int, k_list: int,
               classes: Optional[torch.Tensor] = None, dist: str = "f32", stop_mass=None,
               min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
-              lists16: bool = False, few: bool = False, few_rows: Optional[int] = None):
+              lists16: bool = False, few: bool = False, few_rows: Optional[int] = None, subset=None,
+              sub_rows: Optional[int] = None):
         """Device part: router + scan (+ RCCL merge).  Returns device tensors.
+        `subset`, `sub_rows`: as in bucket_topk -- one collection of stored ids for
+        the whole batch; float32 lists on one GPU, ValueError for what
+        check_subset names and for a batch with a value that is not
+        fp16-representable.
         `few` (nothing sets it for the caller): the scan is the few-query one,
         bucket_topk(few=True) -- float32 lists of at most 256 pairs on one GPU,
         `few_rows` rows a slice (None: the call chooses); ValueError for what
@@ -2227,13 +2282,16 @@ class Searcher:
         ValueError, like every refusal of `want`, before anything is launched."""
         ctx = i8_lists16().__enter__() if lists16 else None
         try:
+            sub = self._checked_subset(subset, sub_rows, k_list, q_search, dist=dist, want=want, avoid=avoid,
+                                       rerank=rerank, lists16=lists16, few=few)
             k_list, want, rerank = self._checked(k_list, R, q_search, classes, dist, stop_mass, min_probes, want,
                                                  avoid, rerank, lists16, few, few_rows)
             if classes is None:
                 classes = self.route(q_nav, R, stop_mass=stop_mass, min_probes=min_probes)
             q_search = _rows_q(q_search, self.index.device)
             d, pos, status = self._scan(q_search, classes, k_list, self.qmode(q_search), dist == "f64",
-                                        want=want, rerank=rerank, few=(few_rows,) if few else None)
+                                        want=want, rerank=rerank, few=(few_rows,) if few else None,
+                                        subset=None if sub is None else (sub, sub_rows))
             return classes, d, pos, status
         finally:
             if ctx is not None:
@@ -2264,6 +2322,20 @@ class Searcher:
             want_w = filter_words(ix, want, avoid, int((q_search if classes is None else classes).shape[0]),
                                   *((k_list, dist) if rerank is None else (rerank, "f32")), per_query=per_query)
         return k_list, want_w, rerank
+
+    def _checked_subset(self, subset, sub_rows, k_list: int, q_search, **flags):
+        """The `subset=` of lists / search before the router is launched: check_subset with what the Searcher
+        adds (float32 lists, no re-rank, one process, a batch of fp16-exact queries), then the prepared Subset
+        (None: no subset)."""
+        if subset is None:
+            if sub_rows is not None:
+                raise ValueError("sub_rows comes with subset=")
+            return None
+        check_subset(self.index, k_list, sub_rows, exchange=self.exchange, **flags)
+        self.index._check_live()
+        if self.qmode(_rows_q(q_search, self.index.device)) != _lib.LMI_Q_F16:
+            refuse("subset", self.index, "batch")
+        return subset_mod.prepare(self.index, subset)
 
     def _check_list_shape(self, k_list: int, dist: str, rerank=None) -> None:
         """The lists a call may ask of this index: float32 ones of at most LMI_MAX_K entries where a metric or a
@@ -2326,8 +2398,9 @@ class Searcher:
 
     def range_search(self, q_nav, q_search, R: int, radius, *, classes: Optional[torch.Tensor] = None,
                      dist: str = "f32", stop_mass=None, min_probes: int = 1, want=None, avoid=None,
-                     pair_cap: int = 256, timings: Optional[dict] = None):
-        """Every object of each query's probed buckets within `radius` of it
+                     pair_cap: int = 256, timings: Optional[dict] = None, subset=None):
+        """(`subset`: refused -- a range search inside an id allow-list is not offered.)
+        Every object of each query's probed buckets within `radius` of it
         (K11) -> host arrays (lims int64 [nq + 1], dists float64 [total], anns
         uint32 [total]): query i owns entries lims[i]:lims[i + 1], ordered by
         (distance, global position); the comparison d <= radius is inclusive.
@@ -2371,6 +2444,8 @@ class Searcher:
         float64 d > 1024; in either arithmetic d_pad > 1248 (the collect
         scan's query tile would not fit a workgroup's LDS)."""
         import time
+        if subset is not None:
+            refuse("subset", self.index, "range")
         check_stop(stop_mass, min_probes)
         ix = self.index
         ix._check_live()
@@ -2512,6 +2587,8 @@ class Searcher:
     def streamed(self, q_nav, q_search, R: int, k: int = 10, **kw) -> "StreamedSearch":
         """The step as a four-stage pipeline of captured graphs over a stream
         of batches (StreamedSearch); answers equal search(...) per batch."""
+        if kw.pop("subset", None) is not None:
+            refuse("subset", self.index, "streamed")
         check_i8(self.index, "streamed() (the batch stream)")
         check_metric(self.index, "streamed() (the batch stream)")
         from .stream import StreamedSearch
@@ -2521,6 +2598,8 @@ class Searcher:
         """The step captured as a HIP graph (GraphedSearch), from the batch in
         host memory to the answer in host memory: same results as
         search(..., semantics="reference", replay_on="device")."""
+        if kw.pop("subset", None) is not None:
+            refuse("subset", self.index, "streamed")
         check_i8(self.index, "graph() (the captured step)")
         check_metric(self.index, "graph() (the captured step)")
         from .graphed import GraphedSearch
@@ -2531,8 +2610,14 @@ class Searcher:
                timings: Optional[dict] = None, replay_on: str = "device",
                semantics: str = "reference", dist: str = "f32", stop_mass=None,
                min_probes: int = 1, want=None, avoid=None, rerank: Optional[int] = None,
-               lists16: bool = False, few: bool = False, few_rows: Optional[int] = None):
+               lists16: bool = False, few: bool = False, few_rows: Optional[int] = None, subset=None,
+               sub_rows: Optional[int] = None):
         """Whole hot path for one batch -> (dists f64 [nq, w], anns u32 [nq, w]).
+
+        `subset`, `sub_rows`: as in lists -- search inside an id allow-list, one for
+        the batch: the answer of this search on the index built from the
+        subset's rows alone (semantics="reference": the replay reads every
+        bucket's subset row count as its size).  Never seeded.
 
         `few`, `few_rows`: as in lists -- the scan alone changes; K3, the replay,
         `stop_mass` and both semantics run unchanged on its lists (never seeded).
@@ -2592,6 +2677,9 @@ class Searcher:
             raise ValueError("dist must be 'f32' or 'f64'")
         ctx = i8_lists16().__enter__() if lists16 else None
         try:
+            sub = self._checked_subset(subset, sub_rows, k_round if semantics == "reference" else max(k_round, k),
+                                       q_search, dist=dist, want=want, avoid=avoid, rerank=rerank, lists16=lists16,
+                                       few=few)
             k_list, want_w, rerank = self._checked(
                 k_round if semantics == "reference" else max(k_round, k), R, q_search, classes, dist, stop_mass,
                 min_probes, want, avoid, rerank, lists16, few, few_rows, per_query=semantics == "exact")
@@ -2622,7 +2710,7 @@ class Searcher:
             # the running threshold then never exceeds round 0's k-th distance;
             # with k > k_round the first merge pads with 10000s)
             seed = (semantics == "reference" and use_threshold and k <= k_round and _SEED_ROUND0
-                    and want_w is None and self.index.metric == "cosine" and not few)
+                    and want_w is None and self.index.metric == "cosine" and not few and sub is None)
             h_st = self._host("st", (2,), torch.int32)
             # the device replay's arm: the answer and both status words in one buffer, one D2H copy
             ans, w_ans = None, k_round if classes.shape[1] == 1 else k
@@ -2633,7 +2721,7 @@ class Searcher:
                     ans = answer_buffer(nq, w_ans, dev)
                 return self._scan(q_search, classes, k_list, mode, f64, lap_scan,
                                   status_out=None if ans is None else ans[3][0:1], seed_round0=seed, want=want_w,
-                                  rerank=rerank, few=few_arg)
+                                  rerank=rerank, few=few_arg, subset=None if sub is None else (sub, sub_rows))
 
             def check_status(st, rst=0):
                 # every rank holds the OR of all ranks' scan bits (they rode the
@@ -2667,7 +2755,7 @@ class Searcher:
                 def finish(d, pos, status):
                     bsz, p2id = self._device_tables()
                     replay_device(classes, d, pos, k_round=k_round, k_final=k, pos_to_id=p2id,
-                                  bucket_size=bsz if want_w is None else torch.from_numpy(
+                                  bucket_size=bsz if want_w is None and sub is None else torch.from_numpy(
                                       np.ascontiguousarray(bsize, dtype=np.int64)).to(dev),
                                   use_threshold=use_threshold, out=(ans[1], ans[2], ans[3][1:2]))
                     # a fresh pinned buffer from torch's caching host allocator,
@@ -2699,6 +2787,8 @@ class Searcher:
             bsize = self.index.bucket_size
             if want_w is not None and semantics == "reference":
                 bsize = self.eligible_bucket_size(int(want or 0), int(avoid or 0))
+            if sub is not None:  # (likewise: the subset's rows of every bucket)
+                bsize = sub.bucket_size
             answer, st, rst = finish(d, pos, status)
             if check_status(st, rst):
                 # the cached fp16 check was stale: redo once with exact fp32 MFMA, its stages untimed -- on the

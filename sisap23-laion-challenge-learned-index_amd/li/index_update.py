@@ -211,6 +211,24 @@ def _edit_words(words, n: int, name: str) -> np.ndarray:
     return np.array(np.broadcast_to(w.astype(np.uint32), (n,)))   # (a copy: broadcast views are read-only)
 
 
+def positions_of(index, ids: np.ndarray) -> np.ndarray:
+    """The positions of the int64 `ids` (one row each: ids are unique in an index), in the caller's order: a
+    sorted search of pos_to_id, whose order is worked out on the first call for an index and kept (the table
+    never changes in an index's life; a repeated edit, as deletes by tombstone are, or a search inside an
+    allow-list then costs log n an id).  UnknownIds for an id the index does not hold."""
+    n = int(ids.size)
+    by_id = index.__dict__.get("_by_id")
+    if by_id is None:
+        by_id = index._by_id = np.argsort(index.pos_to_id, kind="stable")
+    at = np.searchsorted(index.pos_to_id, ids, sorter=by_id)
+    pos = by_id[np.minimum(at, by_id.size - 1)] if by_id.size else np.zeros(n, np.int64)
+    found = (index.pos_to_id[pos] == ids) if by_id.size else np.zeros(n, bool)
+    if not found.all():
+        missing = np.unique(ids[~found])
+        raise UnknownIds(f"ids not in the index: {missing[:8].tolist()}" + (" ..." if missing.size > 8 else ""))
+    return pos
+
+
 @torch.no_grad()
 def edit_tags(index, ids, set_bits, clear_bits) -> None:
     """DeviceIndex.edit_tags: the host table and the device words of `index` itself, one launch of
@@ -230,18 +248,7 @@ def edit_tags(index, ids, set_bits, clear_bits) -> None:
     uniq = np.unique(ids)
     if uniq.size != n:
         raise ValueError("edit_tags: duplicate ids")
-    # positions of the ids (one row each: ids are unique in an index), in the caller's order: a sorted
-    # search of pos_to_id, whose order is worked out on the first edit of an index and kept (the table
-    # never changes in an index's life; a repeated edit, as deletes by tombstone are, then costs log n an id)
-    by_id = index.__dict__.get("_by_id")
-    if by_id is None:
-        by_id = index._by_id = np.argsort(index.pos_to_id, kind="stable")
-    at = np.searchsorted(index.pos_to_id, ids, sorter=by_id)
-    pos = by_id[np.minimum(at, by_id.size - 1)] if by_id.size else np.zeros(n, np.int64)
-    found = (index.pos_to_id[pos] == ids) if by_id.size else np.zeros(n, bool)
-    if not found.all():
-        missing = np.unique(ids[~found])
-        raise UnknownIds(f"ids not in the index: {missing[:8].tolist()}" + (" ..." if missing.size > 8 else ""))
+    pos = positions_of(index, ids)
     if n == 0:
         return
     dev = index.device
